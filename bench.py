@@ -11,10 +11,16 @@ the pinned DiffCSP network stands in at the same B / n / T.
 A "step" is ONE denoising step of the chain over the whole batch (corrector eval + update +
 predictor eval + update + log-probs).  Per-step cost does not depend on t, so
     value = n_gpus * B * K / (T * elapsed)          [complete 1000-step structures per second]
-The default K = 1000 is one complete chain.  For N > 1 every rank samples its own B crystals
+The default K = 1000 is one complete chain; K > 1000 times consecutive chains from the same initial
+state (1000 steps each, the remainder last).  For N > 1 every rank samples its own B crystals
 (independent units, no data-path collective): weak scaling.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds everything
+else: the CPU baseline, the live counter traffic of the edge stage, and the secondary legs under
+`extra` (exact-fp32 path, recording chain, TF32-class build, MatterGen-shaped sampler, fine-tune).
+--dump-outputs DIR writes the arrays the last timed call returned as DIR/<name>.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
 import argparse
@@ -844,6 +850,29 @@ def tf32_class_leg(args, K, W):
         return {"error": repr(e)}
 
 
+def chain_segments(n):
+    """Lengths of the sampler calls that make up n denoising steps: whole chains of T steps, the remainder last."""
+    return [T] * (n // T) + ([n % T] if n % T else [])
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, suffix=""):
+    """--dump-outputs: every tensor the timed call returned, as <out_dir>/<name><suffix>.npy -- float32 for floating-point tensors,
+    float64 for integer ones (exact at these sizes)."""
+    host = {}
+    for name, t in sorted(arrays.items()):
+        if torch.is_tensor(t):
+            a = t.detach().cpu().numpy()
+            host[name] = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_LIMIT_BYTES, f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def resolve_batch(args):
     """--scaling strong: ONE global batch of 256 crystals (north_star: "batch 256 ... >= 6x at 8 GPUs"), B / N crystals per rank, global ids in the noise
     counters as always (so the N-rank samples are the 1-rank samples).  --batch: the per-GPU batch directly -- the per-rank shapes of a strong-scaling run
@@ -871,6 +900,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="besides the headline: CPU baseline, live counter traffic (rocprofv3 child runs) and the "
+                    "secondary legs under `extra`; a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="--mode sample: write the arrays the last timed call returned as "
+                    "DIR/<name>.npy (float32 / float64; ranks > 0 add _rank<r> to the name)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--ft-groups", type=int, default=None, help="--mode ft: crystal groups fine-tuned concurrently (default: automatic)")
     ap.add_argument("--streams", type=int, default=4, help="crystal groups of the batch sampled concurrently on separate HIP "
@@ -916,7 +949,8 @@ def main():
         os.environ["MI_LIB_PATH"] = _b.build(verbose=False, variant="tf32")
         args.path = "split-gemm"
     K, W = args.steps, args.warmup
-    assert 1 <= K <= T and 0 <= W <= T, f"steps and warmup must be <= T = {T}"
+    assert K >= 1 and W >= 0, "steps must be >= 1 and warmup >= 0"
+    k_last = chain_segments(K)[-1]   # steps of the last timed call (= K up to T)
 
     ctx = dist_setup(args.gpus)
     world, rank, local_rank, share, dist = ctx
@@ -957,8 +991,8 @@ def main():
     if gc_early:
         gc.collect()   # (everything the host has to do between the warm-up and the window is done BEFORE the warm-up: a generation-2 collection of a torch
         #  process takes tens of ms, during which an idle part drops its power state -- the warm-up steps are meant to be the last thing the GPU did)
-    if W > 0:
-        m.sample(cb, seed=SEED_NOISE + 1, t_start=T, t_stop=T - W, **skw)
+    for n in chain_segments(W):
+        m.sample(cb, seed=SEED_NOISE + 1, t_start=T, t_stop=T - n, **skw)
     if not gc_early:
         gc.collect()
     gc.disable()   # (as timeit does: a 20-step window is 0.1 s, a generation-2 collection of a torch process several ms of it; re-enabled right behind the window)
@@ -966,7 +1000,8 @@ def main():
         barrier()
         _lib.check(lib.mi_profile_enable(m.decoder._h, 1))
         t0 = time.perf_counter()
-        final, _ = m.sample(cb, seed=SEED_NOISE, init=state, t_start=T, t_stop=T - K, **skw)
+        for n in chain_segments(K):
+            final, _ = m.sample(cb, seed=SEED_NOISE, init=state, t_start=T, t_stop=T - n, **skw)
         barrier()
         elapsed = time.perf_counter() - t0
     finally:
@@ -978,6 +1013,8 @@ def main():
     if args.counter_child:   # (under rocprofv3 --pmc: the dispatches are what is wanted, nothing is printed)
         torch.cuda.synchronize()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, final, "" if rank == 0 else f"_rank{rank}")
     finite = all(bool(torch.isfinite(v).all()) for v in (final["frac_coords"], final["lattices"], final["atom_types"]))
     sat = _lib.saturation_events(reset=True)   # fp16-plane conversions that clamped during the run (0 = the format held)
 
@@ -1007,9 +1044,10 @@ def main():
         # HBM-side bytes per launch, MEASURED BY THIS RUN: two short child runs of this same command line under rocprofv3 (--pmc
         # FETCH_SIZE, then --pmc WRITE_SIZE: separate passes, corrected as the MI355X guide prescribes), after the timed region.  A
         # property of the code that was just timed -- no committed file can go stale behind a kernel change.  null (with the reason)
-        # when rocprofv3 is missing or a pass fails; --no-counters skips the passes.
-        traffic, traffic_src = None, {"measured": "skipped (--no-counters)" if args.no_counters else "not applicable to this path / world size"}
-        if args.path == "split-gemm" and world == 1 and not args.no_counters:
+        # when rocprofv3 is missing or a pass fails; --no-counters skips the passes, and only --full runs them.
+        traffic, traffic_src = None, {"measured": "skipped (--no-counters)" if args.no_counters else "not applicable to this path / world size" if args.full
+                                      else "not measured (a plain run; --full measures it)"}
+        if args.full and args.path == "split-gemm" and world == 1 and not args.no_counters:
             traffic, traffic_src = measure_traffic_live(args)
         out = {
             "metric": "crystal structures/sec (1000-step reverse diffusion)", "value": value, "unit": "structures/s",
@@ -1025,7 +1063,7 @@ def main():
                        "record": False,
                        "record_note": "per-step log-probabilities not computed and the T+1 states not kept in the timed region (SURVEY 8(d) config 2: recording off "
                                       "for timing, on for parity); the reference computes and keeps both on every step (models/diffcsp/diffusion.py:353-390) -- "
-                                      "extra.recording_chain is the same window with record=True",
+                                      "extra.recording_chain (--full) is the same window with record=True",
                        "gc_disabled_in_window": True},
             "roofline": {"bound": "mfma", "kernel": kernel, "achieved": issued, "peak": peak,
                          "unit": "TFLOP/s", "frac": issued / peak, "traffic": traffic, "traffic_source": traffic_src,
@@ -1047,7 +1085,7 @@ def main():
                            "hbm_frac_section8d": (y_eval * 2 * B * K / elapsed) / (PEAK_HBM_TBPS * 1e12),
                            "edge_stage_share_of_step": busy_ms * 1e-3 / elapsed},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if args.path == "split-gemm":
                 # the precision trade, visible in every record: the same workload on the exact-fp32 path (f32-input MFMA, register-
                 # chained edge stage, bit-for-bit an fp32 fma chain), a short run outside the timed region
@@ -1064,19 +1102,19 @@ def main():
                                                     "dtype": "f32 (v_mfma_f32_32x32x2_f32)"}}
                 set_gemm_mode("split")
                 m.decoder.set_edge_mode("gemm")
-                # what the timed region leaves out, priced: the same K steps from the same state with record=True -- every step's state kept on the
+                # what the timed region leaves out, priced: the last timed call's steps from the same state with record=True -- every step's state kept on the
                 # device and its three log-probabilities computed (21-image wrapped-normal sums, block reductions), as diffusion.py:353-390 does
                 try:
                     m.sample(cb, seed=SEED_NOISE + 1, t_start=T, t_stop=T - 2, record=True, **skw)
                     torch.cuda.synchronize()
                     tr = time.perf_counter()
-                    fin_r, traj_r = m.sample(cb, seed=SEED_NOISE, init=state, t_start=T, t_stop=T - K, record=True, **skw)
+                    fin_r, traj_r = m.sample(cb, seed=SEED_NOISE, init=state, t_start=T, t_stop=T - k_last, record=True, **skw)
                     torch.cuda.synchronize()
                     tr = time.perf_counter() - tr
                     same = all(bool(torch.equal(fin_r[k], final[k])) for k in ("frac_coords", "lattices", "atom_types"))
-                    kept = sorted(k for k in traj_r[T - K + 1]) if (T - K + 1) in traj_r else []
-                    out["extra"]["recording_chain"] = {"value": B * K / (T * tr), "unit": "structures/s", "steps": K, "ms_per_step": tr * 1e3 / K, "record": True,
-                                                       "relative_to_headline": (B * K / (T * tr)) / value, "states_kept": len(traj_r), "fields_per_state": kept,
+                    kept = sorted(k for k in traj_r[T - k_last + 1]) if (T - k_last + 1) in traj_r else []
+                    out["extra"]["recording_chain"] = {"value": B * k_last / (T * tr), "unit": "structures/s", "steps": k_last, "ms_per_step": tr * 1e3 / k_last, "record": True,
+                                                       "relative_to_headline": (B * k_last / (T * tr)) / value, "states_kept": len(traj_r), "fields_per_state": kept,
                                                        "final_state_bit_identical_to_timed_chain": same,
                                                        "note": "record=True: states of all steps retained + log_prob_l / log_prob_t / log_prob_x per step (for t > 1)"}
                     del fin_r, traj_r

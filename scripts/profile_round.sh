@@ -19,7 +19,8 @@ d = json.load(open(p)); d["head"] = "$HEAD"; d["command"] = "$CMD"
 json.dump(d, open(p, "w"), indent=1)
 PY
 rm -rf $O   # the raw databases are tens of MiB; the summaries are what is kept
-python bench.py --steps 20 --warmup 3 > gpurun_out/${TAG}_bench_default_steps20.json 2>/dev/null
-python bench.py > gpurun_out/${TAG}_bench_default.json 2>/dev/null
+R=$(dirname $O)   # the results directory
+python bench.py --steps 20 --warmup 3 --full > $R/${TAG}_bench_default_steps20.json 2>/dev/null
+python bench.py --full > $R/${TAG}_bench_default.json 2>/dev/null
 python bench.py --mode ft > gpurun_out/${TAG}_bench_finetune.json 2>/dev/null
 tail -c 300 gpurun_out/${TAG}_bench_default.json; sed -n 7,16p gpurun_out/${TAG}_rocprofv3_summary.md | cut -c1-150

@@ -109,3 +109,23 @@ def test_strong_scaling_shards_one_global_batch_of_256(bench):
         bench.resolve_batch(ns(gpus=3, scaling="strong"))
     bench.resolve_batch(ns())     # (back to the default for whoever imports the module next)
     assert bench.B == 256
+
+
+def test_steps_beyond_one_chain_are_whole_chains_then_the_remainder(bench):
+    """--steps K times K denoising steps for any K >= 1: consecutive calls of T = 1000 steps from the initial state, the remainder last."""
+    assert bench.chain_segments(0) == [] and bench.chain_segments(1) == [1] and bench.chain_segments(1000) == [1000]
+    assert bench.chain_segments(2500) == [1000, 1000, 500] and sum(bench.chain_segments(3001)) == 3001
+
+
+def test_dump_outputs_writes_float_arrays_of_every_returned_tensor(bench, tmp_path):
+    import numpy as np
+    final = dict(frac_coords=torch.rand(6, 3), lattices=torch.rand(2, 3, 3, dtype=torch.float64), num_atoms=torch.tensor([2, 4]), label="not an array")
+    bench.dump_outputs(str(tmp_path / "o"), final)
+    bench.dump_outputs(str(tmp_path / "o"), final, "_rank1")
+    got = {p.name: np.load(p) for p in (tmp_path / "o").iterdir()}
+    assert set(got) == {f"{k}{s}.npy" for k in ("frac_coords", "lattices", "num_atoms") for s in ("", "_rank1")}
+    assert got["frac_coords.npy"].dtype == np.float32 and np.array_equal(got["frac_coords.npy"], final["frac_coords"].numpy())
+    assert got["lattices.npy"].dtype == np.float32 and got["num_atoms.npy"].dtype == np.float64 and got["num_atoms.npy"].tolist() == [2.0, 4.0]
+    with pytest.raises(AssertionError, match="limit"):
+        bench.dump_outputs(str(tmp_path / "big"), dict(x=torch.zeros(17 << 20)))
+    assert not (tmp_path / "big").exists()
