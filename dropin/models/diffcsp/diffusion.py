@@ -1,1 +1,1 @@
-from matinvent_amd.diffcsp import DiffCSPModule, SinusoidalTimeEmbeddings, MAX_ATOMIC_NUM  # noqa: F401
+from matinvent_amd.diffcsp import DiffCSPModule, SinusoidalTimeEmbeddings, MAX_ATOMIC_NUM, log_prob_wn, p_wrapped_normal  # noqa: F401

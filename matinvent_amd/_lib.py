@@ -156,6 +156,12 @@ SIGNATURES = {
     "mi_profile_read": (_I, [_P, C.POINTER(_L), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
+# the trajectory extension, include/matinvent_hip_traj.h (a header of its own: SIGNATURES above is the boundary header + the debug header)
+TRAJ_SIGNATURES = {
+    "mi_traj_logprob": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "mi_traj_logprob_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -172,7 +178,7 @@ def load():
             f"matinvent_amd: HIP library not found at {LIB_PATH}; build it with `python -m matinvent_amd.build` "
             "(there is no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(TRAJ_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -955,6 +955,7 @@ int net_forward(mi_net* net, mi_batch* b, const float* t_emb, const float* atom_
     const size_t NH = (size_t)N * H;
     Tape& tp = b->tape;
     tp.valid = false;  // this forward overwrites h / hf / x1, which a pending backward would read
+    ++b->fwd_epoch;
     // cspnet.py:243-257: the edge list follows the coordinates.  Inside the sampler's chain (mi_batch::knn_nosync) on the plane-GEMM path the build does not
     // synchronise: b->E is then the capacity, b->e_dev the device-side edge count every consumer below takes its row count from
     if (b->knn) MI_TRY(knn_build(b, frac, lattices, s, b->knn_nosync && !train && g_knn_nosync && MI_PLANES_FP16 && g_gemm_mode == MI_GEMM_SPLIT && net->edge_mode != 0));

@@ -1,0 +1,54 @@
+// Per-step scalars and the log-probability terms of the reverse diffusion (diffusion.py:25-29, 297-368), shared by the sampler's recording
+// (sampler.hip) and the re-evaluation of a recorded step (traj_logprob.hip), so both compute the same formulas the same way.
+// Include after `#pragma clang fp contract(off)`: the arithmetic mirrors the reference's separately-rounded fp32 tensor ops.
+// (pymod1, torch's `x % 1.`, lives in common.h.)
+#pragma once
+#include "common.h"
+
+namespace mi {
+
+struct StepCoef {
+    float c0, c1, sigma, sqrt_sn, step_corr, std_corr, step_pred, std_pred, std_corr_sq, std_pred_sq, sigma_sq, log_sigma;
+};
+__device__ __forceinline__ StepCoef load_coef(const float* coef, int t) {
+    const float* c = coef + (size_t)t * MI_NCOEF;
+    return StepCoef{c[MI_C_C0], c[MI_C_C1], c[MI_C_SIGMA], c[MI_C_SQRT_SN], c[MI_C_STEP_CORR], c[MI_C_STD_CORR],
+                    c[MI_C_STEP_PRED], c[MI_C_STD_PRED], c[MI_C_STD_CORR_SQ], c[MI_C_STD_PRED_SQ], c[MI_C_SIGMA_SQ],
+                    c[MI_C_LOG_SIGMA]};
+}
+
+// log_prob_wn (diffusion.py:25-29): log sum_{i=-10..10} exp(-(x - mu + i)^2 / 2 / sigma^2)
+__device__ __forceinline__ float log_prob_wn(float x, float mu, float sigma_sq) {
+    float p = 0.f;
+    float d = x - mu;
+#pragma unroll
+    for (int i = -10; i <= 10; ++i) {
+        float v = d + (float)i;
+        p += expf(-(v * v) / 2.0f / sigma_sq);
+    }
+    return logf(p);
+}
+// torch.distributions.Normal(mu, sigma).log_prob(v)
+__device__ __forceinline__ float normal_log_prob(float v, float mu, float var, float log_sigma) {
+    float d = v - mu;
+    return -(d * d) / (2.0f * var) - log_sigma - 0.91893853320467274178f;
+}
+
+// log_prob_wn and its derivative with respect to mu in one pass: returns log p (the same operations, in the same order, as log_prob_wn) and
+// *dmu = sum_k w_k (x - mu + k) / sigma^2 / sum_k w_k, w_k = exp(-(x - mu + k)^2 / 2 / sigma^2) -- what torch's autograd of log_prob_wn gives
+// (0 / 0 = NaN where the sum underflows, as there)
+__device__ __forceinline__ float log_prob_wn_dmu(float x, float mu, float sigma_sq, float* dmu) {
+    float p = 0.f, q = 0.f;
+    float d = x - mu;
+#pragma unroll
+    for (int i = -10; i <= 10; ++i) {
+        float v = d + (float)i;
+        float w = expf(-(v * v) / 2.0f / sigma_sq);
+        p += w;
+        q += w * (v / sigma_sq);
+    }
+    *dmu = q / p;
+    return logf(p);
+}
+
+}  // namespace mi

@@ -195,6 +195,13 @@ struct mi_batch {
     hipStream_t hi_stream = nullptr;
     hipEvent_t hi_ev[2] = {nullptr, nullptr};
     Tape tape;
+    uint64_t fwd_epoch = 0;   // bumped by every evaluation of this handle (net_forward): what a pending backward's caller saw must still be current
+    // mi_traj_logprob (traj_logprob.hip): the local derivatives of the last taped call that used this handle -- d log_prob / d(network output),
+    // per element, before the upstream gradient -- and the gradient seeds its backward hands to net_backward (allocated on first use)
+    float *tr_dl = nullptr, *tr_dx = nullptr, *tr_dt = nullptr;      // [B][9], [N][3], [N][A]
+    float *tr_sl = nullptr, *tr_sx = nullptr, *tr_st = nullptr;      // the seeds, same shapes
+    mi_batch* tr_partner = nullptr;                                   // (corrector handle) the predictor handle of that call; NULL: no taped call pending
+    uint64_t tr_epoch = 0, tr_partner_epoch = 0;                      // both handles' fwd_epoch right after that call
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // fork / join of work put on an auxiliary stream (mi_ft_micro_step)
     std::vector<void*> allocs;
 };

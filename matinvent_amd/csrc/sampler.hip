@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "net.h"
+#include "logprob.h"
 
 namespace mi {
 
@@ -41,33 +42,6 @@ __global__ void philox_fill_kernel(uint64_t seed, uint32_t step, uint32_t draw, 
     if (i >= n) return;
     uint64_t e = (uint64_t)(off + i);
     out[i] = uniform ? philox_uniform1(seed, step, draw, e) : philox_normal1(seed, step, draw, e);
-}
-
-struct StepCoef {
-    float c0, c1, sigma, sqrt_sn, step_corr, std_corr, step_pred, std_pred, std_corr_sq, std_pred_sq, sigma_sq, log_sigma;
-};
-__device__ __forceinline__ StepCoef load_coef(const float* coef, int t) {
-    const float* c = coef + (size_t)t * MI_NCOEF;
-    return StepCoef{c[MI_C_C0], c[MI_C_C1], c[MI_C_SIGMA], c[MI_C_SQRT_SN], c[MI_C_STEP_CORR], c[MI_C_STD_CORR],
-                    c[MI_C_STEP_PRED], c[MI_C_STD_PRED], c[MI_C_STD_CORR_SQ], c[MI_C_STD_PRED_SQ], c[MI_C_SIGMA_SQ],
-                    c[MI_C_LOG_SIGMA]};
-}
-
-// log_prob_wn (diffusion.py:25-29): log sum_{i=-10..10} exp(-(x - mu + i)^2 / 2 / sigma^2)
-__device__ __forceinline__ float log_prob_wn(float x, float mu, float sigma_sq) {
-    float p = 0.f;
-    float d = x - mu;
-#pragma unroll
-    for (int i = -10; i <= 10; ++i) {
-        float v = d + (float)i;
-        p += expf(-(v * v) / 2.0f / sigma_sq);
-    }
-    return logf(p);
-}
-// torch.distributions.Normal(mu, sigma).log_prob(v)
-__device__ __forceinline__ float normal_log_prob(float v, float mu, float var, float log_sigma) {
-    float d = v - mu;
-    return -(d * d) / (2.0f * var) - log_sigma - 0.91893853320467274178f;
 }
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {

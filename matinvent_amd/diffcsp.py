@@ -22,6 +22,22 @@ def _scatter_mean(src, index, dim_size):
     return out / cnt.clamp(min=1)
 
 
+def p_wrapped_normal(x, sigma, N=10, T=1.0):
+    """diffusion.py:18-22 (host utility: the device kernels carry their own copy of the sum)."""
+    p_ = 0
+    for i in range(-N, N + 1):
+        p_ += torch.exp(-(x + T * i) ** 2 / 2 / sigma ** 2)
+    return p_
+
+
+def log_prob_wn(x, mu, sigma, N=10, T=1.0):
+    """diffusion.py:25-29: log of the naive 21-image wrapped-normal sum (host utility; csrc/logprob.h is the device form)."""
+    p_ = 0
+    for i in range(-N, N + 1):
+        p_ += torch.exp(-(x - mu + T * i) ** 2 / 2 / sigma ** 2)
+    return torch.log(p_)
+
+
 def _cfg(d, drop=("_target_",)):
     return {k: v for k, v in dict(d).items() if k not in drop}
 
@@ -47,6 +63,16 @@ class _Counts:
 
     def __init__(self, num_atoms):
         self.num_atoms = torch.as_tensor(num_atoms, dtype=torch.long)
+
+
+class _TrajPair:
+    """The corrector's and the predictor's batch handle of forward_logprb for one atom-count vector, and the number of calls made on them
+    (a taped call's backward runs only while it is the latest: the C entry's MI_ESTATE check sees evaluations of the handles, this counter
+    sees which forward_logprb call left them)."""
+
+    def __init__(self, b_corr, b_pred):
+        self.handles = (b_corr, b_pred)
+        self.calls = 0
 
 
 class DiffCSPModule(nn.Module):
@@ -181,6 +207,76 @@ class DiffCSPModule(nn.Module):
     def forward(self, noised_input):
         time_emb, atom_types, frac, lattices, num_atoms, node2graph = noised_input
         return self.decoder(time_emb, atom_types, frac, lattices, num_atoms, node2graph, batch=self._batch_for(num_atoms))
+
+    # ---- trajectory log-probabilities (diffusion.py:158-227) ------------------------------------
+    def _traj_batches(self, num_atoms):
+        """The (corrector, predictor) pair of batch handles forward_logprb evaluates on: its own, per atom-count vector, apart from
+        `crystal_batch` / `_batch_for` -- a call never overwrites a fine-tune tape or a weight-gradient window."""
+        key = tuple(int(x) for x in num_atoms.tolist())
+        cache = self.__dict__.setdefault("_traj_cache", {})
+        pair = cache.get(key)
+        if pair is None:
+            if len(cache) >= 4:
+                cache.pop(next(iter(cache)))
+            pair = _TrajPair(self.decoder.make_batch(list(key)), self.decoder.make_batch(list(key)))
+            cache[key] = pair
+        pair.calls += 1   # every call overwrites what the pair holds: a pending backward of an earlier call must refuse (TrajLogProbFunction)
+        return pair
+
+    def forward_logprb(self, state, step_lr=1e-5):
+        """DiffCSPModule.forward_logprb (diffusion.py:158-227): re-evaluate one recorded step -- the corrector's network evaluation on
+        (atom_types, frac_coords, lattices), the predictor's on frac_coords_mid -- under the current weights.  Returns
+        (log_prob_l, log_prob_t, log_prob_x, (pred_l_corr, pred_x_corr, pred_t_corr)) like the reference, differentiable with respect
+        to decoder.theta when grad is enabled (matinvent_amd.autograd.TrajLogProbFunction); under torch.no_grad() nothing is taped.
+
+        Deviation: crystal b is evaluated at ITS OWN timesteps[b] (time embedding and scalars); the reference takes timesteps[0]'s scalars
+        for every crystal.  The two agree whenever the timesteps are equal -- the only case sample_mdp produces.  t must lie in 2..T
+        (ValueError otherwise; the reference's formulas give inf / NaN at t = 1).  One pending backward per atom-count vector: a later
+        call with the same atom counts overwrites the tapes, and the earlier call's backward then raises instead of returning wrong
+        gradients."""
+        for k, v in state.items():   # (the reference moves the caller's tensors to the device in place, :159-160)
+            state[k] = v.to(self.device)
+        dev = self.device
+        T = self.beta_scheduler.timesteps
+        times = state["timesteps"].to(torch.int32)
+        th = times.cpu()
+        if th.numel() and (int(th.min()) < 2 or int(th.max()) > T):
+            raise ValueError(f"forward_logprb: timesteps must lie in 2..{T} (got {int(th.min())}..{int(th.max())}); the reference's "
+                             "formulas give inf / NaN at t = 1")
+        num_atoms = state["num_atoms"]
+        pair = self._traj_batches(num_atoms)
+        batches = pair.handles
+        B, N = batches[0].num_graphs, batches[0].num_nodes
+        f = lambda k: state[k].detach().to(dev, torch.float32).contiguous()
+        at, fr, fm, lat = f("atom_types"), f("frac_coords"), f("frac_coords_mid"), f("lattices")
+        nat, nfr, nlat = f("next_atom_types"), f("next_frac_coords"), f("next_lattices")
+        assert at.shape == (N, MAX_ATOMIC_NUM) and fr.shape == fm.shape == nfr.shape == (N, 3) and lat.numel() == nlat.numel() == B * 9
+        coef = self._coefficients_dev(step_lr)
+        times = times.to(dev).contiguous()
+        freqs = self.time_embedding.freqs
+        theta = self.decoder.theta
+        if torch.is_grad_enabled() and theta.requires_grad:
+            from .autograd import TrajLogProbFunction
+            lp_l, lp_t, lp_x, pl, px, pt = TrajLogProbFunction.apply(theta, self.decoder, pair, times, coef, T, freqs, at, fr, fm, lat,
+                                                                     nat, nfr, nlat)
+            return lp_l, lp_t, lp_x, (pl, px, pt)
+        lib = _lib.load()
+        self.decoder.sync()
+        lp = torch.empty(3, B, device=dev)
+        pl, px, pt = torch.empty(B, 3, 3, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, MAX_ATOMIC_NUM, device=dev)
+        _lib.check(lib.mi_traj_logprob(self.decoder._h, batches[0]._h, batches[1]._h, _ptr(times), _ptr(coef), T, _ptr(freqs), _ptr(at),
+                                       _ptr(fr), _ptr(fm), _ptr(lat), _ptr(nat), _ptr(nfr), _ptr(nlat), _ptr(lp), _ptr(pl), _ptr(px), _ptr(pt),
+                                       0, _stream()), "mi_traj_logprob")
+        return lp[0], lp[1], lp[2], (pl, px, pt)
+
+    def _coefficients_dev(self, step_lr):
+        """_coefficients on the device (mi_traj_logprob reads the table there), cached with it."""
+        host = self._coefficients(step_lr)
+        cached = self.__dict__.get("_coef_dev")
+        if cached is None or cached[0] is not host or cached[1].device != self.device:
+            cached = (host, host.to(self.device).contiguous())
+            self.__dict__["_coef_dev"] = cached
+        return cached[1]
 
     def _batch_for(self, num_atoms):
         """CrystalBatch of THIS module for a num_atoms tensor (small cache keyed by the atom counts and

@@ -95,3 +95,81 @@ class DiffCSPSampler:
             data_list = [d for p in parts for d in p[0]]
             struc_list = [s for p in parts for s in p[1]]
         return data_list, struc_list
+
+
+def _unpack(model, counts, outputs):
+    """The final state of a `model.sample` call as CrystalData records (sample.py:221-244), each carrying the device-side geometry that
+    invalid_filter thresholds (K18: the same quantities DiffCSPSampler.generate attaches)."""
+    from . import _lib
+    from .structure import check_structures
+    if hasattr(model, "check_graph"):
+        model.check_graph()
+    _lib.check_saturation("sample_loop / sample_mdp")
+    geom = check_structures(model.crystal_batch(counts), outputs["frac_coords"], outputs["lattices"]).cpu()
+    frac_coords = outputs["frac_coords"].detach().cpu()
+    num_atoms = outputs["num_atoms"].detach().cpu()
+    atom_types = torch.argmax(outputs["atom_types"].detach().cpu(), dim=-1) + 1
+    lengths, angles = lattices_to_params_shape(outputs["lattices"].detach().cpu())
+    offset = [0] + torch.cumsum(num_atoms, dim=0).tolist()
+    data_list = []
+    for i in range(len(num_atoms)):
+        d = CrystalData(frac_coords=frac_coords[offset[i]:offset[i + 1]], atom_types=atom_types[offset[i]:offset[i + 1]],
+                        lengths=lengths[i].view(1, -1), angles=angles[i].view(1, -1), num_atoms=int(num_atoms[i]))
+        d.geometry = {"max_cell_edge": float(geom[i, 0]), "min_distance": float(geom[i, 1]), "volume": float(geom[i, 2])}
+        data_list.append(d)
+    return data_list
+
+
+def _draw_seed(seed):
+    # the reference's noise comes from torch's global generator: so does the Philox key here, unless the caller names one
+    return int(torch.randint(0, 2 ** 62, (1,))) if seed is None else int(seed)
+
+
+def sample_loop(sample_size, model, device=None, step_lr=-1, seed=None):
+    """sample.py:204-246: one batch of `sample_size` crystals (atom counts from the MP-20 prior) -> list of CrystalData."""
+    model.eval()
+    dataset = SampleDataset(total_num=sample_size)
+    step_lr = step_lr if step_lr >= 0 else DEFAULT_STEP_LR["gen"]["mp_20"]
+    counts = _AtomCounts(dataset.num_atoms)
+    outputs, _ = model.sample(counts, step_lr=step_lr, seed=_draw_seed(seed))
+    return _unpack(model, counts, outputs)
+
+
+def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None):
+    """sample.py:249-309: sample with the trajectory recorded and return (sample_list, sample_traj), restricted to the crystals that
+    pass invalid_filter.  sample_traj[k] is the step t = T - k (t = T .. 2) with the reference's keys (atom_types, lattices, frac_coords,
+    frac_coords_mid, num_atoms, timesteps, log_prob_{t,x,l}; host tensors) plus next_frac_coords / next_lattices / next_atom_types --
+    the state at t - 1 -- so that any element can go straight to DiffCSPModule.forward_logprb.  (The reference's own sample_mdp unpacks
+    invalid_filter into the wrong values and never builds the next_* keys that forward_logprb reads.)"""
+    from .filters import invalid_filter
+    model.eval()
+    dataset = SampleDataset(total_num=sample_size)
+    step_lr = step_lr if step_lr >= 0 else DEFAULT_STEP_LR["gen"]["mp_20"]
+    counts = _AtomCounts(dataset.num_atoms)
+    outputs, traj = model.sample(counts, step_lr=step_lr, seed=_draw_seed(seed), record=True)
+    data_list = _unpack(model, counts, outputs)
+    valid = invalid_filter(data_list, return_mask=True)
+    sample_list = [d for d, ok in zip(data_list, valid) if ok]
+    valid_idx = torch.as_tensor(np.where(valid)[0], dtype=torch.long)
+    atom_bool = torch.as_tensor(valid)[traj[0]["batch_idx"].cpu()]
+    cpu = lambda v: v.detach().cpu()
+    sample_traj = []
+    for i in range(model.beta_scheduler.timesteps, 1, -1):
+        cur, nxt = traj[i], traj[i - 1]
+        gi = valid_idx.to(cur["lattices"].device)
+        ai = atom_bool.to(cur["atom_types"].device)
+        sample_traj.append({
+            "atom_types": cpu(cur["atom_types"][ai]),
+            "lattices": cpu(cur["lattices"][gi]),
+            "frac_coords": cpu(cur["frac_coords"][ai]),
+            "frac_coords_mid": cpu(cur["frac_coords_mid"][ai]),
+            "num_atoms": cpu(cur["num_atoms"][gi]),
+            "timesteps": torch.tensor([i] * len(valid_idx), dtype=torch.long),
+            "log_prob_t": cpu(cur["log_prob_t"][gi]),
+            "log_prob_x": cpu(cur["log_prob_x"][gi]),
+            "log_prob_l": cpu(cur["log_prob_l"][gi]),
+            "next_frac_coords": cpu(nxt["frac_coords"][ai]),
+            "next_lattices": cpu(nxt["lattices"][gi]),
+            "next_atom_types": cpu(nxt["atom_types"][ai]),
+        })
+    return sample_list, sample_traj
