@@ -202,6 +202,11 @@ struct mi_batch {
     float *tr_sl = nullptr, *tr_sx = nullptr, *tr_st = nullptr;      // the seeds, same shapes
     mi_batch* tr_partner = nullptr;                                   // (corrector handle) the predictor handle of that call; NULL: no taped call pending
     uint64_t tr_epoch = 0, tr_partner_epoch = 0;                      // both handles' fwd_epoch right after that call
+    // mi_traj_pg_step (corrector handle): the gathered state at t and t-1, the new log-probabilities and their seeds (allocated on first use)
+    float *pg_a = nullptr, *pg_x = nullptr, *pg_xm = nullptr, *pg_l = nullptr;     // [N][A], [N][3], [N][3], [B][9]
+    float *pg_na = nullptr, *pg_nx = nullptr, *pg_nl = nullptr;                    // [N][A], [N][3], [B][9]
+    float *pg_lp = nullptr, *pg_g = nullptr;                                       // [3][B] each
+    int* pg_t = nullptr;                                                           // [B] the times the kernels read (checked copy)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // fork / join of work put on an auxiliary stream (mi_ft_micro_step)
     std::vector<void*> allocs;
 };

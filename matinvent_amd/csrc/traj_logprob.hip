@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/matinvent_hip_traj.h"
+#include "../../include/matinvent_hip_pg.h"
 #include "net.h"
 #include "logprob.h"
 
@@ -160,32 +161,13 @@ static bool same_counts(const mi_batch* p, const mi_batch* q) {
     return p->B == q->B && p->N == q->N && p->num_atoms_h == q->num_atoms_h;
 }
 
-}  // namespace mi
-
-using namespace mi;
-
-extern "C" {
-
-int mi_traj_logprob(mi_net* net, mi_batch* bc, mi_batch* bp, const int* t_dev, const float* coef_dev, int T, const float* time_freqs,
-                    const float* atom_types, const float* frac, const float* frac_mid, const float* lattices, const float* next_atom_types,
-                    const float* next_frac, const float* next_lattices, float* log_prob, float* pred_corr_l, float* pred_corr_x,
-                    float* pred_corr_t, int keep_tape, void* stream) {
-    MI_CHECK(net && bc && bp, MI_EINVAL, "null handle");
-    MI_CHECK(bc != bp, MI_EINVAL, "the corrector and the predictor evaluation need two distinct batch handles");
-    MI_CHECK(bc->H == net->H && bc->L == net->L && bp->H == net->H && bp->L == net->L, MI_EINVAL, "batch was created for a different network");
-    MI_CHECK(same_counts(bc, bp), MI_EINVAL, "the two batch handles hold different atom counts");
-    MI_CHECK(t_dev && coef_dev && time_freqs && atom_types && frac && frac_mid && lattices && next_atom_types && next_frac && next_lattices &&
-                 log_prob, MI_EINVAL, "null argument");
-    MI_CHECK(T >= 2, MI_EINVAL, "T = %d: a recorded step needs T >= 2", T);
+// the work of mi_traj_logprob after its argument checks (the times in t_dev are valid): shared with mi_traj_pg_step, which checks its times on the host
+static int traj_logprob_enqueue(mi_net* net, mi_batch* bc, mi_batch* bp, const int* t_dev, const float* coef_dev, const float* time_freqs,
+                                const float* atom_types, const float* frac, const float* frac_mid, const float* lattices,
+                                const float* next_atom_types, const float* next_frac, const float* next_lattices, float* log_prob,
+                                float* pred_corr_l, float* pred_corr_x, float* pred_corr_t, int keep_tape, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const int B = bc->B, N = bc->N;
-    bc->tr_partner = nullptr;   // whatever was pending on this pair is about to be overwritten
-    if (B == 0) return MI_OK;
-    std::vector<int> th(B);
-    MI_HIP(hipMemcpyAsync(th.data(), t_dev, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
-    MI_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < B; ++i)
-        MI_CHECK(th[i] >= 2 && th[i] <= T, MI_EINVAL, "timesteps[%d] = %d: a recorded step has t in 2..T = %d", i, th[i], T);
     if (keep_tape) {
         MI_TRY(traj_buffers(bc));
         MI_TRY(traj_buffers(bp));
@@ -225,6 +207,138 @@ int mi_traj_logprob(mi_net* net, mi_batch* bc, mi_batch* bp, const int* t_dev, c
     return MI_OK;
 }
 
+static bool traj_handles_ok(mi_net* net, mi_batch* bc, mi_batch* bp) {
+    return bc->H == net->H && bc->L == net->L && bp->H == net->H && bp->L == net->L;
+}
+
+// ---- the PPO-clipped policy-gradient micro-step (mi_traj_pg_step) ----------------------------------------------------------------
+
+struct GatherArgs {
+    const int* t;                                   // [B] caller's times (the host checked its copy: 2..T)
+    const int* n2g;                                 // [N]
+    const float *ta, *tx, *txm, *tl;                // the rollout: [T+1][N][A], [T+1][N][3] x 2, [T+1][B][9]
+    float *a, *x, *xm, *l, *na, *nx, *nl;           // crystal b's state at t_b and t_b - 1
+    int* t_out;                                     // [B] the times every later kernel of the micro-step reads
+    int B, N, T;
+};
+
+__device__ __forceinline__ int pg_time(const int* t, int b, int T) {
+    const int v = t[b];
+    return v < 2 ? 2 : (v > T ? T : v);   // (the host checked these values: the clamp only keeps every read of a stray one inside the rollout)
+}
+
+// one thread per gathered element of the seven arrays: N*A (types at t, at t-1), N*3 (coordinates at t, mid coordinates at t, coordinates at
+// t-1), B*9 (lattice at t, at t-1); plain copies, the bits of the record
+__global__ __launch_bounds__(256) void traj_pg_gather_kernel(GatherArgs a) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.B) a.t_out[i] = pg_time(a.t, (int)i, a.T);
+    const int64_t nt = (int64_t)a.N * MI_NUM_TYPES, nx = (int64_t)a.N * 3, nl = (int64_t)a.B * 9;
+    if (i < 2 * nt) {
+        const bool next = i >= nt;
+        const int64_t e = next ? i - nt : i;
+        const int t = pg_time(a.t, a.n2g[e / MI_NUM_TYPES], a.T) - (next ? 1 : 0);
+        (next ? a.na : a.a)[e] = a.ta[(int64_t)t * nt + e];
+        return;
+    }
+    i -= 2 * nt;
+    if (i < 3 * nx) {
+        const int k = (int)(i / nx);
+        const int64_t e = i - k * nx;
+        const int t = pg_time(a.t, a.n2g[e / 3], a.T) - (k == 2 ? 1 : 0);
+        const float* src = k == 1 ? a.txm : a.tx;
+        float* dst = k == 0 ? a.x : (k == 1 ? a.xm : a.nx);
+        dst[e] = src[(int64_t)t * nx + e];
+        return;
+    }
+    i -= 3 * nx;
+    if (i < 2 * nl) {
+        const bool next = i >= nl;
+        const int64_t e = next ? i - nl : i;
+        const int t = pg_time(a.t, (int)(e / 9), a.T) - (next ? 1 : 0);
+        (next ? a.nl : a.l)[e] = a.tl[(int64_t)t * nl + e];
+    }
+}
+
+struct SurrogateArgs {
+    const int* t;          // [B] (checked)
+    const float* lp;       // [3][B] new log-probabilities
+    const float* lp_old;   // [T+1][B][3] the sampler's record
+    const float* adv;      // [B]
+    float* g;              // [3][B] seeds
+    float* stats;          // [4][B] running sums
+    float w0, w1, w2, lo, hi, eps, scale;
+    int B;
+};
+
+// one thread per crystal: the clipped surrogate, its upstream gradient and the running statistics -- each crystal's sums owned by one thread
+__global__ __launch_bounds__(256) void traj_pg_surrogate_kernel(SurrogateArgs a) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.B) return;
+    const float* o = a.lp_old + ((int64_t)a.t[b] * a.B + b) * 3;
+    const float lp_new = (a.w0 * a.lp[b] + a.w1 * a.lp[a.B + b]) + a.w2 * a.lp[2 * a.B + b];
+    const float lp_old = (a.w0 * o[0] + a.w1 * o[1]) + a.w2 * o[2];
+    const float d = lp_new - lp_old;
+    const float rho = expf(d);
+    const float na = -a.adv[b];
+    const float rc = rho < a.lo ? a.lo : (rho > a.hi ? a.hi : rho);   // torch.clamp (NaN passes through)
+    const float u = na * rho, c = na * rc;
+    const float L = u > c ? u : c;
+    const bool unclipped = !(rho < a.lo || rho > a.hi) || u > c;
+    const float g = unclipped ? (a.scale * na) * rho : 0.f;
+    a.g[b] = a.w0 * g;
+    a.g[a.B + b] = a.w1 * g;
+    a.g[2 * a.B + b] = a.w2 * g;
+    a.stats[b] += L;
+    a.stats[a.B + b] += rho;
+    a.stats[2 * a.B + b] += 0.5f * (d * d);
+    a.stats[3 * a.B + b] += fabsf(rho - 1.0f) > a.eps ? 1.0f : 0.0f;
+}
+
+static int pg_buffers(mi_batch* b) {
+    if (b->pg_g) return MI_OK;
+    const size_t nt = (size_t)b->N * MI_NUM_TYPES, nx = (size_t)b->N * 3, nl = (size_t)b->B * 9;
+    MI_TRY(dev_alloc(b, &b->pg_a, nt));
+    MI_TRY(dev_alloc(b, &b->pg_na, nt));
+    MI_TRY(dev_alloc(b, &b->pg_x, nx));
+    MI_TRY(dev_alloc(b, &b->pg_xm, nx));
+    MI_TRY(dev_alloc(b, &b->pg_nx, nx));
+    MI_TRY(dev_alloc(b, &b->pg_l, nl));
+    MI_TRY(dev_alloc(b, &b->pg_nl, nl));
+    MI_TRY(dev_alloc(b, &b->pg_lp, (size_t)3 * b->B));
+    MI_TRY(dev_alloc(b, &b->pg_t, (size_t)b->B));
+    return dev_alloc(b, &b->pg_g, (size_t)3 * b->B);   // (last: its presence marks the set complete)
+}
+
+}  // namespace mi
+
+using namespace mi;
+
+extern "C" {
+
+int mi_traj_logprob(mi_net* net, mi_batch* bc, mi_batch* bp, const int* t_dev, const float* coef_dev, int T, const float* time_freqs,
+                    const float* atom_types, const float* frac, const float* frac_mid, const float* lattices, const float* next_atom_types,
+                    const float* next_frac, const float* next_lattices, float* log_prob, float* pred_corr_l, float* pred_corr_x,
+                    float* pred_corr_t, int keep_tape, void* stream) {
+    MI_CHECK(net && bc && bp, MI_EINVAL, "null handle");
+    MI_CHECK(bc != bp, MI_EINVAL, "the corrector and the predictor evaluation need two distinct batch handles");
+    MI_CHECK(traj_handles_ok(net, bc, bp), MI_EINVAL, "batch was created for a different network");
+    MI_CHECK(same_counts(bc, bp), MI_EINVAL, "the two batch handles hold different atom counts");
+    MI_CHECK(t_dev && coef_dev && time_freqs && atom_types && frac && frac_mid && lattices && next_atom_types && next_frac && next_lattices &&
+                 log_prob, MI_EINVAL, "null argument");
+    MI_CHECK(T >= 2, MI_EINVAL, "T = %d: a recorded step needs T >= 2", T);
+    hipStream_t s = (hipStream_t)stream;
+    const int B = bc->B;
+    bc->tr_partner = nullptr;   // whatever was pending on this pair is about to be overwritten
+    if (B == 0) return MI_OK;
+    std::vector<int> th(B);
+    MI_HIP(hipMemcpyAsync(th.data(), t_dev, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, s));
+    MI_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < B; ++i)
+        MI_CHECK(th[i] >= 2 && th[i] <= T, MI_EINVAL, "timesteps[%d] = %d: a recorded step has t in 2..T = %d", i, th[i], T);
+    return traj_logprob_enqueue(net, bc, bp, t_dev, coef_dev, time_freqs, atom_types, frac, frac_mid, lattices, next_atom_types, next_frac,
+                                next_lattices, log_prob, pred_corr_l, pred_corr_x, pred_corr_t, keep_tape, stream);
+}
+
 int mi_traj_logprob_backward(mi_net* net, mi_batch* bc, mi_batch* bp, const float* g_logp, const float* d_corr_l, const float* d_corr_x,
                              const float* d_corr_t, float* grad_theta, void* stream) {
     MI_CHECK(net && bc && bp && g_logp && grad_theta, MI_EINVAL, "null argument");
@@ -247,6 +361,52 @@ int mi_traj_logprob_backward(mi_net* net, mi_batch* bc, mi_batch* bp, const floa
     MI_KERNEL_CHECK();
     MI_TRY(net_backward(net, bp, bp->tr_sl, bp->tr_sx, bp->tr_st, grad_theta, s));
     return net_backward(net, bc, bc->tr_sl, bc->tr_sx, bc->tr_st, grad_theta, s);
+}
+
+int mi_traj_pg_step(mi_net* net, mi_batch* bc, mi_batch* bp, const float* coef_dev, int T, const float* time_freqs,
+                    const float* traj_atom_types, const float* traj_frac, const float* traj_frac_mid, const float* traj_lattices,
+                    const float* traj_lp_old, const int* t_host, const int* t_dev, const float* adv_dev, float clip_range,
+                    const float* w_host, float loss_scale, float* log_prob, float* grad_theta, float* stats, void* stream) {
+    MI_CHECK(net && bc && bp, MI_EINVAL, "null handle");
+    MI_CHECK(bc != bp, MI_EINVAL, "the corrector and the predictor evaluation need two distinct batch handles");
+    MI_CHECK(traj_handles_ok(net, bc, bp), MI_EINVAL, "batch was created for a different network");
+    MI_CHECK(same_counts(bc, bp), MI_EINVAL, "the two batch handles hold different atom counts");
+    MI_CHECK(coef_dev && time_freqs && traj_atom_types && traj_frac && traj_frac_mid && traj_lattices && traj_lp_old && t_host && t_dev &&
+                 adv_dev && w_host && grad_theta && stats, MI_EINVAL, "null argument");
+    MI_CHECK(T >= 2, MI_EINVAL, "T = %d: a recorded step needs T >= 2", T);
+    MI_CHECK(clip_range >= 0.f, MI_EINVAL, "clip_range = %g: must be >= 0", (double)clip_range);
+    MI_CHECK(net->W2T != nullptr, MI_ESTATE, "mi_net_set_params must run before backward");
+    const int B = bc->B, N = bc->N;
+    // every time is checked before anything is enqueued: the kernels index the rollout with them
+    for (int i = 0; i < B; ++i)
+        MI_CHECK(t_host[i] >= 2 && t_host[i] <= T, MI_EINVAL, "t[%d] = %d: a recorded step has t in 2..T = %d", i, t_host[i], T);
+    if (B == 0 || N == 0) return MI_OK;
+    MI_TRY(pg_buffers(bc));
+    hipStream_t s = (hipStream_t)stream;
+
+    GatherArgs g;
+    g.t = t_dev, g.n2g = bc->node2graph;
+    g.ta = traj_atom_types, g.tx = traj_frac, g.txm = traj_frac_mid, g.tl = traj_lattices;
+    g.a = bc->pg_a, g.x = bc->pg_x, g.xm = bc->pg_xm, g.l = bc->pg_l, g.na = bc->pg_na, g.nx = bc->pg_nx, g.nl = bc->pg_nl;
+    g.t_out = bc->pg_t;
+    g.B = B, g.N = N, g.T = T;
+    const int64_t ng = 2 * (int64_t)N * MI_NUM_TYPES + 9 * (int64_t)N + 18 * (int64_t)B;
+    hipLaunchKernelGGL(traj_pg_gather_kernel, dim3(cdiv(ng, 256)), dim3(256), 0, s, g);
+    MI_KERNEL_CHECK();
+
+    float* lp = log_prob ? log_prob : bc->pg_lp;
+    MI_TRY(traj_logprob_enqueue(net, bc, bp, bc->pg_t, coef_dev, time_freqs, bc->pg_a, bc->pg_x, bc->pg_xm, bc->pg_l, bc->pg_na, bc->pg_nx,
+                                bc->pg_nl, lp, nullptr, nullptr, nullptr, 1, stream));
+
+    SurrogateArgs u;
+    u.t = bc->pg_t, u.lp = lp, u.lp_old = traj_lp_old, u.adv = adv_dev, u.g = bc->pg_g, u.stats = stats;
+    u.w0 = w_host[0], u.w1 = w_host[1], u.w2 = w_host[2];
+    u.lo = (float)(1.0 - (double)clip_range), u.hi = (float)(1.0 + (double)clip_range), u.eps = clip_range;
+    u.scale = loss_scale;
+    u.B = B;
+    hipLaunchKernelGGL(traj_pg_surrogate_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, u);
+    MI_KERNEL_CHECK();
+    return mi_traj_logprob_backward(net, bc, bp, bc->pg_g, nullptr, nullptr, nullptr, grad_theta, stream);
 }
 
 }  // extern "C"

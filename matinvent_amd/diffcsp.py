@@ -295,8 +295,12 @@ class DiffCSPModule(nn.Module):
 
     @torch.no_grad()
     def sample(self, batch, diff_ratio=1.0, step_lr=1e-5, seed=0, noise=None, init=None, record=False, t_start=None,
-               t_stop=0, node_offset=0, graph_offset=0, streams=None):
+               t_stop=0, node_offset=0, graph_offset=0, streams=None, rec_sink=None):
         """DiffCSPModule.sample (diffusion.py:273-399).
+
+        `rec_sink` (a list; with record=True): receives one (first crystal, first atom, buffers) per chain, in crystal order -- the
+        chain's stacked record buffers [T+1, ...] (atom_types, frac_coords, lattices, frac_coords_mid, log_prob_{l,t,x}) that the
+        per-step dict `traj` views (sampling.sample_rollout compacts them on the device).
 
         `streams` > 1 splits the crystals into that many contiguous groups and runs their chains CONCURRENTLY on separate
         HIP streams (crystals never interact, and the counter-based noise is indexed by global atom / crystal id, so the
@@ -306,7 +310,7 @@ class DiffCSPModule(nn.Module):
         if self.__dict__.get("_knn_pending"):
             self.check_graph()   # (the verdict of the previous call's chains: by now they have long finished)
         if isinstance(batch, CrystalBatch):
-            return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset)
+            return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink)
         if (self.keep_lattice or self.keep_coords) and init is None:
             # CSP mode (diffusion.py:283-287): the known part of the structure replaces the drawn initial state and is never moved
             cb0 = self.crystal_batch(batch, node_offset, graph_offset)
@@ -328,7 +332,7 @@ class DiffCSPModule(nn.Module):
             streams = 4 if e_total >= 98304 else 3 if e_total >= 49152 else 2 if e_total >= 16384 else 1
         streams = max(1, min(int(streams), len(na)))
         if streams == 1:
-            return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset)
+            return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink)
         key = ("split", streams, tuple(na))
         parts = getattr(batch, "_mi_split", {}).get(key)
         if parts is None:  # contiguous crystal groups, cached on the batch object like its CrystalBatch
@@ -356,6 +360,7 @@ class DiffCSPModule(nn.Module):
         else:
             state = (torch.empty(n_tot, 3, device=dev), torch.empty(b_tot, 3, 3, device=dev), torch.empty(n_tot, MAX_ATOMIC_NUM, device=dev))
         ready = cur.record_event()
+        sinks = [[] for _ in parts] if rec_sink is not None else [None] * len(parts)
         # long-lived worker threads, one per stream (streams.ChainWorkers): a call hands each its chain and waits -- no thread start per call
         from .streams import ChainWorkers
         workers = ChainWorkers.get(streams, self.device)
@@ -367,11 +372,17 @@ class DiffCSPModule(nn.Module):
             nz = None if noise is None else {"corr_x": noise["corr_x"][:, n0[k]:n0[k + 1]], "pred_x": noise["pred_x"][:, n0[k]:n0[k + 1]],
                                              "pred_t": noise["pred_t"][:, n0[k]:n0[k + 1]], "pred_l": noise["pred_l"][:, g0[k]:g0[k + 1]]}
             r = self._sample_one(parts[k], step_lr, seed, nz, None, record, t_start, t_stop, node_offset + n0[k], graph_offset + g0[k],
-                                 inplace=own, drawn=init is not None)
+                                 inplace=own, drawn=init is not None, rec_sink=sinks[k])
             cur.wait_event(stream.record_event())
             return r
 
         out = workers.run(run, streams)
+        if rec_sink is not None:
+            for k, sk in enumerate(sinks):
+                for _, _, bufs in sk:
+                    for v in bufs.values():
+                        v.record_stream(cur)   # (allocated on the group stream, consumed on the caller's)
+                rec_sink.extend((g0[k] + g, n0[k] + n, bufs) for g, n, bufs in sk)
 
         def merge(ds):
             m = {}
@@ -407,7 +418,8 @@ class DiffCSPModule(nn.Module):
         for cb, stream in pending:
             _lib.check(lib.mi_knn_graph_status(cb._h, C.c_void_p(stream.cuda_stream)), "mi_knn_graph_status")
 
-    def _sample_one(self, batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, inplace=None, drawn=False):
+    def _sample_one(self, batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, inplace=None, drawn=False,
+                    rec_sink=None):
         """One chain over one CrystalBatch on the current stream.
 
         Returns (traj[t_stop], traj) like the reference.  `traj` holds every step only when
@@ -460,6 +472,8 @@ class DiffCSPModule(nn.Module):
             self.__dict__.setdefault("_knn_pending", []).append((cb, torch.cuda.current_stream()))
         final = dict(atom_types=a, frac_coords=x, lattices=l, num_atoms=cb.num_atoms, batch_idx=cb.batch)
         traj = {t_stop: final}
+        if record and rec_sink is not None:
+            rec_sink.append((0, 0, rec_t))
         if record:
             for t in range(t_start, t_stop - 1, -1):
                 d = dict(atom_types=rec_t["atom_types"][t], frac_coords=rec_t["frac_coords"][t], lattices=rec_t["lattices"][t],

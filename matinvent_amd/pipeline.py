@@ -149,3 +149,77 @@ class Baseline(ReinL):
         for step in range(self.rl_epoch):
             self.step = step
             self.rl_step()
+
+
+class MatInventPG(MatInvent):
+    """MatInvent with the PPO-clipped policy gradient on recorded trajectories (policy.pg_step, DDPO-style) in place of the
+    reward-weighted denoising loss.  Each RL loop: rollout (sampling.sample_rollout: the kept crystals' chains stay on the device) ->
+    the validity pre-filter, the optional filter callable and max_num, as in MatInvent -> reward_step -> pg_step over EVERY kept
+    crystal.  On-policy: there is no top-k and no replay (a stored crystal's log-probabilities belong to weights that no longer exist),
+    so replay=True is refused.  Single GPU, DiffCSP only (MatterGen has no log-probability path), one sampling batch per loop."""
+
+    def __init__(self, rl_epoch, model_suite, reward, sample_cfg, finetune_cfg, save_dir, save_freq=50, device=None, logger=None,
+                 replay=False, replay_args=None, topk_ratio=1.0, **kwargs):
+        from .suite import MatterGenSuite
+        if replay:
+            raise ValueError("MatInventPG is on-policy: replay=True is not supported (replayed crystals carry log-probabilities of "
+                             "earlier weights)")
+        if isinstance(model_suite, MatterGenSuite):
+            raise ValueError("MatInventPG needs the DiffCSP suite: the MatterGen suite has no trajectory log-probability path")
+        if rank_world()[1] > 1:
+            raise ValueError("MatInventPG runs on one GPU: world_size > 1 is not supported")
+        nb = C.merge(model_suite.sample_cfg, sample_cfg).get("num_batches", 1)
+        if int(nb or 1) != 1:
+            raise ValueError(f"MatInventPG samples one batch per loop: num_batches = {nb} is not supported")
+        super().__init__(rl_epoch=rl_epoch, model_suite=model_suite, reward=reward, sample_cfg=sample_cfg, finetune_cfg=finetune_cfg,
+                         topk_ratio=topk_ratio, save_dir=save_dir, save_freq=save_freq, device=device, logger=logger, replay=False,
+                         replay_args=None, **kwargs)
+
+    def sample_step(self):
+        """Rollout + the MatInvent sample step's filtering.  Returns (data, strucs, rollout restricted to data, metrics)."""
+        from .data import data2struc
+        from .sampling import sample_rollout
+        self.sampler.seed += 1
+        data, rollout = sample_rollout(int(self.sample_cfg.batch_size), self.agent, seed=self.sampler.seed,
+                                       geometric_filter=bool(self.sample_cfg.get("geometric_filter", True)))
+        strucs = [data2struc(d) for d in data]
+        logging.info(f"rollout kept {len(data)} samples")
+        if getattr(self, "sample_dir", None):
+            write_extxyz(strucs, os.path.join(self.sample_dir, f"step_{self.step:0>4d}_valid.extxyz"))
+        pos = {id(d): i for i, d in enumerate(data)}
+        flt = self.sample_cfg.get("filter")
+        metrics = {}
+        if callable(flt):
+            data, strucs, metrics = flt(data, strucs, None)
+        max_num = self.sample_cfg.get("max_num")
+        if max_num and len(strucs) > max_num:
+            data, strucs = data[:max_num], strucs[:max_num]
+        self._rollout_pos = pos
+        return data, strucs, rollout, metrics
+
+    def rl_step(self):
+        from .policy import pg_step
+        t0 = time.time()
+        logging.info(f"*****   LOOP {self.step} START   *****")
+        data, strucs, rollout, metrics = self.sample_step()
+        if len(data) == 0:
+            logging.warning("no sample passed the validity pre-filter; skipping scoring and the policy-gradient update for this loop")
+            return
+        data, strucs, rewards, props = self.reward_step(data, strucs, None, f"step_{self.step:0>4d}")
+        log = {f"{k} mean": v.mean() for k, v in props.items()}
+        log.update({"reward mean": rewards.mean() if len(rewards) else float("nan"),
+                    "reward std": rewards.std() if len(rewards) else float("nan"), "cost": self.cost}, **metrics)
+        if len(data) < 2:
+            logging.warning(f"{len(data)} scored sample(s): the advantages need at least two; skipping the policy-gradient update for "
+                            "this loop")
+            if self.logger is not None:
+                self.logger.log(log, step=self.step)
+            return
+        rollout = rollout.select([self._rollout_pos[id(d)] for d in data])
+        stats = pg_step(self.agent, rollout, rewards, self.finetune_cfg, seed=self.sampler.seed)
+        last = stats[-1] if stats else {}
+        log.update({"clip_frac": last.get("clip_frac", float("nan")), "approx_kl": last.get("approx_kl", float("nan")),
+                    "ratio mean": last.get("ratio_mean", float("nan"))})
+        if self.logger is not None:
+            self.logger.log(log, step=self.step)
+        logging.info(f"*****   LOOP {self.step} FINISH   *****  {(time.time() - t0) / 60:.2f} min")

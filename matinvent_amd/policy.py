@@ -1,0 +1,133 @@
+"""PPO-clipped policy gradient on recorded reverse-diffusion trajectories (DDPO-style), the log-probability objective next to
+MatInvent's reward-weighted denoising loss (finetune.ft_step).
+
+For every kept crystal b of a rollout (sampling.sample_rollout) and a diffusion time t drawn from 2..T, the step t -> t-1 is
+re-evaluated under the current weights (DiffCSPModule.forward_logprb's arithmetic):
+
+    lp_new = w . (log_prob_l, log_prob_t, log_prob_x),  lp_old = w . (the sampler's record),  rho = exp(lp_new - lp_old)
+    L_b    = max(-A_b rho, -A_b clip(rho, 1 - eps, 1 + eps)),      loss = sum over micro-steps and crystals of L_b / M
+
+with A the normalised, clipped advantages and M = B * accum_steps (ft_step's `/ accum_steps` convention).  Each micro-step is ONE C
+call (mi_traj_pg_step: gather, two taped evaluations, surrogate and seeds, backward into theta.grad) with no host synchronisation;
+the statistics are read back once per epoch."""
+import logging
+
+import numpy as np
+import torch
+
+from . import _lib
+from .cspnet import _ptr, _stream
+from .optim import FusedAdam
+
+# clip_range: DDPO's 1e-4 is below the rounding of the re-evaluated lattice log-probability -- at unchanged weights |log rho| reaches 0.12 over a
+# T = 1000 chain of the benchmark network -- so the default is PPO's 0.2, above that measured maximum
+DEFAULTS = dict(clip_range=0.2, adv_clip=5.0, logprob_weights=(1.0, 1.0, 1.0))
+
+
+def advantages(rewards, adv_clip=DEFAULTS["adv_clip"]):
+    """(r - mean) / (std + 1e-8) with the population std, clipped to +-adv_clip; float32 [B] (host)."""
+    r = np.asarray(rewards, dtype=np.float64)
+    a = (r - r.mean()) / (r.std() + 1e-8)
+    return np.clip(a, -adv_clip, adv_clip).astype(np.float32)
+
+
+def draw_timesteps(T, B, timesteps, epochs, seed=None):
+    """For each epoch and each crystal, `timesteps` distinct times from 2..T without replacement (capped at T - 1, all of them), from a
+    generator seeded with `seed`.  Returns a list of `epochs` int32 arrays [K, B]: row k holds every crystal's time of micro-step k."""
+    K = min(int(timesteps), T - 1)
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(epochs):
+        perm = np.argsort(rng.random((B, T - 1)), axis=1)[:, :K] + 2      # a uniform K-subset of 2..T per crystal, in random order
+        out.append(np.ascontiguousarray(perm.T.astype(np.int32)))
+    return out
+
+
+def _cfg_get(cfg, k, default=None):
+    if isinstance(cfg, dict):
+        return cfg.get(k, default)
+    v = getattr(cfg, k, None)
+    if v is None and hasattr(cfg, "get"):
+        v = cfg.get(k, None)
+    return default if v is None else v
+
+
+def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info):
+    """One call of the PPO-clipped policy gradient over every crystal of `rollout` (sampling.Rollout) with rewards [B].
+
+    cfg (finetune_cfg; key or attribute access): lr, epochs, timesteps (draws per crystal per epoch, capped at T - 1), accum_steps
+    (micro-steps per optimiser step; a partial window at the end of an epoch steps too), clip_range (eps, default 0.2), adv_clip
+    (default 5.0), logprob_weights (w, default [1, 1, 1]).  Micro-step k evaluates every crystal at its k-th draw, so one pair of batch
+    handles serves the call; it is released on return.  A fresh FusedAdam per call, like ft_step.  `seed` seeds the timestep draws.
+    Returns one dict per epoch: loss (mean of L_b over micro-steps and crystals), ratio_mean, approx_kl (mean of (lp_new - lp_old)^2 / 2)
+    and clip_frac (fraction with |rho - 1| > eps)."""
+    lr, epochs = float(_cfg_get(cfg, "lr")), int(_cfg_get(cfg, "epochs"))
+    timesteps, accum_steps = int(_cfg_get(cfg, "timesteps")), int(_cfg_get(cfg, "accum_steps"))
+    clip_range = float(_cfg_get(cfg, "clip_range", DEFAULTS["clip_range"]))
+    adv_clip = float(_cfg_get(cfg, "adv_clip", DEFAULTS["adv_clip"]))
+    w = [float(v) for v in _cfg_get(cfg, "logprob_weights", DEFAULTS["logprob_weights"])]
+    if len(w) != 3:
+        raise ValueError(f"pg_step: logprob_weights needs three values (l, t, x), got {w}")
+    if accum_steps < 1 or epochs < 0 or timesteps < 1:
+        raise ValueError(f"pg_step: accum_steps = {accum_steps}, epochs = {epochs}, timesteps = {timesteps}")
+    B, T = rollout.num_graphs, rollout.T
+    if len(rewards) != B:
+        raise ValueError(f"pg_step: {len(rewards)} rewards for {B} crystals")
+    if B == 0:
+        raise ValueError("pg_step: the rollout holds no crystal")
+    if T != agent.beta_scheduler.timesteps:
+        raise ValueError(f"pg_step: the rollout's chain has T = {T}, the agent's T = {agent.beta_scheduler.timesteps}")
+    dev = agent.device
+    dec = agent.decoder
+    theta = dec.theta
+    adv = torch.from_numpy(advantages(rewards, adv_clip)).to(dev)                 # one upload per call
+    draws = draw_timesteps(T, B, timesteps, epochs, seed)
+    K = draws[0].shape[0] if draws else 0
+    M = B * accum_steps
+    na = [int(v) for v in rollout.num_atoms.tolist()]
+    b_corr, b_pred = dec.make_batch(na), dec.make_batch(na)                        # this call's pair (freed with the objects on return)
+    w_host = np.asarray(w, dtype=np.float32)
+    optimizer = FusedAdam([theta], lr=lr)
+    if theta.grad is None:
+        theta.grad = torch.zeros_like(theta)
+    stats = torch.zeros(4, B, device=dev)
+    out = []
+    for epoch in range(epochs):
+        agent.train()
+        optimizer.zero_grad(set_to_none=False)
+        stats.zero_()
+        t_host = draws[epoch]
+        t_dev = torch.from_numpy(t_host).to(dev)                                   # one upload per epoch: [K, B]
+        for k in range(K):
+            pg_micro_step(agent, (b_corr, b_pred), rollout, t_host[k], t_dev[k], adv, clip_range, w_host, 1.0 / M, theta.grad, stats)
+            if (k + 1) % accum_steps == 0:
+                optimizer.step()
+                optimizer.zero_grad(set_to_none=False)
+        if K % accum_steps:
+            optimizer.step()
+            optimizer.zero_grad(set_to_none=False)
+        s = (stats.sum(dim=1) / max(1, K * B)).tolist()                           # one read-back per epoch
+        d = dict(loss=s[0], ratio_mean=s[1], approx_kl=s[2], clip_frac=s[3])
+        out.append(d)
+        log(f"PG epoch {epoch}: " + ", ".join(f"{k}: {v:.4g}" for k, v in d.items()))
+    del b_corr, b_pred
+    return out
+
+
+def pg_micro_step(agent, handles, rollout, t_host, t_dev, adv, clip_range, w_host, loss_scale, grad, stats, log_prob=None):
+    """One mi_traj_pg_step: every crystal of `rollout` at its time t_host[b] (int32 host [B]; t_dev the same on the device), advantages
+    adv [B] (device), weights w_host (float32 host [3]); grad += the surrogate's gradient scaled by loss_scale, stats [4, B] += (L_b, rho,
+    approx-KL term, clipped indicator); log_prob [3, B] (optional) receives the new log-probabilities.  `handles`: two batch handles of
+    agent.decoder over rollout.num_atoms.  Enqueued on the current stream without a host synchronisation."""
+    dec = agent.decoder
+    traj = [rollout.atom_types, rollout.frac_coords, rollout.frac_coords_mid, rollout.lattices, rollout.lp_old]
+    for v in traj:
+        assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()
+    t_host = np.ascontiguousarray(t_host, dtype=np.int32)
+    w_host = np.ascontiguousarray(w_host, dtype=np.float32)
+    assert t_host.shape == (rollout.num_graphs,) and w_host.shape == (3,) and t_dev.dtype == torch.int32
+    dec.sync()
+    _lib.check(_lib.load().mi_traj_pg_step(dec._h, handles[0]._h, handles[1]._h, _ptr(agent._coefficients_dev(rollout.step_lr)), rollout.T,
+                                           _ptr(agent.time_embedding.freqs), *(_ptr(v) for v in traj), t_host.ctypes.data, _ptr(t_dev),
+                                           _ptr(adv), float(clip_range), w_host.ctypes.data, float(loss_scale), _ptr(log_prob), _ptr(grad),
+                                           _ptr(stats), _stream()), "mi_traj_pg_step")

@@ -173,3 +173,80 @@ def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None):
             "next_atom_types": cpu(nxt["atom_types"][ai]),
         })
     return sample_list, sample_traj
+
+
+@dataclass
+class Rollout:
+    """The kept crystals' reverse-diffusion chains on the device, stacked over t = 0..T (index t = the state at diffusion time t):
+    atom_types [T+1, N, 100], frac_coords / frac_coords_mid [T+1, N, 3], lattices [T+1, B, 9], lp_old [T+1, B, 3] = the sampler's own
+    recorded (log_prob_l, log_prob_t, log_prob_x) of the step t -> t-1 (defined for t = 2..T).  num_atoms: host long [B]; node_offsets:
+    host long [B+1]; step_lr: the step size the chain ran with (mi_traj_pg_step re-evaluates with the same one)."""
+    atom_types: torch.Tensor
+    frac_coords: torch.Tensor
+    frac_coords_mid: torch.Tensor
+    lattices: torch.Tensor
+    lp_old: torch.Tensor
+    num_atoms: torch.Tensor
+    node_offsets: torch.Tensor
+    T: int
+    step_lr: float
+
+    @property
+    def num_graphs(self):
+        return len(self.num_atoms)
+
+    def select(self, idx):
+        """The rollout restricted to crystals `idx` (in that order): one compaction per array."""
+        idx = [int(i) for i in idx]
+        if idx == list(range(self.num_graphs)):
+            return self
+        gi = torch.as_tensor(idx, dtype=torch.long)
+        ai = torch.cat([torch.arange(int(self.node_offsets[i]), int(self.node_offsets[i + 1])) for i in idx]) if idx else torch.zeros(0, dtype=torch.long)
+        dev = self.atom_types.device
+        gd, ad = gi.to(dev), ai.to(dev)
+        na = self.num_atoms[gi]
+        return Rollout(self.atom_types.index_select(1, ad), self.frac_coords.index_select(1, ad), self.frac_coords_mid.index_select(1, ad),
+                       self.lattices.index_select(1, gd), self.lp_old.index_select(1, gd), na,
+                       torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(na, 0)]), self.T, self.step_lr)
+
+
+def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=True):
+    """Sample like sample_mdp (same atom-count draw, seed handling and invalid_filter; geometric_filter=False keeps every crystal) and
+    keep the kept crystals' whole trajectories on the device as a Rollout -- compacted once per chain straight from the sampler's stacked
+    record buffers, without the per-step dict or a host copy.  Returns (sample_list, rollout).  The policy gradient (policy.pg_step)
+    consumes it.  CSP mode (keep_lattice / keep_coords) is refused: forward_logprb does not model it."""
+    from .filters import invalid_filter
+    if getattr(model, "keep_lattice", False) or getattr(model, "keep_coords", False):
+        raise ValueError("sample_rollout: CSP mode (keep_lattice / keep_coords) is not supported -- forward_logprb does not model a given "
+                         "lattice or given coordinates")
+    model.eval()
+    dataset = SampleDataset(total_num=sample_size)
+    step_lr = step_lr if step_lr >= 0 else DEFAULT_STEP_LR["gen"]["mp_20"]
+    counts = _AtomCounts(dataset.num_atoms)
+    sink = []
+    outputs, _ = model.sample(counts, step_lr=step_lr, seed=_draw_seed(seed), record=True, rec_sink=sink)
+    data_list = _unpack(model, counts, outputs)
+    valid = invalid_filter(data_list, return_mask=True) if geometric_filter else np.ones(len(data_list), dtype=bool)
+    sample_list = [d for d, ok in zip(data_list, valid) if ok]
+    valid = torch.as_tensor(np.asarray(valid, dtype=bool))
+    na = counts.num_atoms
+    T = model.beta_scheduler.timesteps
+    sink.sort(key=lambda e: e[0])
+    bounds = [e[0] for e in sink] + [len(na)]
+    parts = {k: [] for k in ("atom_types", "frac_coords", "frac_coords_mid", "lattices", "lp_old")}
+    for k, (g0, n0, rec) in enumerate(sink):
+        g1 = bounds[k + 1]
+        gv = valid[g0:g1]
+        dev = rec["lattices"].device
+        gi = torch.nonzero(gv).flatten().to(dev)
+        ai = torch.nonzero(torch.repeat_interleave(gv, na[g0:g1])).flatten().to(dev)
+        parts["atom_types"].append(rec["atom_types"].index_select(1, ai))
+        parts["frac_coords"].append(rec["frac_coords"].index_select(1, ai))
+        parts["frac_coords_mid"].append(rec["frac_coords_mid"].index_select(1, ai))
+        parts["lattices"].append(rec["lattices"].view(T + 1, -1, 9).index_select(1, gi))
+        parts["lp_old"].append(torch.stack((rec["log_prob_l"], rec["log_prob_t"], rec["log_prob_x"]), dim=-1).index_select(1, gi))
+    st = {k: (v[0] if len(v) == 1 else torch.cat(v, dim=1)) for k, v in parts.items()}
+    kept = na[valid]
+    rollout = Rollout(st["atom_types"], st["frac_coords"], st["frac_coords_mid"], st["lattices"], st["lp_old"], kept,
+                      torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(kept, 0)]), T, float(step_lr))
+    return sample_list, rollout
