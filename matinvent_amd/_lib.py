@@ -167,6 +167,12 @@ PG_SIGNATURES = {
     "mi_traj_pg_step": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P, C.c_float, _P, _P, _P, _P]),
 }
 
+# the KL-anchored policy-gradient extension, include/matinvent_hip_pg_kl.h (a header of its own: PG_SIGNATURES above is the policy-gradient header)
+PG_KL_SIGNATURES = {
+    "mi_traj_pg_kl_step": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P, C.c_float, C.c_float, _P, _P,
+                                _P, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -183,7 +189,8 @@ def load():
             f"matinvent_amd: HIP library not found at {LIB_PATH}; build it with `python -m matinvent_amd.build` "
             "(there is no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(TRAJ_SIGNATURES.items()) + list(PG_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(TRAJ_SIGNATURES.items()) + list(PG_SIGNATURES.items()) + \
+            list(PG_KL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

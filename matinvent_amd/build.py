@@ -29,7 +29,7 @@ if not os.environ.get("MI_ALLOW_PACKED_FP32"):   # (ablation only: rebuilds the 
 
 
 def _headers():
-    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", "matinvent_hip.h"), os.path.join(HERE, "..", "include", "matinvent_hip_debug.h"), os.path.join(HERE, "..", "include", "matinvent_hip_traj.h"), os.path.join(HERE, "..", "include", "matinvent_hip_pg.h"), __file__]
+    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", "matinvent_hip.h"), os.path.join(HERE, "..", "include", "matinvent_hip_debug.h"), os.path.join(HERE, "..", "include", "matinvent_hip_traj.h"), os.path.join(HERE, "..", "include", "matinvent_hip_pg.h"), os.path.join(HERE, "..", "include", "matinvent_hip_pg_kl.h"), __file__]
 
 
 # Library variants: "" = the product library; "tf32" = the TF32-CLASS build (every plane-set product keeps its leading fp16 x fp16 term only:
@@ -55,7 +55,7 @@ def _stale(variant: str = "") -> bool:
         if f.read() != _flags_tag(variant):
             return True
     t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "matinvent_hip.h"), os.path.join(HERE, "..", "include", "matinvent_hip_debug.h"), os.path.join(HERE, "..", "include", "matinvent_hip_traj.h"), os.path.join(HERE, "..", "include", "matinvent_hip_pg.h"), __file__]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "matinvent_hip.h"), os.path.join(HERE, "..", "include", "matinvent_hip_debug.h"), os.path.join(HERE, "..", "include", "matinvent_hip_traj.h"), os.path.join(HERE, "..", "include", "matinvent_hip_pg.h"), os.path.join(HERE, "..", "include", "matinvent_hip_pg_kl.h"), __file__]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -207,6 +207,11 @@ struct mi_batch {
     float *pg_na = nullptr, *pg_nx = nullptr, *pg_nl = nullptr;                    // [N][A], [N][3], [B][9]
     float *pg_lp = nullptr, *pg_g = nullptr;                                       // [3][B] each
     int* pg_t = nullptr;                                                           // [B] the times the kernels read (checked copy)
+    // mi_traj_pg_kl_step (allocated on first use).  Corrector handle: d KL_k / d(agent output) of the last call and the per-term KL when the
+    // caller keeps none.  Prior handle: the prior's corrector coordinate head (its predictor's heads stay in pred_l / pred_x / pred_t).
+    float *kl_dl = nullptr, *kl_dt = nullptr, *kl_dxc = nullptr, *kl_dxp = nullptr;   // [B][9], [N][A], [N][3], [N][3]
+    float* kl_val = nullptr;                                                            // [3][B]
+    float* kl_pxc = nullptr;                                                            // [N][3] (prior handle)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // fork / join of work put on an auxiliary stream (mi_ft_micro_step)
     std::vector<void*> allocs;
 };

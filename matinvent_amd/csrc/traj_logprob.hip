@@ -13,6 +13,7 @@
 
 #include "../../include/matinvent_hip_traj.h"
 #include "../../include/matinvent_hip_pg.h"
+#include "../../include/matinvent_hip_pg_kl.h"
 #include "net.h"
 #include "logprob.h"
 
@@ -309,6 +310,181 @@ static int pg_buffers(mi_batch* b) {
     return dev_alloc(b, &b->pg_g, (size_t)3 * b->B);   // (last: its presence marks the set complete)
 }
 
+// the argument checks of a policy-gradient micro-step, all on the host, before anything is enqueued (the kernels index the rollout with the times)
+static int pg_check(mi_net* net, mi_batch* bc, mi_batch* bp, const float* coef_dev, int T, const float* time_freqs, const float* traj_atom_types,
+                    const float* traj_frac, const float* traj_frac_mid, const float* traj_lattices, const float* traj_lp_old, const int* t_host,
+                    const int* t_dev, const float* adv_dev, float clip_range, const float* w_host, const float* grad_theta, const float* stats) {
+    MI_CHECK(net && bc && bp, MI_EINVAL, "null handle");
+    MI_CHECK(bc != bp, MI_EINVAL, "the corrector and the predictor evaluation need two distinct batch handles");
+    MI_CHECK(traj_handles_ok(net, bc, bp), MI_EINVAL, "batch was created for a different network");
+    MI_CHECK(same_counts(bc, bp), MI_EINVAL, "the two batch handles hold different atom counts");
+    MI_CHECK(coef_dev && time_freqs && traj_atom_types && traj_frac && traj_frac_mid && traj_lattices && traj_lp_old && t_host && t_dev &&
+                 adv_dev && w_host && grad_theta && stats, MI_EINVAL, "null argument");
+    MI_CHECK(T >= 2, MI_EINVAL, "T = %d: a recorded step needs T >= 2", T);
+    MI_CHECK(clip_range >= 0.f, MI_EINVAL, "clip_range = %g: must be >= 0", (double)clip_range);
+    MI_CHECK(net->W2T != nullptr, MI_ESTATE, "mi_net_set_params must run before backward");
+    for (int i = 0; i < bc->B; ++i)
+        MI_CHECK(t_host[i] >= 2 && t_host[i] <= T, MI_EINVAL, "t[%d] = %d: a recorded step has t in 2..T = %d", i, t_host[i], T);
+    return MI_OK;
+}
+
+// one gather launch: crystal b's state at t_b and t_b - 1 into bc's pg_* buffers, the checked times into pg_t
+static int pg_gather(mi_batch* bc, int T, const int* t_dev, const float* ta, const float* tx, const float* txm, const float* tl, hipStream_t s) {
+    const int B = bc->B, N = bc->N;
+    GatherArgs g;
+    g.t = t_dev, g.n2g = bc->node2graph;
+    g.ta = ta, g.tx = tx, g.txm = txm, g.tl = tl;
+    g.a = bc->pg_a, g.x = bc->pg_x, g.xm = bc->pg_xm, g.l = bc->pg_l, g.na = bc->pg_na, g.nx = bc->pg_nx, g.nl = bc->pg_nl;
+    g.t_out = bc->pg_t;
+    g.B = B, g.N = N, g.T = T;
+    const int64_t ng = 2 * (int64_t)N * MI_NUM_TYPES + 9 * (int64_t)N + 18 * (int64_t)B;
+    hipLaunchKernelGGL(traj_pg_gather_kernel, dim3(cdiv(ng, 256)), dim3(256), 0, s, g);
+    MI_KERNEL_CHECK();
+    return MI_OK;
+}
+
+// one surrogate launch: seeds into bc->pg_g, statistics rows 0..3
+static int pg_surrogate(mi_batch* bc, const float* lp, const float* traj_lp_old, const float* adv_dev, float clip_range, const float* w_host,
+                        float loss_scale, float* stats, hipStream_t s) {
+    const int B = bc->B;
+    SurrogateArgs u;
+    u.t = bc->pg_t, u.lp = lp, u.lp_old = traj_lp_old, u.adv = adv_dev, u.g = bc->pg_g, u.stats = stats;
+    u.w0 = w_host[0], u.w1 = w_host[1], u.w2 = w_host[2];
+    u.lo = (float)(1.0 - (double)clip_range), u.hi = (float)(1.0 + (double)clip_range), u.eps = clip_range;
+    u.scale = loss_scale;
+    u.B = B;
+    hipLaunchKernelGGL(traj_pg_surrogate_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, u);
+    MI_KERNEL_CHECK();
+    return MI_OK;
+}
+
+// ---- the KL anchor to a frozen prior (mi_traj_pg_kl_step) ---------------------------------------------------------------------------
+
+struct KlArgs {
+    const int* t;                                   // [B] (checked)
+    const float* coef;                              // [T+1][MI_NCOEF]
+    const int* node_off;                            // [B+1]
+    const float *pxc_a, *pl_a, *pxp_a, *pt_a;       // the agent: corrector coordinate head; predictor's three heads
+    const float *pxc_p, *pl_p, *pxp_p, *pt_p;       // the prior, same
+    float *dl, *dt, *dxc, *dxp;                     // d KL_k / d(agent output): [B][9], [N][A], [N][3], [N][3]
+    float* kl;                                      // [3][B] (KL_l, KL_t, KL_x)
+    float* stats;                                   // [B] row 4 of the statistics: += w . KL
+    float w0, w1, w2;
+    int B;
+};
+
+// one 256-thread block per crystal, the thread-to-element maps and reduction trees of traj_logprob_kernel: no atomics, same bits every call.
+// Every difference is taken between the two predictions, never between the two rounded means.
+__global__ __launch_bounds__(256) void traj_pg_kl_kernel(KlArgs a) {
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const StepCoef c = load_coef(a.coef, a.t[b]);
+    const int n0 = a.node_off[b], n1 = a.node_off[b + 1], n = n1 - n0;
+    const float cnt = (float)(n > 0 ? n : 1);
+
+    // coordinates: mu_a - mu_p = -s (p_a - p_p) on the torus, s = step * sqrt(sn); its nearest image mi(d) = d - rint(d); KL = mi^2 / (2 std^2),
+    // d KL / d p_a = mi * s / std^2, each coordinate with weight 1 / (3 n)
+    const float sc = c.step_corr * c.sqrt_sn, sp = c.step_pred * c.sqrt_sn;
+    const float kc = sc / c.std_corr_sq / 3.0f / cnt, kp = sp / c.std_pred_sq / 3.0f / cnt;
+    float klc = 0.f, klp = 0.f;
+    for (int idx = n0 * 3 + tid; idx < n1 * 3; idx += 256) {
+        float d = sc * (a.pxc_a[idx] - a.pxc_p[idx]);
+        d = d - rintf(d);
+        klc += (d * d) / (2.0f * c.std_corr_sq);
+        a.dxc[idx] = d * kc;
+        d = sp * (a.pxp_a[idx] - a.pxp_p[idx]);
+        d = d - rintf(d);
+        klp += (d * d) / (2.0f * c.std_pred_sq);
+        a.dxp[idx] = d * kp;
+    }
+    klc = block_sum_256(klc, red);
+    klp = block_sum_256(klp, red);
+
+    // lattice: m_a - m_p = -c0 c1 (pl_a - pl_p); KL = 1/9 sum (c0 c1 d)^2 / (2 sigma^2), d KL / d pl_a = c0 c1 (c0 c1 d) / (9 sigma^2)
+    const float cc = c.c0 * c.c1;
+    float kll = 0.f;
+    if (tid < 9) {
+        const int idx = b * 9 + tid;
+        const float d = cc * (a.pl_a[idx] - a.pl_p[idx]);
+        kll = (d * d) / (2.0f * c.sigma_sq);
+        a.dl[idx] = d * cc / c.sigma_sq / 9.0f;
+    }
+    kll = block_sum_256(kll, red);
+
+    // atom-type logits: the same Normal, mean over the 100 logits, then over the atoms; one wave per atom
+    const int lane = tid & 63, wave = tid >> 6;
+    const float kt = cc / c.sigma_sq / (float)MI_NUM_TYPES / cnt;
+    float klt = 0.f;
+    for (int i = n0 + wave; i < n1; i += 4) {
+        float s = 0.f;
+        for (int k = lane; k < MI_NUM_TYPES; k += 64) {
+            const size_t idx = (size_t)i * MI_NUM_TYPES + k;
+            const float d = cc * (a.pt_a[idx] - a.pt_p[idx]);
+            s += (d * d) / (2.0f * c.sigma_sq);
+            a.dt[idx] = d * kt;
+        }
+        s = wave_sum(s);
+        klt += s / (float)MI_NUM_TYPES;
+    }
+    __syncthreads();
+    if (lane == 0) red[wave] = klt;
+    __syncthreads();
+    if (tid == 0) {
+        const float l = kll / 9.0f;
+        const float t = ((red[0] + red[1]) + (red[2] + red[3])) / cnt;
+        const float x = (klc / 3.0f) / cnt + (klp / 3.0f) / cnt;
+        a.kl[b] = l;
+        a.kl[a.B + b] = t;
+        a.kl[2 * a.B + b] = x;
+        a.stats[b] += (a.w0 * l + a.w1 * t) + a.w2 * x;
+    }
+}
+
+struct KlSeedArgs {
+    const float* g;                                 // [3][B] the surrogate's seeds (w_k g_b)
+    const int* n2g;                                 // [N]
+    const float *dl, *dx_corr, *dx_pred, *dt;       // the log-probabilities' local derivatives
+    const float *kdl, *kdxc, *kdxp, *kdt;           // the KL's local derivatives
+    float kl0, kl1, kl2;                            // kl_coef * loss_scale * w_k
+    float *sc_l, *sc_x, *sc_t, *sp_l, *sp_x, *sp_t; // seeds of the corrector's / predictor's backward
+    int B, N;
+};
+
+// traj_seed_kernel's map, one thread per output element of both evaluations; seed = g_b dlp + (kl_coef loss_scale w_k) dKL.  The corrector's
+// lattice and type heads enter neither term: their seeds are zero.
+__global__ __launch_bounds__(256) void traj_pg_kl_seed_kernel(KlSeedArgs a) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nl = (int64_t)a.B * 9, nx = (int64_t)a.N * 3, nt = (int64_t)a.N * MI_NUM_TYPES;
+    if (i < nl) {
+        a.sp_l[i] = a.g[i / 9] * a.dl[i] + a.kl0 * a.kdl[i];
+        a.sc_l[i] = 0.f;
+        return;
+    }
+    i -= nl;
+    if (i < nx) {
+        const float gx = a.g[2 * a.B + a.n2g[i / 3]];
+        a.sp_x[i] = gx * a.dx_pred[i] + a.kl2 * a.kdxp[i];
+        a.sc_x[i] = gx * a.dx_corr[i] + a.kl2 * a.kdxc[i];
+        return;
+    }
+    i -= nx;
+    if (i < nt) {
+        a.sp_t[i] = a.g[a.B + a.n2g[i / MI_NUM_TYPES]] * a.dt[i] + a.kl1 * a.kdt[i];
+        a.sc_t[i] = 0.f;
+    }
+}
+
+static int kl_buffers(mi_batch* bc, mi_batch* pb) {
+    if (!pb->kl_pxc) MI_TRY(dev_alloc(pb, &pb->kl_pxc, (size_t)pb->N * 3));
+    if (bc->kl_dl) return MI_OK;
+    const size_t nt = (size_t)bc->N * MI_NUM_TYPES, nx = (size_t)bc->N * 3, nl = (size_t)bc->B * 9;
+    MI_TRY(dev_alloc(bc, &bc->kl_dt, nt));
+    MI_TRY(dev_alloc(bc, &bc->kl_dxc, nx));
+    MI_TRY(dev_alloc(bc, &bc->kl_dxp, nx));
+    MI_TRY(dev_alloc(bc, &bc->kl_val, (size_t)3 * bc->B));
+    return dev_alloc(bc, &bc->kl_dl, nl);   // (last: its presence marks the set complete)
+}
+
 }  // namespace mi
 
 using namespace mi;
@@ -367,46 +543,89 @@ int mi_traj_pg_step(mi_net* net, mi_batch* bc, mi_batch* bp, const float* coef_d
                     const float* traj_atom_types, const float* traj_frac, const float* traj_frac_mid, const float* traj_lattices,
                     const float* traj_lp_old, const int* t_host, const int* t_dev, const float* adv_dev, float clip_range,
                     const float* w_host, float loss_scale, float* log_prob, float* grad_theta, float* stats, void* stream) {
-    MI_CHECK(net && bc && bp, MI_EINVAL, "null handle");
-    MI_CHECK(bc != bp, MI_EINVAL, "the corrector and the predictor evaluation need two distinct batch handles");
-    MI_CHECK(traj_handles_ok(net, bc, bp), MI_EINVAL, "batch was created for a different network");
-    MI_CHECK(same_counts(bc, bp), MI_EINVAL, "the two batch handles hold different atom counts");
-    MI_CHECK(coef_dev && time_freqs && traj_atom_types && traj_frac && traj_frac_mid && traj_lattices && traj_lp_old && t_host && t_dev &&
-                 adv_dev && w_host && grad_theta && stats, MI_EINVAL, "null argument");
-    MI_CHECK(T >= 2, MI_EINVAL, "T = %d: a recorded step needs T >= 2", T);
-    MI_CHECK(clip_range >= 0.f, MI_EINVAL, "clip_range = %g: must be >= 0", (double)clip_range);
-    MI_CHECK(net->W2T != nullptr, MI_ESTATE, "mi_net_set_params must run before backward");
-    const int B = bc->B, N = bc->N;
-    // every time is checked before anything is enqueued: the kernels index the rollout with them
-    for (int i = 0; i < B; ++i)
-        MI_CHECK(t_host[i] >= 2 && t_host[i] <= T, MI_EINVAL, "t[%d] = %d: a recorded step has t in 2..T = %d", i, t_host[i], T);
-    if (B == 0 || N == 0) return MI_OK;
+    MI_TRY(pg_check(net, bc, bp, coef_dev, T, time_freqs, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, traj_lp_old, t_host, t_dev,
+                    adv_dev, clip_range, w_host, grad_theta, stats));
+    if (bc->B == 0 || bc->N == 0) return MI_OK;
     MI_TRY(pg_buffers(bc));
     hipStream_t s = (hipStream_t)stream;
-
-    GatherArgs g;
-    g.t = t_dev, g.n2g = bc->node2graph;
-    g.ta = traj_atom_types, g.tx = traj_frac, g.txm = traj_frac_mid, g.tl = traj_lattices;
-    g.a = bc->pg_a, g.x = bc->pg_x, g.xm = bc->pg_xm, g.l = bc->pg_l, g.na = bc->pg_na, g.nx = bc->pg_nx, g.nl = bc->pg_nl;
-    g.t_out = bc->pg_t;
-    g.B = B, g.N = N, g.T = T;
-    const int64_t ng = 2 * (int64_t)N * MI_NUM_TYPES + 9 * (int64_t)N + 18 * (int64_t)B;
-    hipLaunchKernelGGL(traj_pg_gather_kernel, dim3(cdiv(ng, 256)), dim3(256), 0, s, g);
-    MI_KERNEL_CHECK();
+    MI_TRY(pg_gather(bc, T, t_dev, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, s));
 
     float* lp = log_prob ? log_prob : bc->pg_lp;
     MI_TRY(traj_logprob_enqueue(net, bc, bp, bc->pg_t, coef_dev, time_freqs, bc->pg_a, bc->pg_x, bc->pg_xm, bc->pg_l, bc->pg_na, bc->pg_nx,
                                 bc->pg_nl, lp, nullptr, nullptr, nullptr, 1, stream));
-
-    SurrogateArgs u;
-    u.t = bc->pg_t, u.lp = lp, u.lp_old = traj_lp_old, u.adv = adv_dev, u.g = bc->pg_g, u.stats = stats;
-    u.w0 = w_host[0], u.w1 = w_host[1], u.w2 = w_host[2];
-    u.lo = (float)(1.0 - (double)clip_range), u.hi = (float)(1.0 + (double)clip_range), u.eps = clip_range;
-    u.scale = loss_scale;
-    u.B = B;
-    hipLaunchKernelGGL(traj_pg_surrogate_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, u);
-    MI_KERNEL_CHECK();
+    MI_TRY(pg_surrogate(bc, lp, traj_lp_old, adv_dev, clip_range, w_host, loss_scale, stats, s));
     return mi_traj_logprob_backward(net, bc, bp, bc->pg_g, nullptr, nullptr, nullptr, grad_theta, stream);
+}
+
+int mi_traj_pg_kl_step(mi_net* net, mi_batch* bc, mi_batch* bp, mi_net* prior, mi_batch* pb, const float* coef_dev, int T,
+                       const float* time_freqs, const float* traj_atom_types, const float* traj_frac, const float* traj_frac_mid,
+                       const float* traj_lattices, const float* traj_lp_old, const int* t_host, const int* t_dev, const float* adv_dev,
+                       float clip_range, const float* w_host, float loss_scale, float kl_coef, float* log_prob, float* kl_out,
+                       float* grad_theta, float* stats, void* stream, void* aux_stream) {
+    MI_TRY(pg_check(net, bc, bp, coef_dev, T, time_freqs, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, traj_lp_old, t_host, t_dev,
+                    adv_dev, clip_range, w_host, grad_theta, stats));
+    MI_CHECK(prior && pb, MI_EINVAL, "null prior handle");
+    MI_CHECK(pb != bc && pb != bp, MI_EINVAL, "the prior needs a batch handle of its own");
+    MI_CHECK(pb->H == prior->H && pb->L == prior->L, MI_EINVAL, "prior batch was created for a different network");
+    MI_CHECK(same_counts(bc, pb), MI_EINVAL, "the prior's batch handle holds different atom counts");
+    MI_CHECK(prior->TD == net->TD, MI_EINVAL, "the prior's time embedding has %d dimensions, the agent's %d (one frequency table serves both)", prior->TD, net->TD);
+    MI_CHECK(kl_coef >= 0.f, MI_EINVAL, "kl_coef = %g: must be >= 0", (double)kl_coef);
+    MI_CHECK(prior->theta != nullptr, MI_ESTATE, "mi_net_set_params must run on the prior before it is evaluated");
+    const int B = bc->B, N = bc->N;
+    if (B == 0 || N == 0) return MI_OK;
+    MI_TRY(pg_buffers(bc));
+    MI_TRY(kl_buffers(bc, pb));
+    hipStream_t s = (hipStream_t)stream;
+    // 1. the gather; 2. the prior's two inference evaluations on the gathered state (its own time embedding, from the gathered times)
+    MI_TRY(pg_gather(bc, T, t_dev, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, s));
+    MI_TRY(mi_time_embedding(bc->pg_t, time_freqs, B, prior->TD, pb->temb, stream));
+    const bool aux = aux_stream && aux_stream != stream;
+    hipStream_t sp = aux ? (hipStream_t)aux_stream : s;
+    if (aux) {
+        if (!pb->ev_fork) {
+            MI_HIP(hipEventCreateWithFlags(&pb->ev_fork, hipEventDisableTiming));
+            MI_HIP(hipEventCreateWithFlags(&pb->ev_join, hipEventDisableTiming));
+        }
+        MI_HIP(hipEventRecord(pb->ev_fork, s));
+        MI_HIP(hipStreamWaitEvent(sp, pb->ev_fork, 0));
+    }
+    // (the corrector evaluation's coordinate head alone is read: its lattice / type heads land in pred_l / pred_t, which the predictor overwrites)
+    MI_TRY(net_forward(prior, pb, pb->temb, bc->pg_a, bc->pg_x, bc->pg_l, pb->pred_l, pb->kl_pxc, pb->pred_t, sp, false, false, true));
+    MI_TRY(net_forward(prior, pb, pb->temb, bc->pg_a, bc->pg_xm, bc->pg_l, pb->pred_l, pb->pred_x, pb->pred_t, sp, false));
+    if (aux) MI_HIP(hipEventRecord(pb->ev_join, sp));
+    // 3. the agent's two taped evaluations and the log-probabilities
+    float* lp = log_prob ? log_prob : bc->pg_lp;
+    MI_TRY(traj_logprob_enqueue(net, bc, bp, bc->pg_t, coef_dev, time_freqs, bc->pg_a, bc->pg_x, bc->pg_xm, bc->pg_l, bc->pg_na, bc->pg_nx,
+                                bc->pg_nl, lp, nullptr, nullptr, nullptr, 1, stream));
+    if (aux) MI_HIP(hipStreamWaitEvent(s, pb->ev_join, 0));
+    // 4. the KL and its local derivatives
+    KlArgs k;
+    k.t = bc->pg_t, k.coef = coef_dev, k.node_off = bc->node_off;
+    k.pxc_a = bc->pred_x, k.pl_a = bp->pred_l, k.pxp_a = bp->pred_x, k.pt_a = bp->pred_t;
+    k.pxc_p = pb->kl_pxc, k.pl_p = pb->pred_l, k.pxp_p = pb->pred_x, k.pt_p = pb->pred_t;
+    k.dl = bc->kl_dl, k.dt = bc->kl_dt, k.dxc = bc->kl_dxc, k.dxp = bc->kl_dxp;
+    k.kl = kl_out ? kl_out : bc->kl_val;
+    k.stats = stats + 4 * (size_t)B;
+    k.w0 = w_host[0], k.w1 = w_host[1], k.w2 = w_host[2];
+    k.B = B;
+    hipLaunchKernelGGL(traj_pg_kl_kernel, dim3(B), dim3(256), 0, s, k);
+    MI_KERNEL_CHECK();
+    // 5. the surrogate; 6. the seeds of both evaluations (surrogate + KL); 7. one backward per evaluation
+    MI_TRY(pg_surrogate(bc, lp, traj_lp_old, adv_dev, clip_range, w_host, loss_scale, stats, s));
+    KlSeedArgs g;
+    g.g = bc->pg_g, g.n2g = bc->node2graph;
+    g.dl = bp->tr_dl, g.dx_corr = bc->tr_dx, g.dx_pred = bp->tr_dx, g.dt = bp->tr_dt;
+    g.kdl = bc->kl_dl, g.kdxc = bc->kl_dxc, g.kdxp = bc->kl_dxp, g.kdt = bc->kl_dt;
+    const float kc = kl_coef * loss_scale;
+    g.kl0 = kc * w_host[0], g.kl1 = kc * w_host[1], g.kl2 = kc * w_host[2];
+    g.sc_l = bc->tr_sl, g.sc_x = bc->tr_sx, g.sc_t = bc->tr_st;
+    g.sp_l = bp->tr_sl, g.sp_x = bp->tr_sx, g.sp_t = bp->tr_st;
+    g.B = B, g.N = N;
+    const int64_t n = (int64_t)B * 9 + (int64_t)N * (3 + MI_NUM_TYPES);
+    hipLaunchKernelGGL(traj_pg_kl_seed_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, g);
+    MI_KERNEL_CHECK();
+    MI_TRY(net_backward(net, bp, bp->tr_sl, bp->tr_sx, bp->tr_st, grad_theta, s));
+    return net_backward(net, bc, bc->tr_sl, bc->tr_sx, bc->tr_st, grad_theta, s);
 }
 
 }  // extern "C"

@@ -156,7 +156,8 @@ class MatInventPG(MatInvent):
     reward-weighted denoising loss.  Each RL loop: rollout (sampling.sample_rollout: the kept crystals' chains stay on the device) ->
     the validity pre-filter, the optional filter callable and max_num, as in MatInvent -> reward_step -> pg_step over EVERY kept
     crystal.  On-policy: there is no top-k and no replay (a stored crystal's log-probabilities belong to weights that no longer exist),
-    so replay=True is refused.  Single GPU, DiffCSP only (MatterGen has no log-probability path), one sampling batch per loop."""
+    so replay=True is refused.  Single GPU, DiffCSP only (MatterGen has no log-probability path), one sampling batch per loop.
+    finetune_cfg.kl_coef > 0 anchors the agent's transitions to the frozen prior's (policy.pg_step) and logs prior_kl."""
 
     def __init__(self, rl_epoch, model_suite, reward, sample_cfg, finetune_cfg, save_dir, save_freq=50, device=None, logger=None,
                  replay=False, replay_args=None, topk_ratio=1.0, **kwargs):
@@ -216,10 +217,12 @@ class MatInventPG(MatInvent):
                 self.logger.log(log, step=self.step)
             return
         rollout = rollout.select([self._rollout_pos[id(d)] for d in data])
-        stats = pg_step(self.agent, rollout, rewards, self.finetune_cfg, seed=self.sampler.seed)
+        stats = pg_step(self.agent, rollout, rewards, self.finetune_cfg, seed=self.sampler.seed, prior=self.prior)
         last = stats[-1] if stats else {}
         log.update({"clip_frac": last.get("clip_frac", float("nan")), "approx_kl": last.get("approx_kl", float("nan")),
                     "ratio mean": last.get("ratio_mean", float("nan"))})
+        if float(self.finetune_cfg.get("kl_coef", 0.0) or 0.0) > 0.0:
+            log["prior_kl"] = last.get("prior_kl", float("nan"))
         if self.logger is not None:
             self.logger.log(log, step=self.step)
         logging.info(f"*****   LOOP {self.step} FINISH   *****  {(time.time() - t0) / 60:.2f} min")
