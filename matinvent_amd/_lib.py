@@ -173,6 +173,9 @@ PG_KL_SIGNATURES = {
                                 _P, _P, _P, _P]),
 }
 
+# every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
+EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES)
+
 _lib = None
 
 
@@ -189,11 +192,11 @@ def load():
             f"matinvent_amd: HIP library not found at {LIB_PATH}; build it with `python -m matinvent_amd.build` "
             "(there is no CPU fallback)")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(TRAJ_SIGNATURES.items()) + list(PG_SIGNATURES.items()) + \
-            list(PG_KL_SIGNATURES.items()):
-        fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
-        fn.restype = res
-        fn.argtypes = args
+    for table in (SIGNATURES,) + EXTENSION_SIGNATURES:
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 

@@ -15,6 +15,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libmatinvent_hip.so")
 OBJ = os.path.join(HERE, "lib", "obj")
 SOURCES = ["cspnet.hip", "node_chain.hip", "node_bwd.hip", "edge_stage.hip", "edge_fused.hip", "sampler.hip", "backward.hip", "graph.hip", "gemnet.hip", "traj_logprob.hip"]
+# the public headers, include/*.h: every object and the library depend on all of them (a new extension header is picked up by itself)
+PUBLIC_HEADERS = sorted(os.path.join(HERE, "..", "include", f) for f in os.listdir(os.path.join(HERE, "..", "include")) if f.endswith(".h"))
 ARCH = ["--offload-arch=gfx950"]
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 # NO packed-fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 / v_pk_mov_b32) in device code.  Measured on MI355X
@@ -29,7 +31,7 @@ if not os.environ.get("MI_ALLOW_PACKED_FP32"):   # (ablation only: rebuilds the 
 
 
 def _headers():
-    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(HERE, "..", "include", "matinvent_hip.h"), os.path.join(HERE, "..", "include", "matinvent_hip_debug.h"), os.path.join(HERE, "..", "include", "matinvent_hip_traj.h"), os.path.join(HERE, "..", "include", "matinvent_hip_pg.h"), os.path.join(HERE, "..", "include", "matinvent_hip_pg_kl.h"), __file__]
+    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + PUBLIC_HEADERS + [__file__]
 
 
 # Library variants: "" = the product library; "tf32" = the TF32-CLASS build (every plane-set product keeps its leading fp16 x fp16 term only:
@@ -55,7 +57,7 @@ def _stale(variant: str = "") -> bool:
         if f.read() != _flags_tag(variant):
             return True
     t = os.path.getmtime(lib)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "matinvent_hip.h"), os.path.join(HERE, "..", "include", "matinvent_hip_debug.h"), os.path.join(HERE, "..", "include", "matinvent_hip_traj.h"), os.path.join(HERE, "..", "include", "matinvent_hip_pg.h"), os.path.join(HERE, "..", "include", "matinvent_hip_pg_kl.h"), __file__]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + PUBLIC_HEADERS + [__file__]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

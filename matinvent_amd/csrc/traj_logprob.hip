@@ -1,14 +1,12 @@
 // Log-probabilities of one recorded reverse-diffusion step under the current weights, and their gradient seeds:
-// DiffCSPModule.forward_logprb (models/diffcsp/diffusion.py:158-227), include/matinvent_hip_traj.h.
+// DiffCSPModule.forward_logprb (models/diffcsp/diffusion.py:158-227), include/matinvent_hip_traj.h; and the policy-gradient micro-step built
+// on them, with or without the KL anchor to a frozen prior (include/matinvent_hip_pg.h, _pg_kl.h): its stages are listed at pg_enqueue.
 //
-// The network evaluations are the library's own (mi_cspnet_forward / _train, mi_cspnet_backward); this unit adds the arithmetic after
-// them -- one launch that turns the two evaluations' outputs into the three per-crystal log-probabilities (and, for a taped call, their
-// local derivatives with respect to every network output), and one launch that scales those derivatives by the upstream gradients.
-// The log-probability terms are the sampler's (logprob.h); the arithmetic mirrors the reference's separately-rounded fp32 tensor ops,
-// so contraction into FMAs is disabled for this translation unit, as for sampler.hip.
+// The network evaluations are the library's own (net_forward, net_backward); this unit adds the arithmetic around them.  The log-probability
+// terms are the sampler's (logprob.h); the arithmetic mirrors the reference's separately-rounded fp32 tensor ops, so contraction into FMAs is
+// disabled for this translation unit, as for sampler.hip.
 #pragma clang fp contract(off)
 
-#include <algorithm>
 #include <vector>
 
 #include "../../include/matinvent_hip_traj.h"
@@ -119,43 +117,50 @@ struct SeedArgs {
     const float* g;      // [3][B] upstream gradients of (log_prob_l, log_prob_t, log_prob_x)
     const int* n2g;      // [N]
     const float *dl, *dx_corr, *dx_pred, *dt;                      // local derivatives of the forward
-    const float *uc_l, *uc_x, *uc_t;                               // upstream gradients of the returned corrector predictions (or NULL)
+    const float *uc_l, *uc_x, *uc_t;                               // !KL: upstream gradients of the returned corrector predictions (or NULL)
     float *sc_l, *sc_x, *sc_t, *sp_l, *sp_x, *sp_t;                // seeds of the corrector's / predictor's backward
     int B, N;
+    const float *kdl, *kdxc, *kdxp, *kdt;                          // KL: the KL's local derivatives ...
+    float kl0, kl1, kl2;                                           // ... and their weights kl_coef * loss_scale * w_k
 };
 
-// one thread per output element of both evaluations: B*9 + N*3 + N*A for each
+// one thread per output element of both evaluations: B*9 + N*3 + N*A for each.  !KL: seed = g_b dlp, plus the corrector predictions' own
+// upstream gradient (+ 0.f without one).  KL: seed = g_b dlp + (kl_coef loss_scale w_k) dKL; the corrector's lattice and type heads enter
+// neither term, their seeds are zero.
+template <bool KL>
 __global__ __launch_bounds__(256) void traj_seed_kernel(SeedArgs a) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t nl = (int64_t)a.B * 9, nx = (int64_t)a.N * 3, nt = (int64_t)a.N * MI_NUM_TYPES;
     if (i < nl) {
-        a.sp_l[i] = a.g[i / 9] * a.dl[i];
-        a.sc_l[i] = a.uc_l ? a.uc_l[i] : 0.f;
+        a.sp_l[i] = KL ? a.g[i / 9] * a.dl[i] + a.kl0 * a.kdl[i] : a.g[i / 9] * a.dl[i];
+        a.sc_l[i] = !KL && a.uc_l ? a.uc_l[i] : 0.f;
         return;
     }
     i -= nl;
     if (i < nx) {
         const float gx = a.g[2 * a.B + a.n2g[i / 3]];
-        a.sp_x[i] = gx * a.dx_pred[i];
-        a.sc_x[i] = gx * a.dx_corr[i] + (a.uc_x ? a.uc_x[i] : 0.f);
+        a.sp_x[i] = KL ? gx * a.dx_pred[i] + a.kl2 * a.kdxp[i] : gx * a.dx_pred[i];
+        a.sc_x[i] = gx * a.dx_corr[i] + (KL ? a.kl2 * a.kdxc[i] : (a.uc_x ? a.uc_x[i] : 0.f));
         return;
     }
     i -= nx;
     if (i < nt) {
-        a.sp_t[i] = a.g[a.B + a.n2g[i / MI_NUM_TYPES]] * a.dt[i];
-        a.sc_t[i] = a.uc_t ? a.uc_t[i] : 0.f;
+        const float gt = a.g[a.B + a.n2g[i / MI_NUM_TYPES]];
+        a.sp_t[i] = KL ? gt * a.dt[i] + a.kl1 * a.kdt[i] : gt * a.dt[i];
+        a.sc_t[i] = !KL && a.uc_t ? a.uc_t[i] : 0.f;
     }
 }
 
+// a handle's buffer set, allocated on first use; the last entry is allocated last, so its presence marks the set complete
+static int alloc_set(mi_batch* b, std::initializer_list<std::pair<float**, size_t>> set) {
+    if (*(set.end() - 1)->first) return MI_OK;
+    for (const auto& e : set) MI_TRY(dev_alloc(b, e.first, e.second));
+    return MI_OK;
+}
+
 static int traj_buffers(mi_batch* b) {
-    if (b->tr_dx) return MI_OK;
     const size_t nl = (size_t)b->B * 9, nx = (size_t)b->N * 3, nt = (size_t)b->N * MI_NUM_TYPES;
-    MI_TRY(dev_alloc(b, &b->tr_dl, nl));
-    MI_TRY(dev_alloc(b, &b->tr_dt, nt));
-    MI_TRY(dev_alloc(b, &b->tr_sl, nl));
-    MI_TRY(dev_alloc(b, &b->tr_sx, nx));
-    MI_TRY(dev_alloc(b, &b->tr_st, nt));
-    return dev_alloc(b, &b->tr_dx, nx);   // (last: its presence marks the set complete)
+    return alloc_set(b, {{&b->tr_dl, nl}, {&b->tr_dt, nt}, {&b->tr_sl, nl}, {&b->tr_sx, nx}, {&b->tr_st, nt}, {&b->tr_dx, nx}});
 }
 
 static bool same_counts(const mi_batch* p, const mi_batch* q) {
@@ -296,18 +301,10 @@ __global__ __launch_bounds__(256) void traj_pg_surrogate_kernel(SurrogateArgs a)
 }
 
 static int pg_buffers(mi_batch* b) {
-    if (b->pg_g) return MI_OK;
-    const size_t nt = (size_t)b->N * MI_NUM_TYPES, nx = (size_t)b->N * 3, nl = (size_t)b->B * 9;
-    MI_TRY(dev_alloc(b, &b->pg_a, nt));
-    MI_TRY(dev_alloc(b, &b->pg_na, nt));
-    MI_TRY(dev_alloc(b, &b->pg_x, nx));
-    MI_TRY(dev_alloc(b, &b->pg_xm, nx));
-    MI_TRY(dev_alloc(b, &b->pg_nx, nx));
-    MI_TRY(dev_alloc(b, &b->pg_l, nl));
-    MI_TRY(dev_alloc(b, &b->pg_nl, nl));
-    MI_TRY(dev_alloc(b, &b->pg_lp, (size_t)3 * b->B));
-    MI_TRY(dev_alloc(b, &b->pg_t, (size_t)b->B));
-    return dev_alloc(b, &b->pg_g, (size_t)3 * b->B);   // (last: its presence marks the set complete)
+    const size_t nt = (size_t)b->N * MI_NUM_TYPES, nx = (size_t)b->N * 3, nl = (size_t)b->B * 9, n3 = (size_t)3 * b->B;
+    if (!b->pg_t) MI_TRY(dev_alloc(b, &b->pg_t, (size_t)b->B));
+    return alloc_set(b, {{&b->pg_a, nt}, {&b->pg_na, nt}, {&b->pg_x, nx}, {&b->pg_xm, nx}, {&b->pg_nx, nx}, {&b->pg_l, nl}, {&b->pg_nl, nl},
+                         {&b->pg_lp, n3}, {&b->pg_g, n3}});
 }
 
 // the argument checks of a policy-gradient micro-step, all on the host, before anything is enqueued (the kernels index the rollout with the times)
@@ -440,49 +437,100 @@ __global__ __launch_bounds__(256) void traj_pg_kl_kernel(KlArgs a) {
     }
 }
 
-struct KlSeedArgs {
-    const float* g;                                 // [3][B] the surrogate's seeds (w_k g_b)
-    const int* n2g;                                 // [N]
-    const float *dl, *dx_corr, *dx_pred, *dt;       // the log-probabilities' local derivatives
-    const float *kdl, *kdxc, *kdxp, *kdt;           // the KL's local derivatives
-    float kl0, kl1, kl2;                            // kl_coef * loss_scale * w_k
-    float *sc_l, *sc_x, *sc_t, *sp_l, *sp_x, *sp_t; // seeds of the corrector's / predictor's backward
-    int B, N;
-};
-
-// traj_seed_kernel's map, one thread per output element of both evaluations; seed = g_b dlp + (kl_coef loss_scale w_k) dKL.  The corrector's
-// lattice and type heads enter neither term: their seeds are zero.
-__global__ __launch_bounds__(256) void traj_pg_kl_seed_kernel(KlSeedArgs a) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t nl = (int64_t)a.B * 9, nx = (int64_t)a.N * 3, nt = (int64_t)a.N * MI_NUM_TYPES;
-    if (i < nl) {
-        a.sp_l[i] = a.g[i / 9] * a.dl[i] + a.kl0 * a.kdl[i];
-        a.sc_l[i] = 0.f;
-        return;
-    }
-    i -= nl;
-    if (i < nx) {
-        const float gx = a.g[2 * a.B + a.n2g[i / 3]];
-        a.sp_x[i] = gx * a.dx_pred[i] + a.kl2 * a.kdxp[i];
-        a.sc_x[i] = gx * a.dx_corr[i] + a.kl2 * a.kdxc[i];
-        return;
-    }
-    i -= nx;
-    if (i < nt) {
-        a.sp_t[i] = a.g[a.B + a.n2g[i / MI_NUM_TYPES]] * a.dt[i] + a.kl1 * a.kdt[i];
-        a.sc_t[i] = 0.f;
-    }
+static int kl_buffers(mi_batch* bc, mi_batch* pb) {
+    const size_t nt = (size_t)bc->N * MI_NUM_TYPES, nx = (size_t)bc->N * 3, nl = (size_t)bc->B * 9;
+    MI_TRY(alloc_set(pb, {{&pb->kl_pxc, (size_t)pb->N * 3}}));
+    return alloc_set(bc, {{&bc->kl_dt, nt}, {&bc->kl_dxc, nx}, {&bc->kl_dxp, nx}, {&bc->kl_val, (size_t)3 * bc->B}, {&bc->kl_dl, nl}});
 }
 
-static int kl_buffers(mi_batch* bc, mi_batch* pb) {
-    if (!pb->kl_pxc) MI_TRY(dev_alloc(pb, &pb->kl_pxc, (size_t)pb->N * 3));
-    if (bc->kl_dl) return MI_OK;
-    const size_t nt = (size_t)bc->N * MI_NUM_TYPES, nx = (size_t)bc->N * 3, nl = (size_t)bc->B * 9;
-    MI_TRY(dev_alloc(bc, &bc->kl_dt, nt));
-    MI_TRY(dev_alloc(bc, &bc->kl_dxc, nx));
-    MI_TRY(dev_alloc(bc, &bc->kl_dxp, nx));
-    MI_TRY(dev_alloc(bc, &bc->kl_val, (size_t)3 * bc->B));
-    return dev_alloc(bc, &bc->kl_dl, nl);   // (last: its presence marks the set complete)
+// one KL launch: per-term KL into `kl`, their weighted sum onto statistics row 4, the local derivatives into bc's kl_d* buffers
+static int kl_launch(mi_batch* bc, mi_batch* bp, mi_batch* pb, const float* coef_dev, const float* w_host, float* kl, float* stats, hipStream_t s) {
+    KlArgs k;
+    k.t = bc->pg_t, k.coef = coef_dev, k.node_off = bc->node_off;
+    k.pxc_a = bc->pred_x, k.pl_a = bp->pred_l, k.pxp_a = bp->pred_x, k.pt_a = bp->pred_t;
+    k.pxc_p = pb->kl_pxc, k.pl_p = pb->pred_l, k.pxp_p = pb->pred_x, k.pt_p = pb->pred_t;
+    k.dl = bc->kl_dl, k.dt = bc->kl_dt, k.dxc = bc->kl_dxc, k.dxp = bc->kl_dxp;
+    k.kl = kl;
+    k.stats = stats + 4 * (size_t)bc->B;
+    k.w0 = w_host[0], k.w1 = w_host[1], k.w2 = w_host[2];
+    k.B = bc->B;
+    hipLaunchKernelGGL(traj_pg_kl_kernel, dim3(bc->B), dim3(256), 0, s, k);
+    MI_KERNEL_CHECK();
+    return MI_OK;
+}
+
+// the seeds of both evaluations of the taped call pending on (bc, bp), then one backward per evaluation.  kl_w NULL: seeds from the upstream
+// gradients g and d_corr_* (each may be NULL); else g plus kl_w[k] times the KL derivatives in bc's kl_d* buffers.
+static int traj_seed_backward(mi_net* net, mi_batch* bc, mi_batch* bp, const float* g, const float* d_corr_l, const float* d_corr_x,
+                              const float* d_corr_t, const float* kl_w, float* grad_theta, hipStream_t s) {
+    const int B = bc->B, N = bc->N;
+    SeedArgs a;
+    a.g = g;
+    a.n2g = bc->node2graph;
+    a.dl = bp->tr_dl, a.dx_corr = bc->tr_dx, a.dx_pred = bp->tr_dx, a.dt = bp->tr_dt;
+    a.uc_l = d_corr_l, a.uc_x = d_corr_x, a.uc_t = d_corr_t;
+    a.kdl = bc->kl_dl, a.kdxc = bc->kl_dxc, a.kdxp = bc->kl_dxp, a.kdt = bc->kl_dt;
+    a.kl0 = kl_w ? kl_w[0] : 0.f, a.kl1 = kl_w ? kl_w[1] : 0.f, a.kl2 = kl_w ? kl_w[2] : 0.f;
+    a.sc_l = bc->tr_sl, a.sc_x = bc->tr_sx, a.sc_t = bc->tr_st;
+    a.sp_l = bp->tr_sl, a.sp_x = bp->tr_sx, a.sp_t = bp->tr_st;
+    a.B = B, a.N = N;
+    const int64_t n = (int64_t)B * 9 + (int64_t)N * (3 + MI_NUM_TYPES);
+    if (kl_w) {
+        hipLaunchKernelGGL(traj_seed_kernel<true>, dim3(cdiv(n, 256)), dim3(256), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(traj_seed_kernel<false>, dim3(cdiv(n, 256)), dim3(256), 0, s, a);
+    }
+    MI_KERNEL_CHECK();
+    MI_TRY(net_backward(net, bp, bp->tr_sl, bp->tr_sx, bp->tr_st, grad_theta, s));
+    return net_backward(net, bc, bc->tr_sl, bc->tr_sx, bc->tr_st, grad_theta, s);
+}
+
+// The policy-gradient micro-step after its argument checks (pg_check; with a prior, the entry's own), everything enqueued, no host
+// synchronisation.  prior / pb NULL: the clipped surrogate alone (mi_traj_pg_step); else with the KL anchor (mi_traj_pg_kl_step).
+//   1. the buffers, on first use
+//   2. the gather: crystal b's recorded state at t_b and t_b - 1
+//   3. (prior) its time embedding and two inference evaluations of the gathered state -- on aux_stream if there is one, forked after the gather
+//   4. the agent's two taped evaluations and the log-probabilities
+//   5. (prior) the join, then the KL and its local derivatives
+//   6. the surrogate: upstream gradients and statistics
+//   7. the seeds of both evaluations (surrogate, + KL with a prior)
+//   8. one backward per evaluation into grad_theta
+// The seeds go straight to traj_seed_backward: mi_traj_logprob_backward's check of the tape state could not fire here, step 4 has just set it.
+static int pg_enqueue(mi_net* net, mi_batch* bc, mi_batch* bp, mi_net* prior, mi_batch* pb, const float* coef_dev, int T, const float* time_freqs,
+                      const float* traj_atom_types, const float* traj_frac, const float* traj_frac_mid, const float* traj_lattices,
+                      const float* traj_lp_old, const int* t_dev, const float* adv_dev, float clip_range, const float* w_host, float loss_scale,
+                      float kl_coef, float* log_prob, float* kl_out, float* grad_theta, float* stats, void* stream, void* aux_stream) {
+    if (bc->B == 0 || bc->N == 0) return MI_OK;
+    MI_TRY(pg_buffers(bc));
+    if (prior) MI_TRY(kl_buffers(bc, pb));
+    hipStream_t s = (hipStream_t)stream;
+    const bool aux = prior && aux_stream && aux_stream != stream;
+    MI_TRY(pg_gather(bc, T, t_dev, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, s));
+    if (prior) {
+        hipStream_t sp = aux ? (hipStream_t)aux_stream : s;
+        MI_TRY(mi_time_embedding(bc->pg_t, time_freqs, bc->B, prior->TD, pb->temb, stream));
+        if (aux) {
+            if (!pb->ev_fork) {
+                MI_HIP(hipEventCreateWithFlags(&pb->ev_fork, hipEventDisableTiming));
+                MI_HIP(hipEventCreateWithFlags(&pb->ev_join, hipEventDisableTiming));
+            }
+            MI_HIP(hipEventRecord(pb->ev_fork, s));
+            MI_HIP(hipStreamWaitEvent(sp, pb->ev_fork, 0));
+        }
+        // (the corrector evaluation's coordinate head alone is read: its lattice / type heads land in pred_l / pred_t, which the predictor overwrites)
+        MI_TRY(net_forward(prior, pb, pb->temb, bc->pg_a, bc->pg_x, bc->pg_l, pb->pred_l, pb->kl_pxc, pb->pred_t, sp, false, false, true));
+        MI_TRY(net_forward(prior, pb, pb->temb, bc->pg_a, bc->pg_xm, bc->pg_l, pb->pred_l, pb->pred_x, pb->pred_t, sp, false));
+        if (aux) MI_HIP(hipEventRecord(pb->ev_join, sp));
+    }
+    float* lp = log_prob ? log_prob : bc->pg_lp;
+    MI_TRY(traj_logprob_enqueue(net, bc, bp, bc->pg_t, coef_dev, time_freqs, bc->pg_a, bc->pg_x, bc->pg_xm, bc->pg_l, bc->pg_na, bc->pg_nx,
+                                bc->pg_nl, lp, nullptr, nullptr, nullptr, 1, stream));
+    if (aux) MI_HIP(hipStreamWaitEvent(s, pb->ev_join, 0));
+    if (prior) MI_TRY(kl_launch(bc, bp, pb, coef_dev, w_host, kl_out ? kl_out : bc->kl_val, stats, s));
+    MI_TRY(pg_surrogate(bc, lp, traj_lp_old, adv_dev, clip_range, w_host, loss_scale, stats, s));
+    const float kc = kl_coef * loss_scale;
+    const float kl_w[3] = {kc * w_host[0], kc * w_host[1], kc * w_host[2]};
+    return traj_seed_backward(net, bc, bp, bc->pg_g, nullptr, nullptr, nullptr, prior ? kl_w : nullptr, grad_theta, s);
 }
 
 }  // namespace mi
@@ -522,21 +570,7 @@ int mi_traj_logprob_backward(mi_net* net, mi_batch* bc, mi_batch* bp, const floa
     if (bc->B == 0 || bc->N == 0) return MI_OK;
     MI_CHECK(bc->tr_partner == bp && bc->tr_epoch == bc->fwd_epoch && bp->fwd_epoch == bc->tr_partner_epoch && bc->tape.valid && bp->tape.valid,
              MI_ESTATE, "mi_traj_logprob_backward: no taped mi_traj_logprob pending on these handles (not taped, or a later evaluation overwrote it)");
-    hipStream_t s = (hipStream_t)stream;
-    const int B = bc->B, N = bc->N;
-    SeedArgs a;
-    a.g = g_logp;
-    a.n2g = bc->node2graph;
-    a.dl = bp->tr_dl, a.dx_corr = bc->tr_dx, a.dx_pred = bp->tr_dx, a.dt = bp->tr_dt;
-    a.uc_l = d_corr_l, a.uc_x = d_corr_x, a.uc_t = d_corr_t;
-    a.sc_l = bc->tr_sl, a.sc_x = bc->tr_sx, a.sc_t = bc->tr_st;
-    a.sp_l = bp->tr_sl, a.sp_x = bp->tr_sx, a.sp_t = bp->tr_st;
-    a.B = B, a.N = N;
-    const int64_t n = (int64_t)B * 9 + (int64_t)N * (3 + MI_NUM_TYPES);
-    hipLaunchKernelGGL(traj_seed_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, a);
-    MI_KERNEL_CHECK();
-    MI_TRY(net_backward(net, bp, bp->tr_sl, bp->tr_sx, bp->tr_st, grad_theta, s));
-    return net_backward(net, bc, bc->tr_sl, bc->tr_sx, bc->tr_st, grad_theta, s);
+    return traj_seed_backward(net, bc, bp, g_logp, d_corr_l, d_corr_x, d_corr_t, nullptr, grad_theta, (hipStream_t)stream);
 }
 
 int mi_traj_pg_step(mi_net* net, mi_batch* bc, mi_batch* bp, const float* coef_dev, int T, const float* time_freqs,
@@ -545,16 +579,8 @@ int mi_traj_pg_step(mi_net* net, mi_batch* bc, mi_batch* bp, const float* coef_d
                     const float* w_host, float loss_scale, float* log_prob, float* grad_theta, float* stats, void* stream) {
     MI_TRY(pg_check(net, bc, bp, coef_dev, T, time_freqs, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, traj_lp_old, t_host, t_dev,
                     adv_dev, clip_range, w_host, grad_theta, stats));
-    if (bc->B == 0 || bc->N == 0) return MI_OK;
-    MI_TRY(pg_buffers(bc));
-    hipStream_t s = (hipStream_t)stream;
-    MI_TRY(pg_gather(bc, T, t_dev, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, s));
-
-    float* lp = log_prob ? log_prob : bc->pg_lp;
-    MI_TRY(traj_logprob_enqueue(net, bc, bp, bc->pg_t, coef_dev, time_freqs, bc->pg_a, bc->pg_x, bc->pg_xm, bc->pg_l, bc->pg_na, bc->pg_nx,
-                                bc->pg_nl, lp, nullptr, nullptr, nullptr, 1, stream));
-    MI_TRY(pg_surrogate(bc, lp, traj_lp_old, adv_dev, clip_range, w_host, loss_scale, stats, s));
-    return mi_traj_logprob_backward(net, bc, bp, bc->pg_g, nullptr, nullptr, nullptr, grad_theta, stream);
+    return pg_enqueue(net, bc, bp, nullptr, nullptr, coef_dev, T, time_freqs, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, traj_lp_old,
+                      t_dev, adv_dev, clip_range, w_host, loss_scale, 0.f, log_prob, nullptr, grad_theta, stats, stream, nullptr);
 }
 
 int mi_traj_pg_kl_step(mi_net* net, mi_batch* bc, mi_batch* bp, mi_net* prior, mi_batch* pb, const float* coef_dev, int T,
@@ -571,61 +597,8 @@ int mi_traj_pg_kl_step(mi_net* net, mi_batch* bc, mi_batch* bp, mi_net* prior, m
     MI_CHECK(prior->TD == net->TD, MI_EINVAL, "the prior's time embedding has %d dimensions, the agent's %d (one frequency table serves both)", prior->TD, net->TD);
     MI_CHECK(kl_coef >= 0.f, MI_EINVAL, "kl_coef = %g: must be >= 0", (double)kl_coef);
     MI_CHECK(prior->theta != nullptr, MI_ESTATE, "mi_net_set_params must run on the prior before it is evaluated");
-    const int B = bc->B, N = bc->N;
-    if (B == 0 || N == 0) return MI_OK;
-    MI_TRY(pg_buffers(bc));
-    MI_TRY(kl_buffers(bc, pb));
-    hipStream_t s = (hipStream_t)stream;
-    // 1. the gather; 2. the prior's two inference evaluations on the gathered state (its own time embedding, from the gathered times)
-    MI_TRY(pg_gather(bc, T, t_dev, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, s));
-    MI_TRY(mi_time_embedding(bc->pg_t, time_freqs, B, prior->TD, pb->temb, stream));
-    const bool aux = aux_stream && aux_stream != stream;
-    hipStream_t sp = aux ? (hipStream_t)aux_stream : s;
-    if (aux) {
-        if (!pb->ev_fork) {
-            MI_HIP(hipEventCreateWithFlags(&pb->ev_fork, hipEventDisableTiming));
-            MI_HIP(hipEventCreateWithFlags(&pb->ev_join, hipEventDisableTiming));
-        }
-        MI_HIP(hipEventRecord(pb->ev_fork, s));
-        MI_HIP(hipStreamWaitEvent(sp, pb->ev_fork, 0));
-    }
-    // (the corrector evaluation's coordinate head alone is read: its lattice / type heads land in pred_l / pred_t, which the predictor overwrites)
-    MI_TRY(net_forward(prior, pb, pb->temb, bc->pg_a, bc->pg_x, bc->pg_l, pb->pred_l, pb->kl_pxc, pb->pred_t, sp, false, false, true));
-    MI_TRY(net_forward(prior, pb, pb->temb, bc->pg_a, bc->pg_xm, bc->pg_l, pb->pred_l, pb->pred_x, pb->pred_t, sp, false));
-    if (aux) MI_HIP(hipEventRecord(pb->ev_join, sp));
-    // 3. the agent's two taped evaluations and the log-probabilities
-    float* lp = log_prob ? log_prob : bc->pg_lp;
-    MI_TRY(traj_logprob_enqueue(net, bc, bp, bc->pg_t, coef_dev, time_freqs, bc->pg_a, bc->pg_x, bc->pg_xm, bc->pg_l, bc->pg_na, bc->pg_nx,
-                                bc->pg_nl, lp, nullptr, nullptr, nullptr, 1, stream));
-    if (aux) MI_HIP(hipStreamWaitEvent(s, pb->ev_join, 0));
-    // 4. the KL and its local derivatives
-    KlArgs k;
-    k.t = bc->pg_t, k.coef = coef_dev, k.node_off = bc->node_off;
-    k.pxc_a = bc->pred_x, k.pl_a = bp->pred_l, k.pxp_a = bp->pred_x, k.pt_a = bp->pred_t;
-    k.pxc_p = pb->kl_pxc, k.pl_p = pb->pred_l, k.pxp_p = pb->pred_x, k.pt_p = pb->pred_t;
-    k.dl = bc->kl_dl, k.dt = bc->kl_dt, k.dxc = bc->kl_dxc, k.dxp = bc->kl_dxp;
-    k.kl = kl_out ? kl_out : bc->kl_val;
-    k.stats = stats + 4 * (size_t)B;
-    k.w0 = w_host[0], k.w1 = w_host[1], k.w2 = w_host[2];
-    k.B = B;
-    hipLaunchKernelGGL(traj_pg_kl_kernel, dim3(B), dim3(256), 0, s, k);
-    MI_KERNEL_CHECK();
-    // 5. the surrogate; 6. the seeds of both evaluations (surrogate + KL); 7. one backward per evaluation
-    MI_TRY(pg_surrogate(bc, lp, traj_lp_old, adv_dev, clip_range, w_host, loss_scale, stats, s));
-    KlSeedArgs g;
-    g.g = bc->pg_g, g.n2g = bc->node2graph;
-    g.dl = bp->tr_dl, g.dx_corr = bc->tr_dx, g.dx_pred = bp->tr_dx, g.dt = bp->tr_dt;
-    g.kdl = bc->kl_dl, g.kdxc = bc->kl_dxc, g.kdxp = bc->kl_dxp, g.kdt = bc->kl_dt;
-    const float kc = kl_coef * loss_scale;
-    g.kl0 = kc * w_host[0], g.kl1 = kc * w_host[1], g.kl2 = kc * w_host[2];
-    g.sc_l = bc->tr_sl, g.sc_x = bc->tr_sx, g.sc_t = bc->tr_st;
-    g.sp_l = bp->tr_sl, g.sp_x = bp->tr_sx, g.sp_t = bp->tr_st;
-    g.B = B, g.N = N;
-    const int64_t n = (int64_t)B * 9 + (int64_t)N * (3 + MI_NUM_TYPES);
-    hipLaunchKernelGGL(traj_pg_kl_seed_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, g);
-    MI_KERNEL_CHECK();
-    MI_TRY(net_backward(net, bp, bp->tr_sl, bp->tr_sx, bp->tr_st, grad_theta, s));
-    return net_backward(net, bc, bc->tr_sl, bc->tr_sx, bc->tr_st, grad_theta, s);
+    return pg_enqueue(net, bc, bp, prior, pb, coef_dev, T, time_freqs, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, traj_lp_old,
+                      t_dev, adv_dev, clip_range, w_host, loss_scale, kl_coef, log_prob, kl_out, grad_theta, stats, stream, aux_stream);
 }
 
 }  // extern "C"

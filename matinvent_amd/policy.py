@@ -114,6 +114,12 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
     if theta.grad is None:
         theta.grad = torch.zeros_like(theta)
     stats = torch.zeros(5 if use_kl else 4, B, device=dev)
+    handles = (b_corr, b_pred)
+    if use_kl:                                                                     # the micro-step of this call, chosen once
+        micro_step = lambda th, td: pg_kl_micro_step(agent, handles, prior, b_prior, rollout, th, td, adv, clip_range, w_host, kl_coef, 1.0 / M,
+                                                     theta.grad, stats, aux_stream=aux)
+    else:
+        micro_step = lambda th, td: pg_micro_step(agent, handles, rollout, th, td, adv, clip_range, w_host, 1.0 / M, theta.grad, stats)
     out = []
     for epoch in range(epochs):
         agent.train()
@@ -122,11 +128,7 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
         t_host = draws[epoch]
         t_dev = torch.from_numpy(t_host).to(dev)                                   # one upload per epoch: [K, B]
         for k in range(K):
-            if use_kl:
-                pg_kl_micro_step(agent, (b_corr, b_pred), prior, b_prior, rollout, t_host[k], t_dev[k], adv, clip_range, w_host, kl_coef,
-                                 1.0 / M, theta.grad, stats, aux_stream=aux)
-            else:
-                pg_micro_step(agent, (b_corr, b_pred), rollout, t_host[k], t_dev[k], adv, clip_range, w_host, 1.0 / M, theta.grad, stats)
+            micro_step(t_host[k], t_dev[k])
             if (k + 1) % accum_steps == 0:
                 optimizer.step()
                 optimizer.zero_grad(set_to_none=False)
@@ -139,8 +141,21 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
             d["prior_kl"] = s[4]
         out.append(d)
         log(f"PG epoch {epoch}: " + ", ".join(f"{k}: {v:.4g}" for k, v in d.items()))
-    del b_corr, b_pred, b_prior
+    del b_corr, b_pred, b_prior, handles, micro_step
     return out
+
+
+def _micro_step_args(agent, rollout, t_host, t_dev, w_host):
+    """What both micro-steps check and marshal: the rollout's five arrays (device, float32, contiguous), t_host / w_host as contiguous
+    int32 [B] / float32 [3] with their shapes checked; ends with the agent's decoder.sync().  Returns (traj, t_host, w_host)."""
+    traj = [rollout.atom_types, rollout.frac_coords, rollout.frac_coords_mid, rollout.lattices, rollout.lp_old]
+    for v in traj:
+        assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()
+    t_host = np.ascontiguousarray(t_host, dtype=np.int32)
+    w_host = np.ascontiguousarray(w_host, dtype=np.float32)
+    assert t_host.shape == (rollout.num_graphs,) and w_host.shape == (3,) and t_dev.dtype == torch.int32
+    agent.decoder.sync()
+    return traj, t_host, w_host
 
 
 def pg_micro_step(agent, handles, rollout, t_host, t_dev, adv, clip_range, w_host, loss_scale, grad, stats, log_prob=None):
@@ -148,18 +163,11 @@ def pg_micro_step(agent, handles, rollout, t_host, t_dev, adv, clip_range, w_hos
     adv [B] (device), weights w_host (float32 host [3]); grad += the surrogate's gradient scaled by loss_scale, stats [4, B] += (L_b, rho,
     approx-KL term, clipped indicator); log_prob [3, B] (optional) receives the new log-probabilities.  `handles`: two batch handles of
     agent.decoder over rollout.num_atoms.  Enqueued on the current stream without a host synchronisation."""
-    dec = agent.decoder
-    traj = [rollout.atom_types, rollout.frac_coords, rollout.frac_coords_mid, rollout.lattices, rollout.lp_old]
-    for v in traj:
-        assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()
-    t_host = np.ascontiguousarray(t_host, dtype=np.int32)
-    w_host = np.ascontiguousarray(w_host, dtype=np.float32)
-    assert t_host.shape == (rollout.num_graphs,) and w_host.shape == (3,) and t_dev.dtype == torch.int32
-    dec.sync()
-    _lib.check(_lib.load().mi_traj_pg_step(dec._h, handles[0]._h, handles[1]._h, _ptr(agent._coefficients_dev(rollout.step_lr)), rollout.T,
-                                           _ptr(agent.time_embedding.freqs), *(_ptr(v) for v in traj), t_host.ctypes.data, _ptr(t_dev),
-                                           _ptr(adv), float(clip_range), w_host.ctypes.data, float(loss_scale), _ptr(log_prob), _ptr(grad),
-                                           _ptr(stats), _stream()), "mi_traj_pg_step")
+    traj, t_host, w_host = _micro_step_args(agent, rollout, t_host, t_dev, w_host)
+    _lib.check(_lib.load().mi_traj_pg_step(agent.decoder._h, handles[0]._h, handles[1]._h, _ptr(agent._coefficients_dev(rollout.step_lr)),
+                                           rollout.T, _ptr(agent.time_embedding.freqs), *(_ptr(v) for v in traj), t_host.ctypes.data,
+                                           _ptr(t_dev), _ptr(adv), float(clip_range), w_host.ctypes.data, float(loss_scale), _ptr(log_prob),
+                                           _ptr(grad), _ptr(stats), _stream()), "mi_traj_pg_step")
 
 
 def pg_kl_micro_step(agent, handles, prior, prior_handle, rollout, t_host, t_dev, adv, clip_range, w_host, kl_coef, loss_scale, grad, stats,
@@ -169,18 +177,11 @@ def pg_kl_micro_step(agent, handles, prior, prior_handle, rollout, t_host, t_dev
     [5, B]: rows 0..3 as pg_micro_step's, row 4 += KL_b (weighted by w, not by beta); kl_out [3, B] (optional) receives (KL_l, KL_t, KL_x).
     aux_stream (a torch stream, optional): the prior's evaluations run on it.  Enqueued on the current stream without a host
     synchronisation."""
-    dec = agent.decoder
-    traj = [rollout.atom_types, rollout.frac_coords, rollout.frac_coords_mid, rollout.lattices, rollout.lp_old]
-    for v in traj:
-        assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()
-    t_host = np.ascontiguousarray(t_host, dtype=np.int32)
-    w_host = np.ascontiguousarray(w_host, dtype=np.float32)
-    assert t_host.shape == (rollout.num_graphs,) and w_host.shape == (3,) and t_dev.dtype == torch.int32
     assert stats.shape == (5, rollout.num_graphs)
-    dec.sync()
+    traj, t_host, w_host = _micro_step_args(agent, rollout, t_host, t_dev, w_host)
     prior.decoder.sync()
     aux = C.c_void_p(aux_stream.cuda_stream) if aux_stream is not None else None
-    _lib.check(_lib.load().mi_traj_pg_kl_step(dec._h, handles[0]._h, handles[1]._h, prior.decoder._h, prior_handle._h,
+    _lib.check(_lib.load().mi_traj_pg_kl_step(agent.decoder._h, handles[0]._h, handles[1]._h, prior.decoder._h, prior_handle._h,
                                               _ptr(agent._coefficients_dev(rollout.step_lr)), rollout.T, _ptr(agent.time_embedding.freqs),
                                               *(_ptr(v) for v in traj), t_host.ctypes.data, _ptr(t_dev), _ptr(adv), float(clip_range),
                                               w_host.ctypes.data, float(loss_scale), float(kl_coef), _ptr(log_prob), _ptr(kl_out), _ptr(grad),

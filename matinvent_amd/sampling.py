@@ -68,27 +68,8 @@ class DiffCSPSampler:
             self.seed += 1
             counts = _AtomCounts(na[lo:hi])
             outputs, _ = model.sample(counts, step_lr=step_lr, seed=self.seed, node_offset=node_off, graph_offset=lo)
-        from . import _lib
-        if hasattr(model, "check_graph"):
-            model.check_graph()   # (knn edge style: the chains' neighbour lists stayed inside their capacity -- the device is about to be drained anyway)
-        _lib.check_saturation("DiffCSPSampler.generate")  # (the results are about to be copied to the host: the device is drained anyway)
-        # geometric validity quantities of the final state, computed where it lives (K18); the filter step thresholds them
-        from .structure import check_structures
-        geom = check_structures(model.crystal_batch(counts, node_off, lo), outputs["frac_coords"], outputs["lattices"]).cpu()
-        frac_coords = outputs["frac_coords"].detach().cpu()
-        num_atoms = outputs["num_atoms"].detach().cpu()
-        atom_types = outputs["atom_types"].detach().cpu()
-        lattices = outputs["lattices"].detach().cpu()
-        lengths, angles = lattices_to_params_shape(lattices)
-        atom_types = torch.argmax(atom_types, dim=-1) + 1  # sample.py:182
-        offset = [0] + torch.cumsum(num_atoms, dim=0).tolist()
-        data_list, struc_list = [], []
-        for i in range(len(num_atoms)):
-            d = CrystalData(frac_coords=frac_coords[offset[i]:offset[i + 1]], atom_types=atom_types[offset[i]:offset[i + 1]],
-                            lengths=lengths[i].view(1, -1), angles=angles[i].view(1, -1), num_atoms=int(num_atoms[i]))
-            d.geometry = {"max_cell_edge": float(geom[i, 0]), "min_distance": float(geom[i, 1]), "volume": float(geom[i, 2])}
-            data_list.append(d)
-            struc_list.append(data2struc(d))
+        data_list = _unpack(model, counts, outputs, node_off, lo, where="DiffCSPSampler.generate")
+        struc_list = [data2struc(d) for d in data_list]
         if world > 1 or collectives_on():
             from .dist import all_gather_objects
             parts = all_gather_objects((data_list, struc_list))
@@ -97,18 +78,19 @@ class DiffCSPSampler:
         return data_list, struc_list
 
 
-def _unpack(model, counts, outputs):
-    """The final state of a `model.sample` call as CrystalData records (sample.py:221-244), each carrying the device-side geometry that
-    invalid_filter thresholds (K18: the same quantities DiffCSPSampler.generate attaches)."""
+def _unpack(model, counts, outputs, node_offset=0, graph_offset=0, where="sample_loop / sample_mdp"):
+    """The final state of a `model.sample` call as CrystalData records (sample.py:178-195, :221-244), each carrying the device-side geometry
+    that invalid_filter thresholds (K18), computed where the state lives.  node_offset / graph_offset: the shard's position in its batch
+    (DiffCSPSampler.generate under DP); `where` labels a saturation error."""
     from . import _lib
     from .structure import check_structures
     if hasattr(model, "check_graph"):
-        model.check_graph()
-    _lib.check_saturation("sample_loop / sample_mdp")
-    geom = check_structures(model.crystal_batch(counts), outputs["frac_coords"], outputs["lattices"]).cpu()
+        model.check_graph()   # (knn edge style: the chains' neighbour lists stayed inside their capacity -- the device is about to be drained anyway)
+    _lib.check_saturation(where)  # (the results are about to be copied to the host: the device is drained anyway)
+    geom = check_structures(model.crystal_batch(counts, node_offset, graph_offset), outputs["frac_coords"], outputs["lattices"]).cpu()
     frac_coords = outputs["frac_coords"].detach().cpu()
     num_atoms = outputs["num_atoms"].detach().cpu()
-    atom_types = torch.argmax(outputs["atom_types"].detach().cpu(), dim=-1) + 1
+    atom_types = torch.argmax(outputs["atom_types"].detach().cpu(), dim=-1) + 1  # sample.py:182
     lengths, angles = lattices_to_params_shape(outputs["lattices"].detach().cpu())
     offset = [0] + torch.cumsum(num_atoms, dim=0).tolist()
     data_list = []
@@ -125,12 +107,17 @@ def _draw_seed(seed):
     return int(torch.randint(0, 2 ** 62, (1,))) if seed is None else int(seed)
 
 
-def sample_loop(sample_size, model, device=None, step_lr=-1, seed=None):
-    """sample.py:204-246: one batch of `sample_size` crystals (atom counts from the MP-20 prior) -> list of CrystalData."""
+def _prelude(sample_size, model, step_lr):
+    """What sample_loop / sample_mdp / sample_rollout do before model.sample: eval mode, the atom-count draw (numpy's global generator) and
+    the step_lr default.  Returns (counts, step_lr); the callers draw their seed (_draw_seed) after it, as before."""
     model.eval()
     dataset = SampleDataset(total_num=sample_size)
-    step_lr = step_lr if step_lr >= 0 else DEFAULT_STEP_LR["gen"]["mp_20"]
-    counts = _AtomCounts(dataset.num_atoms)
+    return _AtomCounts(dataset.num_atoms), (step_lr if step_lr >= 0 else DEFAULT_STEP_LR["gen"]["mp_20"])
+
+
+def sample_loop(sample_size, model, device=None, step_lr=-1, seed=None):
+    """sample.py:204-246: one batch of `sample_size` crystals (atom counts from the MP-20 prior) -> list of CrystalData."""
+    counts, step_lr = _prelude(sample_size, model, step_lr)
     outputs, _ = model.sample(counts, step_lr=step_lr, seed=_draw_seed(seed))
     return _unpack(model, counts, outputs)
 
@@ -142,10 +129,7 @@ def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None):
     the state at t - 1 -- so that any element can go straight to DiffCSPModule.forward_logprb.  (The reference's own sample_mdp unpacks
     invalid_filter into the wrong values and never builds the next_* keys that forward_logprb reads.)"""
     from .filters import invalid_filter
-    model.eval()
-    dataset = SampleDataset(total_num=sample_size)
-    step_lr = step_lr if step_lr >= 0 else DEFAULT_STEP_LR["gen"]["mp_20"]
-    counts = _AtomCounts(dataset.num_atoms)
+    counts, step_lr = _prelude(sample_size, model, step_lr)
     outputs, traj = model.sample(counts, step_lr=step_lr, seed=_draw_seed(seed), record=True)
     data_list = _unpack(model, counts, outputs)
     valid = invalid_filter(data_list, return_mask=True)
@@ -219,10 +203,7 @@ def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=T
     if getattr(model, "keep_lattice", False) or getattr(model, "keep_coords", False):
         raise ValueError("sample_rollout: CSP mode (keep_lattice / keep_coords) is not supported -- forward_logprb does not model a given "
                          "lattice or given coordinates")
-    model.eval()
-    dataset = SampleDataset(total_num=sample_size)
-    step_lr = step_lr if step_lr >= 0 else DEFAULT_STEP_LR["gen"]["mp_20"]
-    counts = _AtomCounts(dataset.num_atoms)
+    counts, step_lr = _prelude(sample_size, model, step_lr)
     sink = []
     outputs, _ = model.sample(counts, step_lr=step_lr, seed=_draw_seed(seed), record=True, rec_sink=sink)
     data_list = _unpack(model, counts, outputs)

@@ -2,18 +2,10 @@
 include/matinvent_hip.h (the boundary) and include/matinvent_hip_debug.h (experiment knobs) declare -- no compute calls without a GPU."""
 import ctypes
 import os
-import re
 
 from matinvent_amd import _lib
 from matinvent_amd.build import build
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_symbols(header="matinvent_hip.h"):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(mi_[a-z0-9_]+)\s*\(", src)))
+from tests.header_util import INCLUDE, ROOT, declared_symbols
 
 
 def test_library_builds_and_exports_every_declared_symbol():
@@ -30,6 +22,31 @@ def test_library_builds_and_exports_every_declared_symbol():
         assert hasattr(lib, n), f"{n} declared in include/ but not exported"
     # the ctypes table binds exactly the declared set (both headers)
     assert sorted(_lib.SIGNATURES) == sorted(names + debug)
+
+
+def test_every_public_header_is_bound_by_exactly_one_table_and_loaded():
+    """Every symbol of every include/*.h is a key of exactly one _lib table, and load() attached that table's restype / argtypes: a table
+    that is defined but left out of load()'s loop would leave its entries with ctypes' defaults."""
+    tables = (_lib.SIGNATURES,) + _lib.EXTENSION_SIGNATURES
+    assert any(t is _lib.TRAJ_SIGNATURES for t in tables) and any(t is _lib.PG_SIGNATURES for t in tables)
+    assert any(t is _lib.PG_KL_SIGNATURES for t in tables)
+    headers = sorted(f for f in os.listdir(INCLUDE) if f.endswith(".h"))
+    assert len(headers) >= 5
+    build(verbose=False)
+    lib = _lib.load()
+    declared = []
+    for h in headers:
+        names = declared_symbols(h)
+        assert names, h
+        declared += names
+        for n in names:
+            owners = [t for t in tables if n in t]
+            assert len(owners) == 1, f"{n} ({h}) is bound by {len(owners)} tables"
+            res, args = owners[0][n]
+            fn = getattr(lib, n)
+            assert fn.restype == res and fn.argtypes == args, f"{n} ({h}): load() did not attach its signature"
+    assert len(declared) == len(set(declared))                            # no symbol declared by two headers
+    assert sorted(declared) == sorted(n for t in tables for n in t)       # and no table entry without a declaration
 
 
 def test_host_only_entry_points():

@@ -3,7 +3,6 @@ host refusals, the drop-in config, and the closed-form transition KL (tests/kl_u
 Normal KL, the wrapped-normal KL and autograd in float64."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,14 +11,10 @@ import torch
 from matinvent_amd import config as C
 from matinvent_amd import policy
 from tests import kl_util
+from tests.header_util import declared_symbols as _declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXAMPLE = os.path.join(ROOT, "dropin", "configs")
-
-
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(mi_[a-z0-9_]+)\s*\(", src)))
 
 
 def test_kl_header_is_exported_and_bound_in_its_own_table():

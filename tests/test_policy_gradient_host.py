@@ -142,11 +142,10 @@ def test_pipeline_refusals(case, monkeypatch, tmp_path):
 
 def test_pg_header_is_exported_and_bound_in_its_own_table():
     import ctypes
-    import re
     from matinvent_amd import _lib
     from matinvent_amd.build import build
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "matinvent_hip_pg.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(mi_[a-z0-9_]+)\s*\(", src)))
+    from tests.header_util import declared_symbols
+    names = declared_symbols("matinvent_hip_pg.h")
     assert names == ["mi_traj_pg_step"]
     lib = ctypes.CDLL(build(verbose=False))
     assert hasattr(lib, "mi_traj_pg_step")

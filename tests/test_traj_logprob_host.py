@@ -9,7 +9,7 @@ import sys
 import numpy as np
 import torch
 
-from tests.test_abi import ROOT, declared_symbols
+from tests.header_util import ROOT, declared_symbols
 from tests.traj_util import STATE_KEYS, forward_logprb, hparams_of
 
 
