@@ -75,8 +75,7 @@ int mi_debug_set_planes_rt(int mode, int min_rows);
  * sampling and fine-tune batches, models/diffcsp/sample.py:42-62 -- and node-level products) are one round of workgroups whose k-loop
  * is a chain of memory latencies.  Same accumulation order per output: bit-identical results (tests/test_gpu_gemm.py). */
 int mi_debug_set_planes_latency(int max_blocks);
-/* The second edge GEMM of an inference forward (SiLU + fused segmented sum epilogue, cspnet.py:79) with at least `min_rows` edges on
- * the 256 x 256 LDS-DMA kernel as well; 0 (default) = never.  Bit-identical partial sums (same accumulation order). */
+/* Retired (the segmented-sum epilogue on the 256 x 256 LDS-DMA kernel): min_rows <= 0 is accepted and selects nothing, min_rows > 0 returns MI_EINVAL. */
 int mi_debug_set_planes_big_seg(int min_rows);
 /* Experiment: 1 = the node-level kernels of an inference forward (LayerNorm, the node-level products, the aggregation's last pass) run on
  * a helper stream of the highest priority owned by the batch handle, joined to the caller's stream by events at every hand-over;
@@ -85,11 +84,12 @@ int mi_debug_set_planes_big_seg(int min_rows);
 int mi_debug_set_node_priority(int on);
 /* The 128 x 128-tile plane product with its operands staged by LDS-DMA (`buffer_load ... lds` into two 32 KiB stages, fragments
  * software-pipelined over two register sets, one barrier per k-tile): 0 = never, 1 (default) = launches of at most the latency
- * limit above, 2 = every launch of the 128-row kernel.  Bit-identical to the register-staged loop (tests/test_gpu_gemm.py). */
+ * limit above, 2 = every launch of the 128-row kernel, 3 = the launches of more than 256 workgroups only.  Bit-identical to the register-staged
+ * loop (tests/test_gpu_gemm.py).  Returns MI_OK, or MI_EINVAL for a mode above 3 (the setting in force stays). */
 int mi_debug_set_planes_dma(int mode);
 /* The node-level chain between two edge stages of an inference forward (segmented mean, node MLP with residual, LayerNorm, the
  * projections LayerNorm(h) feeds: models/diffcsp/cspnet.py:79-91,61) as ONE launch per layer boundary (csrc/node_chain.hip):
- * 1 (default) = on for hidden_dim 128 / 256 / 512 with LayerNorm, 0 = the seven-launch form.  Returns the previous setting. */
+ * any non-zero value (default 1) = on for hidden_dim 128 / 256 / 512 with LayerNorm, 0 = the seven-launch form.  Returns the previous setting. */
 int mi_debug_set_node_fused(int on);
 /* The same launch in the TRAINING forward, which then also writes what the backward pass reads of it (the aggregated messages and
  * LayerNorm(h) into the tape's cat rows, the two node-MLP pre-activations, the LayerNorm statistics): 1 (default) = on wherever the
@@ -136,26 +136,17 @@ int mi_debug_set_eval_reuse(int mask);
  * chain's serial path costs; results unaffected).  Returns the previous mask. */
 int mi_debug_set_skip(int mask);
 /* The second linear of the edge MLP with the edge -> node reduction (models/diffcsp/cspnet.py:73-79) of an inference forward at
- * hidden_dim 512 on 128-row x 512-column register tiles with the segmented sum as an MFMA product (csrc/edge_stage.hip):
+ * hidden_dim 512 on 128-row x 256-column register tiles with the segmented sum as an MFMA product (csrc/edge_stage.hip):
  * 1 (default) = on (inference forwards, next to the node-chain launch above; training forwards too, with the pre-activation kept
- * for the backward pass), 4 = inference forwards only, 0 = the 128 x 128-tile plane GEMM.  Returns the previous setting. */
+ * for the backward pass), 4 = inference forwards only, 0 = the 128 x 128-tile plane GEMM; 2 and 3 behave as 4.  Returns
+ * the previous setting. */
 int mi_debug_set_edge2_fused(int on);
-/* Both edge products of a layer and the edge -> node sums in ONE launch (csrc/edge_fused.hip: a workgroup owns 64 atom pairs, M1 stays
- * in LDS; inference forwards, fc pair mode, hidden_dim 512, next to the node-chain launch): 1 = on, 0 (default) = the pair GEMM + the
- * second edge GEMM.  M1 is bit-identical; the partial sums are formed over other row groups.  A recorded experiment (parity green, 27 %
- * slower end to end: DESIGN 16.4) that exists in -DMI_ABLATION_KERNELS builds only; the default library ignores 1.  Returns the previous
- * setting. */
+/* Retired (both edge products of a layer in one launch: DESIGN 16.4, 26): accepts any value, selects nothing, returns 0 -- the setting was and stays off. */
 int mi_debug_set_edge_fused(int on);
-/* Phase clock of that launch: dev_buffer = [workgroups][16] uint64 s_memtime stamps (0 entry, 1 + 3c / 2 + 3c / 3 + 3c: first product /
- * pair epilogue / second product of column chunk c, 13 exit), NULL = off. */
-int mi_debug_edge_fused_clock(void* dev_buffer);
-/* The pair-mode first edge GEMM (Fourier block over unordered atom pairs, models/diffcsp/cspnet.py:59-74) on the same form -- 128 x 128
+/* The pair-mode first edge GEMM (Fourier block over unordered atom pairs, models/diffcsp/cspnet.py:59-74) as a register-tile kernel too -- 128 x 128
  * tiles per four-wave workgroup, the Fourier operand by LDS-DMA, the weights in fragment order straight from L2: 9 (default) = that form
  * for hidden_dim multiples of 128 and launches beyond the plane GEMM's small-launch forms (with its k-loop under manual control it is
- * 3-6 % ahead end to end: DESIGN 18.4e), 1 = that form whatever the size, 0 = the plane GEMM always; 2 = 128 x 256 tiles, one
- * workgroup per CU with 512 registers per lane (half the LDS reads per MFMA; measured 11-13 % slower end to end; exists only in a
- * -DMI_ABLATION_KERNELS build, otherwise 2 runs form 1); 3 = the 128 x 128 tile as 2 x 2 waves of 64 pairs x 64 columns (half the LDS reads,
- * twice the weight fetches; 12 % slower; ablation build only).  Same epilogue: bit-identical M1.  Returns the previous setting. */
+ * 3-6 % ahead end to end: DESIGN 18.4e), 1 .. 4 = that form whatever the size, 0 = the plane GEMM always.  Same epilogue: bit-identical M1.  Returns the previous setting. */
 int mi_debug_set_edge1_fused(int on);
 /* Phase clock of ONE launch of the register-tile GEMM (csrc/edge_stage.hip gemm_rt_kernel: the dense layers of the MatterGen-shaped network,
  * the dM1 data gradient of `loss.backward()`, pipeline/mat_invent.py:164): dev_buffer = [workgroups][8] uint64 -- s_memtime at entry / first
@@ -166,11 +157,10 @@ int mi_debug_rt_clock(void* dev_buffer, int ext, int skip);
 /* The lean epilogue of that kernel for the launches that only write a plane set (the dense layers of an inference forward of the
  * MatterGen-shaped network, models/mattergen/pl_module.py:73: activation, plane-set residuals, multiplicand, exact max |y|): transposed
  * accumulator tiles + v_permlane32_swap instead of the LDS patch, every scale folded into two constants.  1 (default) = on, 0 = the general
- * row epilogue for every launch.  Returns the previous setting. */
+ * row epilogue for every launch; 2 behaves as 1 and the bits above bit 1 are ignored.  Returns the previous setting. */
 int mi_debug_set_rt_lean(int on);
 /* Phase clock of that kernel (measurement only): device buffer of [row tiles][8] 64-bit s_memtime stamps (start, first operand chunk
- * landed, main loop done, epilogue done); nullptr = off.  `on` = 2 above selects the variant with a two-deep weight ring and
- * double-buffered activation fragments (ablation). */
+ * landed, main loop done, epilogue done); nullptr = off. */
 int mi_debug_edge2_clock(void* dev_buffer);
 int mi_debug_edge1_clock(void* dev_buffer);   /* the same for the first edge GEMM: [row tiles x column quarters][8] stamps */
 /* Phase clock of that launch (measurement only): a device buffer of [workgroups][16] 64-bit words that every workgroup fills with

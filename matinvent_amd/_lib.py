@@ -95,7 +95,6 @@ SIGNATURES = {
     "mi_debug_rt_clock": (_I, [_P, _I, _I]),
     "mi_debug_set_rt_lean": (_I, [_I]),
     "mi_debug_set_edge_fused": (_I, [_I]),
-    "mi_debug_edge_fused_clock": (_I, [_P]),
     "mi_debug_edge2_clock": (_I, [_P]),
     "mi_debug_set_edge1_fused": (_I, [_I]),
     "mi_debug_edge1_clock": (_I, [_P]),

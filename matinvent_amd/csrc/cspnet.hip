@@ -26,7 +26,6 @@ int g_node_train = 1;             // the training forward's node-level work on t
 int g_edge2_train = 1;            // the training forward's second edge GEMM on the register-tile kernel too, its pre-activation written row-major through LDS patches
 int g_planes_rt = 2;              // register-tile kernel for every qualifying product (gemm_split.h / edge_stage.hip); 1 = only those with epilogue extensions
 int g_planes_rt_min_rows = 16384;
-int g_planes_big_seg_min_rows = 0;
 int g_planes_dma = 1;
 int g_heads_rows16_min_nodes = 1 << 30;   // atoms from which the fused heads run on 16 rows per workgroup instead of 4 (a quarter of the weight streams; mi_debug_set_heads_rows16).
                                           // OFF: measured neutral on the headline (53.9 / 54.0 / 54.4 against 53.7 / 53.8 / 54.2) and -2 % on the reference's default batch, profiles/r5_heads_rows16_ab.log
@@ -1204,13 +1203,6 @@ int net_forward(mi_net* net, mi_batch* b, const float* t_emb, const float* atom_
                         pe1.diag_e = b->e_diag;
                         pe1.diag_nodes = N;
                     }
-                    const bool efused = !train && fused && fold && MI_PLANES_FP16 && edge_fused_supported(net, b);
-                    if (efused) {   // both edge products and the edge -> node sums in one launch, M1 stays in LDS (edge_fused.hip)
-                        MI_TRY(edge_fused(net, b, l, s));
-                        b->seg_shift = -1;
-                        MI_TRY(prof_end(net, s, ps));
-                        continue;   // (fused: the rest of the layer runs in node_chain(l + 1))
-                    }
                     if (b->Np > 0 && fold && edge_gemm1_supported(net, b->Np))   // 128 x 128 tiles, weights straight from L2 in fragment order (edge_stage.hip)
                         MI_TRY(edge_gemm1(net, make_planes(b->FFpl, Kp, PL_S_UNIT), l, (int)b->Np, pe1, s));
                     else if (b->Np > 0)
@@ -1440,7 +1432,6 @@ void mi_net_destroy(mi_net* n) {
     if (n->Wn2pl) (void)hipFree(n->Wn2pl);
     if (n->Wnc) (void)hipFree(n->Wnc);
     if (n->Wffc) (void)hipFree(n->Wffc);
-    if (n->Wffc2) (void)hipFree(n->Wffc2);
     if (n->wbounds) (void)hipFree(n->wbounds);
     for (auto e : n->ev) (void)hipEventDestroy(e);
     delete n;
@@ -1480,7 +1471,6 @@ int mi_net_set_params(mi_net* n, const float* theta, const float* freqs_host, vo
         MI_HIP(hipMalloc((void**)&n->wbounds, (size_t)n->L * 8 * sizeof(float)));
         if (node_chain_pack_elems(H) && cfg_ln_and_wide(n)) MI_HIP(hipMalloc((void**)&n->Wnc, (size_t)n->L * node_chain_pack_elems(H) * sizeof(u16)));
         if (MI_PLANES_FP16 && H % 128 == 0) MI_HIP(hipMalloc((void**)&n->Wffc, (size_t)n->L * H * 2 * ((3 * n->F + 31) / 32 * 32) * 2 * sizeof(u16)));
-        if (MI_PLANES_FP16 && MI_HAVE_ABLATION_KERNELS && H % 256 == 0) MI_HIP(hipMalloc((void**)&n->Wffc2, (size_t)n->L * H * ((3 * n->F + 31) / 32 * 32) * 2 * sizeof(u16)));   // -2 x the sine block (edge_gemm1e_kernel)
         n->Kh = (3 * n->F + 31) / 32 * 32;
         MI_HIP(hipMalloc((void**)&n->Wffpl_pair, (size_t)n->L * planes_elems(H, 2 * n->Kh) * sizeof(u16)));
         MI_HIP(hipMalloc((void**)&n->C0, (size_t)n->L * H * sizeof(float)));
@@ -1616,39 +1606,6 @@ static int batch_create_impl(const mi_net* net, const int* num_atoms_host, int B
     b->Np = (int64_t)pr_i.size();
     pr_off[B] = (int)pr_i.size();
     rowptr[N] = (int)e;
-    // edge_fused.hip's tables: 64-pair tiles, slots of a node's partial sums (see mi_batch)
-    std::vector<int> ef_tile0(std::max(N, 1), 1 << 30);   // (nodes of crystals without pairs: no pair tile)
-    std::vector<unsigned> ef_mask(std::max(N, 1), 0u);
-    if (!knn && b->Np > 0) {
-        int span = 0;
-        for (int g = 0; g < B; ++g) {
-            const int n = num_atoms_host[g], o = b->node_off_h[g];
-            if (pr_off[g + 1] > pr_off[g]) {
-                const int t0 = pr_off[g] >> 6, t1 = (pr_off[g + 1] - 1) >> 6;
-                span = std::max(span, t1 - t0 + 1);
-                for (int i = 0; i < n; ++i) ef_tile0[o + i] = t0;
-            }
-        }
-        b->ef_nslots = span + 1;
-        b->ef_ok = b->ef_nslots <= 32;
-        if (b->ef_ok) {
-            for (size_t q = 0; q < pr_i.size(); ++q) {
-                const int t = (int)(q >> 6);
-                ef_mask[pr_i[q]] |= 1u << (t - ef_tile0[pr_i[q]]);
-                ef_mask[pr_j[q]] |= 1u << (t - ef_tile0[pr_j[q]]);
-            }
-            for (int v = 0; v < N; ++v) ef_mask[v] |= 1u << (b->ef_nslots - 1);
-            for (size_t q0 = 0; q0 < pr_i.size() && b->ef_ok; q0 += 64) {   // every tile's node range must fit the 128 local nodes of its S matrix
-                int lo = pr_i[q0], hi = pr_j[q0];
-                for (size_t q = q0; q < std::min(pr_i.size(), q0 + 64); ++q) {
-                    lo = std::min(lo, pr_i[q]);
-                    hi = std::max(hi, pr_j[q]);
-                }
-                if (hi - lo + 1 > 128) b->ef_ok = false;
-            }
-        }
-        if (b->ef_ok && MI_HAVE_ABLATION_KERNELS) nslots = std::max(nslots, b->ef_nslots);   // (edge_fused.hip exists in ablation builds only)
-    }
     b->nslots = nslots;
     const int H = net->H, L = net->L;
     const size_t NH = (size_t)N * H;
@@ -1680,8 +1637,6 @@ static int batch_create_impl(const mi_net* net, const int* num_atoms_host, int B
     A_(pair_e2, (size_t)b->Np);
     A_(pair_graph, (size_t)b->Np);
     A_(pair_off, B + 1);
-    A_(ef_tile0, (size_t)std::max(N, 1));
-    if (rc == MI_OK) rc = dev_alloc(b, &b->ef_mask, (size_t)std::max(N, 1));
     A_(e_diag, knn ? 0 : N);
     A_(M1pl, planes_elems(E, H));
     A_(lnpl, planes_elems(N, H));
@@ -1739,8 +1694,6 @@ static int batch_create_impl(const mi_net* net, const int* num_atoms_host, int B
     if (he == hipSuccess) he = up(b->pair_e2, pr_e2);
     if (he == hipSuccess) he = up(b->pair_graph, pr_g);
     if (he == hipSuccess) he = up(b->pair_off, pr_off);
-    if (he == hipSuccess) he = up(b->ef_tile0, ef_tile0);
-    if (he == hipSuccess) he = hipMemcpy(b->ef_mask, ef_mask.data(), ef_mask.size() * sizeof(unsigned), hipMemcpyHostToDevice);
     if (he == hipSuccess) he = up(b->e_diag, ediag);
     if (he != hipSuccess) {
         set_error("index table upload failed: %s", hipGetErrorString(he));
@@ -1869,15 +1822,12 @@ int mi_debug_set_node_priority(int on) {
 }
 
 int mi_debug_set_planes_big_seg(int min_rows) {
-    MI_CHECK(min_rows <= 0 || MI_HAVE_ABLATION_KERNELS, MI_EINVAL, "the segmented-sum epilogue on the 256 x 256 kernel is an ablation instantiation: rebuild with "
-             "MI_EXTRA_FLAGS=-DMI_ABLATION_KERNELS");
-    g_planes_big_seg_min_rows = min_rows;
+    MI_CHECK(min_rows <= 0, MI_EINVAL, "retired: the 256 x 256 kernel has no segmented-sum epilogue (DESIGN 15.3, 26)");
     return MI_OK;
 }
 
 int mi_debug_set_planes_dma(int mode) {
-    MI_CHECK(mode < 4 || MI_HAVE_ABLATION_KERNELS, MI_EINVAL, "mode 4 (the four-waves-per-SIMD build of the 128-row loop) is an ablation instantiation: rebuild with "
-             "MI_EXTRA_FLAGS=-DMI_ABLATION_KERNELS");
+    MI_CHECK(mode < 4, MI_EINVAL, "modes 0 .. 3 (mode 4, the four-waves-per-SIMD build of the 128-row loop, is retired: DESIGN 26)");
     g_planes_dma = mode;
     return MI_OK;
 }

@@ -67,10 +67,6 @@ __device__ __forceinline__ void split3_pair(float x, float y, unsigned (&p)[3]) 
 #ifndef MI_PLANES_FP16
 #define MI_PLANES_FP16 1
 #endif
-// Ablation-only instantiations that SPILL registers (the segmented-sum epilogue on the 256 x 256 LDS-DMA kernel: 576 B of scratch; the
-// four-waves-per-SIMD build of the 128-row loop: 15-16 spilled registers) are compiled only with -DMI_ABLATION_KERNELS: the default library
-// ships no kernel with scratch on any path, and the switches that select them (mi_debug_set_planes_big_seg, mi_debug_set_planes_dma(4))
-// return MI_EINVAL without it.
 // TF32-CLASS BUILD (-DMI_TF32_CLASS=1 -> lib/libmatinvent_hip_tf32.so, `python -m matinvent_amd.build --tf32`; never the default, never the
 // headline): every product of two PLANE SETS keeps its leading term only -- fp16(s a) x fp16(s b), i.e. 11-bit significands with f32
 // accumulation, the arithmetic class the reference itself runs after torch.set_float32_matmul_precision("high") (pipeline/mat_invent.py:127,
@@ -80,11 +76,6 @@ __device__ __forceinline__ void split3_pair(float x, float y, unsigned (&p)[3]) 
 #define MI_TF32_CLASS 0
 #endif
 #define MI_TERM0 (MI_TF32_CLASS ? 2 : 0)   // first term of the (a1 b0), (a0 b1), (a0 b0) sequences
-#ifdef MI_ABLATION_KERNELS
-#define MI_HAVE_ABLATION_KERNELS 1
-#else
-#define MI_HAVE_ABLATION_KERNELS 0
-#endif
 constexpr int NPL = MI_PLANES_FP16 ? 2 : 3;
 // scales by operand class (a plane set carries its scale in Planes::scale; the GEMM multiplies the accumulator by 1 / (sA sW)):
 constexpr float PL_SW = MI_PLANES_FP16 ? 64.f : 1.f;      // weights: exact up to |w| = 1023, residual plane normal down to |w| ~ 2e-3
@@ -145,14 +136,7 @@ __device__ __forceinline__ void pl_split_pair(float x, float y, float scale, uns
 // on the BITS of the leading plane: a half that was clamped (|h| = 65504 = 0x7BFF) or is a NaN (> 0x7C00) carries into bit 15 when 0x0401
 // is added to its magnitude -- and / add / or per PAIR instead of compare / select / or per element.  `sat` is meaningful in bits 15 and 31.
 __device__ __forceinline__ void pl_split_scaled_pair_acc(float xr, float yr, unsigned (&p)[3], unsigned& sat) {   // (xr, yr: already multiplied by the scale)
-#if MI_PLANES_FP16 && defined(MI_AB_SPLIT_R3)   // (A/B builds, scripts/gpu_epi_ab.sh: round 3's form of the split, the compiler's own instruction choice)
-    sat |= ((unsigned)(!(fabsf(xr) <= 65504.f)) | (unsigned)(!(fabsf(yr) <= 65504.f))) << 15;
-    const float xs0 = fminf(fmaxf(xr, -65504.f), 65504.f), ys0 = fminf(fmaxf(yr, -65504.f), 65504.f);
-    const f16x2 h0 = {(_Float16)xs0, (_Float16)ys0};
-    p[0] = __builtin_bit_cast(unsigned, h0);
-    p[1] = pack_f16(xs0 - (float)h0[0], ys0 - (float)h0[1]);
-    p[2] = 0u;
-#elif MI_PLANES_FP16
+#if MI_PLANES_FP16
     // (the instruction itself: fminf(fmaxf()) makes the compiler canonicalise -- v_max x, x -- a value that reaches it through a branch
     //  merge; a NaN comes out as -65504 -- v_med3 returns the minimum of the non-NaN operands -- and is counted like a clamp)
     const float xs = __builtin_amdgcn_fmed3f(xr, -65504.f, 65504.f), ys = __builtin_amdgcn_fmed3f(yr, -65504.f, 65504.f);
@@ -464,7 +448,6 @@ extern int g_planes_big;          // 1: row-major-epilogue products with M >= g_
 extern int g_planes_big_min_rows;
 extern int g_planes_rt;           // row-major-epilogue products with a fragment-order W, N % 256 == 0, K % 64 == 0 on the 128 x 256 register-tile kernel: 0 off, 1 = those with epilogue extensions, 2 = all
 extern int g_planes_rt_min_rows;
-extern int g_planes_big_seg_min_rows;  // > 0: products with the fused segmented sum (second edge GEMM, inference) from this many rows up on the 256 x 256 kernel too
 extern int g_planes_dma;             // 128 x 128 tiles fed by LDS-DMA: 0 = never, 1 = launches of at most g_planes_lat_max_blocks workgroups, 2 = every launch
 extern int g_planes_lat_max_blocks;  // plane GEMMs of at most this many workgroups run the latency form (deep operand prefetch); 0 = never
 extern int g_pair_kernel;  // 0 = 128-row kernel for pair mode (default), 1 = size-based choice
@@ -925,16 +908,14 @@ __device__ __forceinline__ void planes_epilogue_rows(const PlanesEpilogue& pe, f
 // enters as two v_fma_mix_f32 per element.  Addresses: the row tile is the workgroup's, so every plane access is a scalar base + one per-lane
 // offset computed once.  Measured instruction count per element: ~10 against ~25 in the general epilogue, which under a partner wave's MFMAs
 // issue at ~16 cycles each (scripts/rt_phases.py: 29 k cycles of epilogue per workgroup, 60 k with the extensions).
-// (FULL = false: without the gathered addends and the fp32 residual rows -- the persistent ablation kernel's budget, see planes_epilogue_is_lean)
-template <int TM, int TN, bool FULL = true>
+template <int TM, int TN>
 __device__ __forceinline__ void planes_epilogue_lean(const PlanesEpilogue& pe, f32x16 (&acc)[TM][TN], int tile, int col_w, int M, int lane) {
 #if MI_PLANES_FP16
     const GemmEpilogue& ep = pe.ep;
     const int l31 = lane & 31, kg = lane >> 5;
     const float os = pe.oscale(), cps = pe.Cp.s();
     const bool has_res = pe.res_pl.base != nullptr, has_res2 = pe.res2_pl.base != nullptr, has_pm = pe.post_mul != nullptr;
-    const bool has_g = FULL && ep.row_bias != nullptr, has_g2 = FULL && ep.row_bias2 != nullptr, has_rf = FULL && ep.residual != nullptr,
-               has_rf2 = FULL && pe.residual2 != nullptr;
+    const bool has_g = ep.row_bias != nullptr, has_g2 = ep.row_bias2 != nullptr, has_rf = ep.residual != nullptr, has_rf2 = pe.residual2 != nullptr;
     const float s1 = ep.out_scale, s2 = (has_res2 || has_rf2) ? pe.out_scale2 : 1.f;
     const float post = s1 * s2 * cps;
     const float ga = ep.act == ACT_SSILU ? 1.66666666666666667f : 1.f;
@@ -1077,10 +1058,9 @@ __device__ __forceinline__ void planes_epilogue_lean(const PlanesEpilogue& pe, f
     }
 #endif
 }
-// whether a launch's epilogue is the lean one's (host side, gemm_rt); full = false: its form without gathers and fp32 residual rows
-inline bool planes_epilogue_is_lean(const PlanesEpilogue& pe, bool full = true) {
+// whether a launch's epilogue is the lean one's (host side, gemm_rt)
+inline bool planes_epilogue_is_lean(const PlanesEpilogue& pe) {
     const GemmEpilogue& ep = pe.ep;
-    if (!full && (ep.row_bias || ep.row_bias2 || ep.residual || pe.residual2)) return false;
     return MI_PLANES_FP16 && pe.Cp.base && !pe.C && !ep.bias && (ep.row_bias || !ep.row_bias2) && !ep.row_bias3 && !ep.pre_add && !ep.pre_act &&
            !(ep.residual && pe.res_pl.base) && !(pe.residual2 && pe.res2_pl.base) && (pe.residual2 || !pe.res2_rows) && !pe.seg_part && !pe.pair_i &&
            (ep.ld_row_bias & 3) == 0 && (ep.ld_row_bias2 & 3) == 0 && (ep.ld_res & 3) == 0 && (pe.ld_res2 & 3) == 0 && (pe.ld_post_mul & 3) == 0 &&
@@ -1125,11 +1105,7 @@ __device__ __forceinline__ void planes_epilogue_pairs(const PlanesEpilogue& pe, 
             h_e2[i][u] = pe.pair_e2[rc];
         }
     // row r, column c of a row-major fp32 array / of the output plane set, as a pointer
-#ifdef MI_AB_PAIRS_R3   // (A/B builds: round 3's addressing and arithmetic)
-    constexpr bool W64 = true;
-#else
     constexpr bool W64 = WIDE;
-#endif
     auto frow = [&](const float* base, int r, int ld, int c) -> const float* {
         if constexpr (W64) return base + (size_t)r * ld + c;
         else return reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (__umul24((unsigned)r, (unsigned)ld * 4u) + (unsigned)c * 4u));
@@ -1179,52 +1155,30 @@ __device__ __forceinline__ void planes_epilogue_pairs(const PlanesEpilogue& pe, 
                         }
                     };
                     float pii[8], pjj[8], pij[8], pji[8], gg[8];   // (no column bias in pair mode: the caller folds it into the per-crystal addend -- a run-time test of it cost a select per element)
-#if defined(MI_DBG_PAIRS_SKIP) && (MI_DBG_PAIRS_SKIP & 2)   // timing diagnostic (wrong results): no row gathers
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) pii[k] = pjj[k] = pij[k] = pji[k] = gg[k] = 0.25f * (float)(ni + nj + gr);
-#else
                     ld8(pii, frow(ep.row_bias, ni, ep.ld_row_bias, col));     // P_i[i]
                     ld8(pjj, frow(ep.row_bias2, nj, ep.ld_row_bias2, col));   // P_j[j]
                     ld8(pij, frow(ep.row_bias, nj, ep.ld_row_bias, col));     // P_i[j]
                     ld8(pji, frow(ep.row_bias2, ni, ep.ld_row_bias2, col));   // P_j[i]
                     ld8(gg, frow(ep.row_bias3, gr, ep.ld_row_bias3, col));
-#endif
 #pragma unroll
                     for (int dir = 0; dir < 2; ++dir) {
-#if defined(MI_DBG_PAIRS_SKIP) && (MI_DBG_PAIRS_SKIP & 16)  // (timing diagnostic, wrong results: every store lands in the first 1024 rows -- the same instructions, no HBM-side traffic)
-                        const int erow = (dir == 0 ? h_e1[i][u] : h_e2[i][u]) & 1023;
-#elif defined(MI_DBG_PAIRS_SKIP) && (MI_DBG_PAIRS_SKIP & 8)   // (timing diagnostic, wrong results: both directions of a pair in adjacent rows 2 p, 2 p + 1)
-                        const int erow = 2 * row + dir;
-#else
                         const int erow = dir == 0 ? h_e1[i][u] : h_e2[i][u];
-#endif
                         float v[8];
 #pragma unroll
                         for (int k = 0; k < 8; ++k) {
                             const float acc = dir == 0 ? cv[k] + sv[k] : cv[k] - sv[k];
                             const float g = dir == 0 ? (pii[k] + pjj[k]) + gg[k] : (pij[k] + pji[k]) + gg[k];
-#ifdef MI_AB_PAIRS_R3
-                            v[k] = acc * os + g;
-#else
                             v[k] = __builtin_fmaf(acc, os, g);   // = (acc os) + g: acc os is exact
-#endif
                         }
                         if (ep.pre_act) {
                             float* d = const_cast<float*>(frow(ep.pre_act, erow, ep.ld_pre, col));
                             *reinterpret_cast<f32x4*>(d) = f32x4{v[0], v[1], v[2], v[3]};
                             *reinterpret_cast<f32x4*>(d + 4) = f32x4{v[4], v[5], v[6], v[7]};
                         }
-#if !(defined(MI_DBG_PAIRS_SKIP) && (MI_DBG_PAIRS_SKIP & 4))   // (timing diagnostic, wrong results: 4 = no SiLU)
                         if (ep.act == ACT_SILU) {
 #pragma unroll
-#ifdef MI_AB_PAIRS_R3
-                            for (int k = 0; k < 8; ++k) v[k] = silu_fast(v[k]) * cps;
-#else
                             for (int k = 0; k < 8; ++k) v[k] = silu_fast_scaled(v[k], inv_cps);
-#endif
-                        } else
-#endif
-                        {
+                        } else {
 #pragma unroll
                             for (int k = 0; k < 8; ++k) v[k] *= cps;
                         }
@@ -1237,95 +1191,12 @@ __device__ __forceinline__ void planes_epilogue_pairs(const PlanesEpilogue& pe, 
                             o[1][k] = pr[1];
                             o[2][k] = pr[2];
                         }
-#if defined(MI_DBG_PAIRS_SKIP) && (MI_DBG_PAIRS_SKIP & 1)   // (timing diagnostic, wrong results: 1 = one plane store per tile and lane instead of all)
-                        if ((o[0][0] ^ o[1][1]) == 0x12345677u)
-#endif
 #pragma unroll
                         for (int pl = 0; pl < NPL; ++pl) {
                             // (non-temporal stores measured equal: 44.4 / 48.9-50.6 against 44.6 / 49.8-50.6 structures/s on one / four chains)
                             *reinterpret_cast<u32x4*>(prow(erow, col, pl)) = o[pl];
                         }
                     }
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    sat_report(sat);
-}
-
-// ONE direction of the pair-mode epilogue (edge_gemm1e_kernel, edge_stage.hip): `acc` = the whole Fourier term of direction `dir` of each
-// pair (0: i -> j = C + S, 1: j -> i = C - S, both accumulated on the matrix pipe); the gathers, activation and plane stores of
-// planes_epilogue_pairs for that direction only.  The accumulators are read, not consumed: the caller goes on accumulating into them.
-template <int TM, int TN>
-__device__ __forceinline__ void planes_epilogue_pairs_dir(const PlanesEpilogue& pe, const f32x16 (&acc)[TM][TN], int dir, int row_w, int col_w, int M, int N,
-                                                          int lane, float* stage, float cps_in) {
-    const GemmEpilogue& ep = pe.ep;
-    const float os = pe.oscale(), cps = cps_in != 0.f ? cps_in : pe.Cp.base ? pe.Cp.s() : 1.f;
-    const int l31 = lane & 31, kg = lane >> 5;
-    unsigned sat = 0;
-    int h_a[TM][2], h_b[TM][2], h_gr[TM][2], h_e[TM][2];   // dir 0: P_i[i] + P_j[j] -> row e1;  dir 1: P_i[j] + P_j[i] -> row e2
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int row = row_w + i * 32 + ((lane + 64 * u) >> 2);
-            const bool ok = row < M;
-            const int ni = ok ? pe.pair_i[row] : 0, nj = ok ? pe.pair_j[row] : 0;
-            h_a[i][u] = dir == 0 ? ni : nj;
-            h_b[i][u] = dir == 0 ? nj : ni;
-            h_gr[i][u] = ok ? pe.pair_graph[row] : 0;
-            h_e[i][u] = ok ? (dir == 0 ? pe.pair_e1[row] : pe.pair_e2[row]) : 0;
-        }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int rb = row_w + i * 32, cb = col_w + j * 32;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) stage[((r & 3) + 8 * (r >> 2) + 4 * kg) * 36 + l31] = acc[i][j][r] * os;
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int q = lane + 64 * u, rl = q >> 2, c8 = (q & 3) * 8;
-                const int row = rb + rl, col = cb + c8;
-                if (row < M && col < N) {
-                    const f32x4 z0 = *reinterpret_cast<const f32x4*>(stage + rl * 36 + c8), z1 = *reinterpret_cast<const f32x4*>(stage + rl * 36 + c8 + 4);
-                    float v[8] = {z0[0], z0[1], z0[2], z0[3], z1[0], z1[1], z1[2], z1[3]};
-                    auto ld8 = [&](float (&dst)[8], const float* src) {
-                        const f32x4 a = *reinterpret_cast<const f32x4*>(src), b = *reinterpret_cast<const f32x4*>(src + 4);
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            dst[k] = a[k];
-                            dst[4 + k] = b[k];
-                        }
-                    };
-                    float pa[8], pb[8], gg[8];
-                    ld8(pa, ep.row_bias + (size_t)h_a[i][u] * ep.ld_row_bias + col);
-                    ld8(pb, ep.row_bias2 + (size_t)h_b[i][u] * ep.ld_row_bias2 + col);
-                    ld8(gg, ep.row_bias3 + (size_t)h_gr[i][u] * ep.ld_row_bias3 + col);
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = v[k] + ((pa[k] + pb[k]) + gg[k]);
-                    const int erow = h_e[i][u];
-                    if (ep.pre_act) {
-                        float* d = ep.pre_act + (size_t)erow * ep.ld_pre + col;
-                        *reinterpret_cast<f32x4*>(d) = f32x4{v[0], v[1], v[2], v[3]};
-                        *reinterpret_cast<f32x4*>(d + 4) = f32x4{v[4], v[5], v[6], v[7]};
-                    }
-                    if (ep.act == ACT_SILU) {
-#pragma unroll
-                        for (int k = 0; k < 8; ++k) v[k] = silu_fast(v[k]);
-                    }
-                    u32x4 o[3];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        unsigned pr[3];
-                        pl_split_pair_acc(v[2 * k], v[2 * k + 1], cps, pr, sat);
-                        o[0][k] = pr[0];
-                        o[1][k] = pr[1];
-                        o[2][k] = pr[2];
-                    }
-#pragma unroll
-                    for (int pl = 0; pl < NPL; ++pl) *reinterpret_cast<u32x4*>(pe.Cp.base + pe.Cp.elem(erow, col, pl)) = o[pl];
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -1762,13 +1633,6 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(V ==
 void gemm_planes_kernel(Planes A, Planes W, int M, int N, int K, PlanesEpilogue pe, int rt_base) {
     gemm_planes_body<V, TM, EXT>(A, W, M, N, K, pe, rt_base);
 }
-// the register-staged loop compiled for FOUR waves per SIMD (<= 128 registers): a node-level launch of this form fits beside two resident
-// pair-mode workgroups (2 x 190 registers) or two LDS-DMA workgroups (2 x 64 KiB LDS + 32 KiB), instead of waiting for one of them to retire
-template <bool EXT = false>
-static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void gemm_planes_slim_kernel(Planes A, Planes W, int M, int N, int K, PlanesEpilogue pe, int rt_base) {
-    gemm_planes_body<0, 2, EXT, 1>(A, W, M, N, K, pe, rt_base);
-}
 // the LDS-DMA form of the 128 x 128 tile (see gemm_planes_body, PF = 0): two 32 KiB stages, two workgroups per CU
 constexpr int PLANES_DMA_LDS = 2 * 4 * 8192;
 template <int V, bool EXT = false>
@@ -1808,11 +1672,12 @@ constexpr int planes_lds_bytes(int V, int TM) {
 // ------------------------------------------------------------------------------------------------------------------------
 #if MI_PLANES_FP16
 constexpr int GEMM_BIG_STAGE = 8 * 8192, GEMM_BIG_LDS = 2 * GEMM_BIG_STAGE;
-// SEG: the MFMA-layout epilogue with the fused segmented sum instead of the row-major one -- its own instantiation (an ablation, DESIGN
-// 15.3): as a run-time branch inside the default instantiation it cost that one 20-30 % (197 -> 258 us on [102 400, 512] x [512, 512])
+// (SEG = true was the MFMA-layout epilogue with the fused segmented sum: as a run-time branch it cost this kernel 20-30 %, as an instantiation
+//  of its own it spilled -- DESIGN 15.3; last present at 3e3d930.  The parameter stays so that the kernels keep their symbol names.)
 template <bool EXT, bool SEG = false>
 static __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_planes_big_kernel(Planes A, Planes W, int M, int N, int K,
                                                                                                                PlanesEpilogue pe) {
+    static_assert(!SEG, "the row-major epilogue is the only one");
     constexpr int TM = 4, TN = 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     M = pe.rows(M);
@@ -1917,10 +1782,7 @@ static __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2
         }
     }
     __syncthreads();   // the epilogue's per-wave patches overlay the operand stages
-    if constexpr (SEG)   // MFMA-layout epilogue: the second edge GEMM's SiLU + fused segmented sum (inference: no pre-activation rows)
-        planes_epilogue<TM, TN>(pe, acc, row0 + wm * 128, col0 + wn * 64, M, N, l31, kg);
-    else
-        planes_epilogue_rows<TM, TN, EXT>(pe, acc, row0 + wm * 128, col0 + wn * 64, M, N, lane, reinterpret_cast<float*>(smem) + wave * 1152);
+    planes_epilogue_rows<TM, TN, EXT>(pe, acc, row0 + wm * 128, col0 + wn * 64, M, N, lane, reinterpret_cast<float*>(smem) + wave * 1152);
 }
 #endif
 
@@ -2344,25 +2206,15 @@ int gemm_planes(const Planes& A, const Planes& W, int M, int N, int K, const Pla
     } else if (MI_PLANES_FP16 && W.frag && g_planes_rt && (g_planes_rt > 1 || ext) && (N & 255) == 0 && (K & 63) == 0 && K >= 128 && Ms >= g_planes_rt_min_rows &&
                planes_epilogue_is_rows(pe, N)) {
         return gemm_rt(A, W.frag, M, N, K, pe, ext, s);
-    } else if (MI_PLANES_FP16 && (N & 255) == 0 &&
-               ((g_planes_big && (g_planes_big > 1 || !ext) && Ms >= g_planes_big_min_rows && planes_epilogue_is_rows(pe, N)) ||
-                (MI_HAVE_ABLATION_KERNELS && g_planes_big_seg_min_rows > 0 && Ms >= g_planes_big_seg_min_rows && !ext && pe.seg_part && !pe.ep.pre_act &&
-                 !planes_epilogue_is_rows(pe, N)))) {
+    } else if (MI_PLANES_FP16 && (N & 255) == 0 && g_planes_big && (g_planes_big > 1 || !ext) && Ms >= g_planes_big_min_rows && planes_epilogue_is_rows(pe, N)) {
 #if MI_PLANES_FP16
         static bool attr_set = false;
         if (!attr_set) {
             MI_HIP(hipFuncSetAttribute((const void*)gemm_planes_big_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_BIG_LDS));
             MI_HIP(hipFuncSetAttribute((const void*)gemm_planes_big_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_BIG_LDS));
-#if MI_HAVE_ABLATION_KERNELS
-            MI_HIP(hipFuncSetAttribute((const void*)gemm_planes_big_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_BIG_LDS));
-#endif
             attr_set = true;
         }
         const dim3 grid((N >> 8) * ((cdiv(M, 256) + 7) / 8 * 8));
-#if MI_HAVE_ABLATION_KERNELS
-        if (!planes_epilogue_is_rows(pe, N)) hipLaunchKernelGGL((gemm_planes_big_kernel<false, true>), grid, dim3(512), GEMM_BIG_LDS, s, A, W, M, N, K, pe);
-        else
-#endif
         if (ext) hipLaunchKernelGGL(gemm_planes_big_kernel<true>, grid, dim3(512), GEMM_BIG_LDS, s, A, W, M, N, K, pe);
         else hipLaunchKernelGGL(gemm_planes_big_kernel<false>, grid, dim3(512), GEMM_BIG_LDS, s, A, W, M, N, K, pe);
 #endif
@@ -2370,13 +2222,8 @@ int gemm_planes(const Planes& A, const Planes& W, int M, int N, int K, const Pla
         // few tiles (node-level products): 64-row tiles -- twice the workgroups, half the serial MFMA work in each
         if (ext) hipLaunchKernelGGL((gemm_planes_kernel<0, 1, true>), dim3(nct * ((cdiv(M, 64) + 7) / 8 * 8)), dim3(256), planes_lds_bytes(0, 1), s, A, W, M, N, K, pe, 0);
         else hipLaunchKernelGGL((gemm_planes_kernel<0, 1>), dim3(nct * ((cdiv(M, 64) + 7) / 8 * 8)), dim3(256), planes_lds_bytes(0, 1), s, A, W, M, N, K, pe, 0);
-#if MI_HAVE_ABLATION_KERNELS
-    } else if (g_planes_dma >= 4 && nct * ((cdiv(Ms, 128) + 7) / 8 * 8) <= 256) {   // mode 4: one-round launches on the four-waves-per-SIMD build
-        if (ext) hipLaunchKernelGGL((gemm_planes_slim_kernel<true>), dim3(nct * ((cdiv(M, 128) + 7) / 8 * 8)), dim3(256), planes_lds_bytes(0, 2), s, A, W, M, N, K, pe, 0);
-        else hipLaunchKernelGGL((gemm_planes_slim_kernel<false>), dim3(nct * ((cdiv(M, 128) + 7) / 8 * 8)), dim3(256), planes_lds_bytes(0, 2), s, A, W, M, N, K, pe, 0);
-#endif
     } else if (MI_PLANES_FP16 && (g_planes_dma == 2 || (g_planes_dma == 1 && nct * ((cdiv(Ms, 128) + 7) / 8 * 8) <= g_planes_lat_max_blocks) ||
-                                  (g_planes_dma >= 3 && nct * ((cdiv(Ms, 128) + 7) / 8 * 8) > 256))) {   // (modes 3 / 4: the LDS-DMA form for the LARGE launches only)
+                                  (g_planes_dma == 3 && nct * ((cdiv(Ms, 128) + 7) / 8 * 8) > 256))) {   // (mode 3: the LDS-DMA form for the LARGE launches only)
         if (ext) hipLaunchKernelGGL((gemm_planes_dma_kernel<0, true>), dim3(nct * ((cdiv(M, 128) + 7) / 8 * 8)), dim3(256), PLANES_DMA_LDS, s, A, W, M, N, K, pe, 0);
         else hipLaunchKernelGGL((gemm_planes_dma_kernel<0>), dim3(nct * ((cdiv(M, 128) + 7) / 8 * 8)), dim3(256), PLANES_DMA_LDS, s, A, W, M, N, K, pe, 0);
     } else if (nct * ((cdiv(Ms, 128) + 7) / 8 * 8) <= g_planes_lat_max_blocks) {   // at most one round: the latency form

@@ -34,7 +34,6 @@ struct mi_net {
     unsigned short* Waggpl = nullptr;  // (H x H):  node_mlp.0.weight[:, H:]  (multiplies the aggregated messages)
     unsigned short* Wn2pl = nullptr;   // (H x H):  node_mlp.2.weight
     unsigned short* Wffc = nullptr;    // [L] the pair-layout Fourier block of edge_mlp.0 in MFMA fragment order (edge_stage.hip: first edge GEMM)
-    unsigned short* Wffc2 = nullptr;   // [L] -2 x its sine block in the same order (the second pass of edge_gemm1e_kernel)
     unsigned short* Wnc = nullptr;     // [L] the three operands above in MFMA fragment order: [Wagg | Wn2 | Wln] (node_chain.hip; H = 128 / 256 / 512 with LayerNorm)
     float* wbounds = nullptr;          // [L][8] row-sum / bias bounds of the layer's weights (fp16 plane format: activation scales)
     // pair mode of the first edge GEMM (symmetric edge lists): K' = 2*Kh columns = [sin block | pad | cos block | pad],
@@ -120,13 +119,7 @@ struct mi_batch {
     int64_t e_hint = 0;           // the last edge count the HOST has seen (a synchronising build, mi_knn_graph_status): picks kernel forms for capacity-sized launches
     bool knn_nosync = false;      // set by mi_sampler_run around its forwards: the chain's graph builds do not synchronise (mi_knn_graph_status reads the verdict behind it)
     int nslots = 1;
-    int seg_shift = 5;  // log2 of the row-block size behind the partial sums currently in `part` (5: plane GEMM epilogue; 7: edge_stage.hip; -1: edge_fused.hip, slots by mask)
-    // edge_fused.hip (fc pair mode): 64-pair tiles.  ef_tile0[v] = first pair tile of v's crystal, ef_mask[v] = slots (tile - ef_tile0, and
-    // ef_nslots - 1 for the self-edge tile) that hold a partial sum of v; ef_ok: every tile's node range fits 128 and ef_nslots <= 32
-    int* ef_tile0 = nullptr;
-    unsigned* ef_mask = nullptr;
-    int ef_nslots = 0;
-    bool ef_ok = false;
+    int seg_shift = 5;  // log2 of the row-block size behind the partial sums currently in `part` (5: plane GEMM epilogue; 7: edge_stage.hip)
     // knn edge style (CSPNet.gen_edges knn branch, graph.hip)
     int knn = 0, max_neighbors = 0, cap_per_node = 0, deg_cap = 0, nmax = 0;
     // pair tables of the fc edge list (unordered node pairs i < j of each crystal): the first edge GEMM runs over pairs
@@ -250,8 +243,6 @@ extern int g_edge2_train;
 extern int g_node_train;
 extern int g_node_cols;
 extern int g_ablate_skip;
-int edge_fused(mi_net* net, mi_batch* b, int layer, hipStream_t s);   // edge_fused.hip: both edge products of a layer in one launch (M1 stays in LDS)
-bool edge_fused_supported(const mi_net* net, const mi_batch* b);
 int edge_gemm2(mi_net* net, mi_batch* b, int layer, hipStream_t s, float* Z2 = nullptr);   // Z2: optional pre-activation output (training forward)
 int node_chain(mi_net* net, mi_batch* b, int l, hipStream_t s, bool train = false);
 extern int g_knn_nosync;

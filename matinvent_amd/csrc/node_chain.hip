@@ -71,8 +71,8 @@ struct NodeChainArgs {
     const float* part = nullptr;    // [nslots][N][H] partial sums of the edge -> node reduction
     const int* rowptr = nullptr;    // [N + 1] CSR rows (degree, slots)
     int seg_shift = 5;              // log2 of the row-block size the partial sums were formed over (32 rows: plane GEMM; 128: edge_stage.hip)
-    const unsigned* slotmask = nullptr;   // optional [N]: bit s set = slot s holds a partial sum of this node (edge_fused.hip: a node's edges sit in
-    int nslots = 0;                       // several 64-pair tiles + the self-edge tile); summed in increasing slot order instead of the CSR slot range
+    const unsigned* slotmask = nullptr;   // optional [N]: bit s set = slot s holds a partial sum of this node; summed in increasing slot order instead of the CSR slot
+    int nslots = 0;                       // range.  (No producer sets it since the one-launch edge stage went, DESIGN 26: the field stays so that the kernels' text does.)
     const float* xpart = nullptr;   // LayerNorm(h) W0[:, :H]^T of layer l-1 (computed with its P_i / P_j), row stride ld_xpart
     int ld_xpart = 0;
     const u16* Wagg = nullptr;      // fragment-order packs (H x H)
@@ -1064,10 +1064,6 @@ static int node_chain_once(mi_net* net, mi_batch* b, int l, hipStream_t s, bool 
         a.part = b->part;
         a.rowptr = b->rowptr;
         a.seg_shift = b->seg_shift;
-        if (b->seg_shift < 0) {   // (edge_fused.hip wrote the partial sums: slots by mask)
-            a.slotmask = b->ef_mask;
-            a.nslots = b->ef_nslots;
-        }
         a.xpart = ((!train && l == 1 && b->PQ0) ? b->PQ0 : b->PQ) + 2 * H;   // (layer l - 1's X_part: layer 0's is in its own buffer on the inference path, mi_batch::PQ0)
         a.ld_xpart = 3 * H;
         a.Wagg = base;
@@ -1092,9 +1088,6 @@ static int node_chain_once(mi_net* net, mi_batch* b, int l, hipStream_t s, bool 
         a.ln_b = net->p("final_layer_norm.bias");
         a.hf = b->hf;
     }
-#if MI_HAVE_ABLATION_KERNELS   // (the deeper weight ring spills registers: an ablation instantiation, see gemm_split.h)
-    if (H == 512 && g_node_fused == 2) return node_chain_launch<512, 8, 8>(a, s);
-#endif
     auto launch = [&](const NodeChainArgs& x) {
         if (H == 512) return node_chain_launch<512, 8, 4>(x, s);
         if (H == 256) return node_chain_launch<256, 8, 4>(x, s);
@@ -1215,6 +1208,6 @@ extern "C" int mi_debug_set_node_train(int on) {
 
 extern "C" int mi_debug_set_node_fused(int on) {
     const int was = mi::g_node_fused;
-    mi::g_node_fused = on;  // (2: the deeper weight ring at hidden_dim 512 -- ablation)
+    mi::g_node_fused = on;  // (any non-zero value selects the one-launch chain: 2 once named a deeper weight ring that spilled)
     return was;
 }

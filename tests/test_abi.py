@@ -70,6 +70,33 @@ def test_host_only_entry_points():
     lib.mi_net_destroy(h)
 
 
+def test_retired_debug_values_are_pinned():
+    """The setter values that once selected ablation-only kernel forms: the plane GEMM's DMA mode 4 and the big-tile
+    segmented-sum switch are refused, the one-launch edge stage's switch selects nothing, and the first edge GEMM's form numbers 2 .. 4
+    stay accepted.  Host-side state only: no GPU."""
+    lib = _lib.load()
+    try:
+        assert lib.mi_debug_set_planes_dma(1) == 0
+        assert lib.mi_debug_set_planes_dma(4) == _lib.MI_EINVAL
+        assert b"mode" in lib.mi_last_error()
+        assert lib.mi_debug_set_planes_dma(3) == 0   # (this setter and the next return a status, not the previous value: the refusal is what can be read)
+        assert lib.mi_debug_set_planes_big_seg(1) == _lib.MI_EINVAL
+        assert lib.mi_debug_set_planes_big_seg(0) == 0
+        assert lib.mi_debug_set_edge_fused(1) == 0   # retired: returns 0 ...
+        assert lib.mi_debug_set_edge_fused(0) == 0   # ... and the 1 before it selected nothing
+        was = lib.mi_debug_set_edge1_fused(2)
+        assert was == 9                               # the default
+        assert lib.mi_debug_set_edge1_fused(9) == 2   # accepted: read back through the return value
+        was = lib.mi_debug_set_rt_lean(2 | (5 << 2))  # (the bits above bit 1 once sized a persistent grid: ignored)
+        assert lib.mi_debug_set_rt_lean(was) == 2
+    finally:
+        lib.mi_debug_set_planes_dma(1)
+        lib.mi_debug_set_planes_big_seg(0)
+        lib.mi_debug_set_edge_fused(0)
+        lib.mi_debug_set_edge1_fused(9)
+        lib.mi_debug_set_rt_lean(1)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     import pytest
     monkeypatch.setattr(_lib, "_lib", None)

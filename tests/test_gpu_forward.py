@@ -330,24 +330,19 @@ def test_node_chain_launch_vs_the_seven_launch_form(H, L, F, num_atoms, style):
     bt = net.make_batch(num_atoms)
     res = {}
     try:
-        # knob: node chain as seven launches (0) / one launch (1) / one launch with the deeper weight ring (2); 3 = one launch AND the second
-        # edge GEMM on the 128-row x H-column register tiles with the segmented sum on the matrix pipe (edge_stage.hip; hidden_dim 512 only)
-        # 4 = form 3 AND the pair-mode first edge GEMM on the same form (weights in fragment order straight from L2); 5 = its 128 x 256-tile
-        # variant (one workgroup per CU, 512 registers per lane; an ablation build only, otherwise form 4 again); 6 = its 2 x 2-wave variant
-        # (a wave owns 64 pairs x 64 columns); 7 = form 3 with BOTH edge products and the edge -> node sums in one launch (edge_fused.hip: a
-        # workgroup owns 64 pairs, M1 stays in LDS; hidden_dim 512, fc; exists in ablation builds only -- the default library runs form 3 again);
-        # 8 = form 3 with the pair-mode first edge GEMM on ONE accumulator set (128 x 256 tiles, the sine half of K a second time against -2 Wsin:
-        # edge_gemm1e_kernel; widths that are multiples of 256, otherwise form 4's kernel)
+        # knob: node chain as seven launches (0) / one launch (1) / one launch selected by the value 2 (2); 3 = one launch AND the second
+        # edge GEMM on 128-row register tiles with the segmented sum on the matrix pipe (edge_stage.hip; hidden_dim 512 only)
+        # 4 = form 3 AND the pair-mode first edge GEMM on the same form (weights in fragment order straight from L2)
+        # (5 .. 8 selected kernel forms that are gone and had been repeating form 4 or form 3 in the shipped library; the numbers stay retired)
         # 9 = form 3 with the pair-mode epilogue's 64-bit addressing (taken by itself only beyond 4 GB of operands)
         # 10 / 11 = form 3 with the chain's products COLUMN-SPLIT over workgroups (node_cols_kernel: 32 rows x 128 columns of one product per
         # workgroup) as one launch per stage / as one launch per layer boundary with agent-scope flag hand-overs; forms 1 .. 9 keep the row-block chain
-        for knob in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11):
+        for knob in (0, 1, 2, 3, 4, 9, 10, 11):
             lib.mi_debug_set_node_cols(knob - 9 if knob >= 10 else 0)
             lib.mi_debug_set_pair_wide(1 if knob == 9 else 0)
             lib.mi_debug_set_node_fused(1 if knob >= 3 else knob)
             lib.mi_debug_set_edge2_fused(1 if knob >= 3 else 0)
-            lib.mi_debug_set_edge1_fused(knob - 3 if 4 <= knob <= 6 else 4 if knob == 8 else 0)
-            lib.mi_debug_set_edge_fused(1 if knob == 7 else 0)
+            lib.mi_debug_set_edge1_fused(1 if knob == 4 else 0)
             with torch.no_grad():
                 outs = [x.clone() for x in net(t_emb, at, fr, lat, None, batch=bt)]
             res[knob] = outs + [net.tap(bt, l + 1).clone() for l in range(L)]
@@ -357,17 +352,16 @@ def test_node_chain_launch_vs_the_seven_launch_form(H, L, F, num_atoms, style):
         lib.mi_debug_set_node_cols(3)
         lib.mi_debug_set_edge2_fused(1)
         lib.mi_debug_set_edge1_fused(9)   # (the default: the register-tile form for launches beyond the plane GEMM's small-launch forms)
-        lib.mi_debug_set_edge_fused(0)
         lib.mi_debug_set_pair_wide(0)
     assert _lib.saturation_events(reset=True) == 0
-    for knob in (4, 5, 6, 9):
+    for knob in (4, 9):
         for a, b, w in zip(res[knob], res[3], ["pred_l", "pred_x", "pred_t"]):   # same epilogue, same k and term order: the same M1, bit for bit
             assert torch.equal(a, b), f"{w}: the first edge GEMM's forms differ (form {knob})"
     for knob in (10, 11):   # the column-split chain: same arithmetic, same k and term order per output element -- every layer's features, bit for bit
         for a, b, w in zip(res[knob], res[3], ["pred_l", "pred_x", "pred_t"] + [f"h after layer {l}" for l in range(L)]):
             assert torch.equal(a, b), f"{w}: the column-split node chain (form {knob}) differs from the row-block launch"
     names = ["pred_l", "pred_x", "pred_t"] + [f"h after layer {l}" for l in range(L)]
-    for knob in (1, 2, 3, 4, 5, 6, 7, 8):
+    for knob in (1, 2, 3, 4):
         for a, b, w in zip(res[knob], res[0], names):
             # (form 3 sums M2 rounded to the plane format's 22 bits: 1e-6 instead of a few ulp)
             _close(a, b, 2e-6 if knob < 3 else 5e-6, f"{w}: form {knob} vs seven launches")
@@ -375,6 +369,6 @@ def test_node_chain_launch_vs_the_seven_launch_form(H, L, F, num_atoms, style):
         n2g = torch.repeat_interleave(torch.arange(B), na)
         with torch.no_grad():
             ref = O.cspnet_forward(P, hp, t_emb.cpu(), at.cpu(), fr.cpu(), lat.cpu(), na, n2g)
-        for knob in (1, 4, 7, 8):
+        for knob in (1, 3, 4):   # (3: what the retired knob 7 ran in the shipped library)
             for a, b, w in zip(res[knob][:3], ref, names):
                 _close(a, b, 3e-5, f"{w} (form {knob}) vs oracle")

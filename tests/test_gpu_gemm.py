@@ -193,11 +193,9 @@ def test_plane_gemm_latency_and_lds_dma_forms_bit_identical(M, N, K):
     outs = []
     try:
         _lib.check(lib.mi_debug_set_planes_big(0, 1))
-        # (modes 3 / 4 -- recorded ablations: the LDS-DMA form for the LARGE launches only, one-round launches register-staged / on the
-        #  four-waves-per-SIMD build)
-        for dma, lat in ((0, 0), (0, 256), (1, 256), (2, 0), (3, 256), (4, 256)):
-            if lib.mi_debug_set_planes_dma(dma) != 0:   # (mode 4 is an ablation instantiation that spills: only in a -DMI_ABLATION_KERNELS build)
-                continue
+        # (mode 3 -- a recorded ablation: the LDS-DMA form for the LARGE launches only, one-round launches register-staged)
+        for dma, lat in ((0, 0), (0, 256), (1, 256), (2, 0), (3, 256)):
+            _lib.check(lib.mi_debug_set_planes_dma(dma))
             _lib.check(lib.mi_debug_set_planes_latency(lat))
             for _ in range(3 if dma else 1):   # (repeated: a DMA / barrier ordering slip would show as run-to-run differences)
                 out = torch.full((M, N), float("nan"), device="cuda")
@@ -235,12 +233,8 @@ def test_latency_forms_in_the_network_bit_identical(na):
     m.decoder.mark_dirty()
     finals = []
     try:
-        for dma, lat, bigseg, hi in ((0, 0, 0, 0), (0, 256, 0, 0), (1, 256, 0, 0), (2, 0, 0, 0), (1, 256, 1, 0), (1, 256, 0, 1), (3, 256, 0, 0), (4, 256, 0, 0)):
-            # (the instantiations that spill registers -- dma mode 4, the big-tile segmented-sum epilogue -- exist only in a
-            #  -DMI_ABLATION_KERNELS build: their switches refuse otherwise, and the configuration is skipped)
-            if lib.mi_debug_set_planes_dma(dma) != 0 or lib.mi_debug_set_planes_big_seg(bigseg) != 0:
-                lib.mi_debug_set_planes_dma(1)
-                continue
+        for dma, lat, hi in ((0, 0, 0), (0, 256, 0), (1, 256, 0), (2, 0, 0), (1, 256, 1), (3, 256, 0)):
+            _lib.check(lib.mi_debug_set_planes_dma(dma))
             _lib.check(lib.mi_debug_set_planes_latency(lat))
             _lib.check(lib.mi_debug_set_node_priority(hi))        # (1: node-level kernels on the batch's high-priority helper stream, joined by events)
             final, _ = m.sample(Box(na), seed=5, step_lr=5e-6, t_start=1000, t_stop=997, streams=1)
@@ -249,7 +243,6 @@ def test_latency_forms_in_the_network_bit_identical(na):
     finally:
         _lib.check(lib.mi_debug_set_planes_latency(256))
         _lib.check(lib.mi_debug_set_planes_dma(1))
-        _lib.check(lib.mi_debug_set_planes_big_seg(0))
         _lib.check(lib.mi_debug_set_node_priority(0))
         lib.mi_debug_set_node_fused(1)
         lib.mi_debug_set_edge2_fused(1)

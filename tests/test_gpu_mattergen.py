@@ -500,7 +500,7 @@ def test_forward_at_a_size_where_the_large_tile_products_run(planes, f16, lean, 
     _lib.check(_lib.load().mi_debug_set_mg_lean(lean))
     if planes == 4:   # the register-tile kernel's general row epilogue (LDS patch) for the launches that by default take its lean one
         _lib.load().mi_debug_set_rt_lean(0)
-    if planes == 5:   # the lean launches as a persistent grid (a recorded ablation: equal on four chains, 1.7 % slower on one)
+    if planes == 5:   # the value 2 (it once selected a persistent grid: equal on four chains, 1.7 % slower on one) is accepted and behaves as 1
         _lib.load().mi_debug_set_rt_lean(2)
     if planes == 2:   # every qualifying product (epilogue extensions included) on the 256 x 256 LDS-DMA kernel, whatever its row count
         _lib.check(_lib.load().mi_debug_set_planes_big(2, 1))   # (the other cases take the default route: the 128 x 256 register-tile
