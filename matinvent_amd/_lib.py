@@ -172,8 +172,17 @@ PG_KL_SIGNATURES = {
                                 _P, _P, _P, _P]),
 }
 
+# the optimizer extension, include/matinvent_hip_optim.h (gradient-norm clipping and the non-finite-step guard of the fused Adam)
+OPTIM_SIGNATURES = {
+    "mi_optim_state_bytes": (_L, []),
+    "mi_optim_workspace_bytes": (_L, [_L]),
+    "mi_optim_sweep_elems": (_L, [_L]),
+    "mi_grad_norm": (_I, [_P, _L, C.c_float, C.c_float, _I, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
+    "mi_adam_step_guarded": (_I, [_P, _P, _P, _P, _L, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
-EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES)
+EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES)
 
 _lib = None
 

@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from .data import CrystalBatchData, CrystalDataset
 from .dist import allreduce_flat_, rank_world, shard_range
-from .optim import FusedAdam
+from .optim import FusedAdam, clip_options, epoch_grad_stats
 
 
 def _sched_host(agent):
@@ -152,21 +152,26 @@ def ft_step(agent, prior, data_list, rewards, cfg, device=None, noise_fn=None, l
     16.1k / 16.7k / 17.3k / 13.9k crystal-timesteps/s with 2 / 3 / 4 / 6 groups, round 3).
     `stack` (fused path, single group): up to that many consecutive timesteps of an accumulation window run as ONE stacked
     micro-step (the weights only change at the optimizer step, so they are independent; same noise, same gradient up to fp32
-    summation order).  None = automatic (small sets, which are bound by the host's launch rate); 1 = off."""
+    summation order).  None = automatic (small sets, which are bound by the host's launch rate); 1 = off.
+    cfg.max_grad_norm (a number > 0) / cfg.skip_nonfinite_steps (bool), both optional: every optimizer step clips the gradient to that
+    global norm / leaves out a step whose gradient holds inf or NaN, on the device inside FusedAdam.step (optim.py); the epoch
+    dicts then also carry grad_norm, grad_norm_max, clipped_steps, skipped_steps.  The norm is taken after the all-reduce of the gradient
+    (and after the groups' gradients are summed), so every rank computes the same coefficient and takes the same decision."""
     get = (lambda k: cfg[k]) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k))
     lr, accum_steps, epochs, timesteps, sigma = get("lr"), int(get("accum_steps")), int(get("epochs")), int(get("timesteps")), get("sigma")
+    opt = clip_options(cfg)   # max_grad_norm / skip_nonfinite_steps: the same on every path below, or ranks would diverge
     device = device or agent.device
     rank, world = rank_world()
     n_global = len(data_list)
     lo, hi = shard_range(n_global, rank, world)
     if hasattr(agent, "collate"):   # MatterGen-shaped module: its own records / collate, the reference's loop over the module surface
         return _ft_step_module_surface(agent, prior, data_list, rewards, lo, hi, n_global, lr, accum_steps, epochs, timesteps, sigma, device, noise_fn,
-                                       log, rank)
+                                       log, rank, opt)
     dataset = CrystalDataset(data_list, rewards)
     if hi == lo:
         # fewer crystals than ranks (the fine-tune set is top-k + replay and shrinks when the validity filter keeps few samples):
         # this rank has nothing to differentiate, but must take part in every all-reduce and apply every optimizer step
-        return _ft_step_empty_shard(agent, n_global, lr, accum_steps, epochs, timesteps, log, rank)
+        return _ft_step_empty_shard(agent, n_global, lr, accum_steps, epochs, timesteps, log, rank, opt)
     # one batch holding the whole (local shard of the) fine-tune set (:129-133); order is irrelevant to the update
     batch = CrystalBatchData([dataset[i] for i in range(lo, hi)]).to(device)
     node_lo = sum(d.num_atoms for d in dataset.data_list[:lo])
@@ -177,8 +182,8 @@ def ft_step(agent, prior, data_list, rewards, cfg, device=None, noise_fn=None, l
     groups = max(1, min(int(groups), hi - lo)) if fused else 1
     if groups > 1:
         return _ft_step_grouped(agent, prior, dataset, lo, hi, node_lo, n_global, groups, lr, accum_steps, epochs, timesteps, sigma, device,
-                                noise_fn, log, rank)
-    optimizer = FusedAdam([theta], lr=lr)  # fresh every call (:136)
+                                noise_fn, log, rank, opt)
+    optimizer = FusedAdam([theta], lr=lr, **opt)  # fresh every call (:136)
     stats = []
     aux = None
     if fused:  # a single (small) group: fork the frozen prior's forward onto a second, really concurrent stream
@@ -229,20 +234,32 @@ def ft_step(agent, prior, data_list, rewards, cfg, device=None, noise_fn=None, l
             allreduce_flat_(theta.grad)
             optimizer.step()
             optimizer.zero_grad(set_to_none=False)
-        a = _epoch_reduce(acc, "ft_step")
-        d = dict(loss=a[0] / timesteps, loss_diff=a[1] / timesteps / n_global, loss_kl=a[2] / timesteps / n_global)
+        d = _epoch_stats(_epoch_reduce(acc, "ft_step", optimizer), timesteps, n_global)
         stats.append(d)
         if rank == 0:
             log(f"Epoch {epoch}: " + ", ".join(f"{k}: {v:.4f}" for k, v in d.items()))
     return stats
 
 
-def _epoch_reduce(acc, where):
+def _epoch_stats(a, timesteps, n_global):
+    """An epoch's dict from _epoch_reduce's list: the three losses; behind them, when the optimizer clips or guards, its statistics."""
+    d = dict(loss=a[0] / timesteps, loss_diff=a[1] / timesteps / n_global, loss_kl=a[2] / timesteps / n_global)
+    if len(a) > 3:
+        d.update(epoch_grad_stats(a[3:]))
+    return d
+
+
+def _epoch_reduce(acc, where, optimizer=None):
     """End of an epoch on every rank: sum the loss accumulators over the ranks and, in the same collective, the ranks' saturation counts
     of the two-plane fp16 format -- a rank-local check would raise on one rank while its peers go on to the next epoch's all-reduces
-    (a hang instead of an error).  Returns the accumulators as a list; raises FloatingPointError on EVERY rank when any rank saturated."""
+    (a hang instead of an error).  Returns the accumulators as a list; raises FloatingPointError on EVERY rank when any rank saturated.
+    An `optimizer` that clips or guards (FusedAdam.guarded): its statistics of the epoch ride in the same transfer and follow the
+    accumulators in the list (optim.GRAD_STATS order); they are the same on every rank, so rank 0's are the ones summed."""
     from . import _lib
     n_local = _lib.saturation_events(reset=True)   # (synchronises the device: the epoch's kernels have finished)
+    if optimizer is not None and optimizer.guarded:
+        g = optimizer.grad_stats(reset=True).to(torch.float32)
+        acc = torch.cat([acc.to(torch.float32), g if rank_world()[0] == 0 else torch.zeros_like(g)])
     buf = torch.cat([acc.to(torch.float32), torch.tensor([float(min(n_local, 1 << 24))], device=acc.device)])
     allreduce_flat_(buf)
     a = buf.tolist()  # the only host read of the epoch
@@ -257,13 +274,14 @@ def _epoch_reduce(acc, where):
 PRIOR_ON_AUX_STREAM = True   # module-surface loop: the frozen prior's forward concurrently with the agent's
 
 
-def _ft_step_module_surface(agent, prior, data_list, rewards, lo, hi, n_global, lr, accum_steps, epochs, timesteps, sigma, device, noise_fn, log, rank):
+def _ft_step_module_surface(agent, prior, data_list, rewards, lo, hi, n_global, lr, accum_steps, epochs, timesteps, sigma, device, noise_fn, log, rank,
+                            opt=None):
     """pipeline/mat_invent.py:136-189 literally, over the module surface (add_noise / calc_sample_loss / calc_kl_reg; the network is
     one differentiable op with a hand-written backward), with the fused Adam on the flat parameter vector, device-side loss
     accumulators and the data-parallel scaling / all-reduce of ft_step."""
     theta = agent.decoder.theta
     if hi == lo:
-        return _ft_step_empty_shard(agent, n_global, lr, accum_steps, epochs, timesteps, log, rank)
+        return _ft_step_empty_shard(agent, n_global, lr, accum_steps, epochs, timesteps, log, rank, opt)
     # The local shard as chunks of at most FT_CHUNK_ATOMS atoms: the training forward keeps every activation for the backward, and the
     # whole benchmark set (256 crystals x 20 atoms: 171 GB of activations + as much again for their gradients) does not fit one GPU.
     # The update is linear in the per-crystal losses (sum / (n_global * accum_steps)), the noise is indexed by global atom / crystal ids,
@@ -281,7 +299,7 @@ def _ft_step_module_surface(agent, prior, data_list, rewards, lo, hi, n_global, 
     for (a_, b_) in bounds:
         cb = agent.collate(data_list[a_:b_], None if rewards is None else list(rewards[a_:b_])).to(device)
         chunks.append((cb, (sum(d.num_atoms for d in data_list[:a_]), a_)))
-    optimizer = FusedAdam([theta], lr=lr)
+    optimizer = FusedAdam([theta], lr=lr, **(opt or {}))
     stats = []
     aux = None
     if PRIOR_ON_AUX_STREAM and torch.device(device).type == "cuda":
@@ -334,20 +352,20 @@ def _ft_step_module_surface(agent, prior, data_list, rewards, lo, hi, n_global, 
             allreduce_flat_(theta.grad)
             optimizer.step()
             optimizer.zero_grad(set_to_none=False)
-        a = _epoch_reduce(acc, "ft_step")
-        d = dict(loss=a[0] / timesteps, loss_diff=a[1] / timesteps / n_global, loss_kl=a[2] / timesteps / n_global)
+        d = _epoch_stats(_epoch_reduce(acc, "ft_step", optimizer), timesteps, n_global)
         stats.append(d)
         if rank == 0:
             log(f"Epoch {epoch}: " + ", ".join(f"{k}: {v:.4f}" for k, v in d.items()))
     return stats
 
 
-def _ft_step_empty_shard(agent, n_global, lr, accum_steps, epochs, timesteps, log, rank):
-    """ft_step of a rank whose shard is empty: zero gradient contribution, the same collectives and optimizer steps as its peers."""
+def _ft_step_empty_shard(agent, n_global, lr, accum_steps, epochs, timesteps, log, rank, opt=None):
+    """ft_step of a rank whose shard is empty: zero gradient contribution, the same collectives and optimizer steps -- with the same
+    clipping / guard options, hence the same coefficient and the same skipped steps -- as its peers."""
     theta = agent.decoder.theta
     if theta.grad is None:
         theta.grad = torch.zeros_like(theta)
-    optimizer = FusedAdam([theta], lr=lr)
+    optimizer = FusedAdam([theta], lr=lr, **(opt or {}))
     stats = []
     for epoch in range(epochs):
         theta.grad.zero_()
@@ -360,8 +378,7 @@ def _ft_step_empty_shard(agent, n_global, lr, accum_steps, epochs, timesteps, lo
             optimizer.step()
             optimizer.zero_grad(set_to_none=False)
         acc = torch.zeros(3, device=theta.device)
-        a = _epoch_reduce(acc, "ft_step")
-        d = dict(loss=a[0] / timesteps, loss_diff=a[1] / timesteps / n_global, loss_kl=a[2] / timesteps / n_global)
+        d = _epoch_stats(_epoch_reduce(acc, "ft_step", optimizer), timesteps, n_global)
         stats.append(d)
         if rank == 0:
             log(f"Epoch {epoch}: " + ", ".join(f"{k}: {v:.4f}" for k, v in d.items()))
@@ -369,7 +386,7 @@ def _ft_step_empty_shard(agent, n_global, lr, accum_steps, epochs, timesteps, lo
 
 
 def _ft_step_grouped(agent, prior, dataset, lo, hi, node_lo, n_global, groups, lr, accum_steps, epochs, timesteps, sigma, device, noise_fn,
-                     log, rank):
+                     log, rank, opt=None):
     """ft_step's fused path with the local set cut into `groups` crystal groups on concurrent streams (see ft_step)."""
     theta = agent.decoder.theta
     cuts = [lo + (hi - lo) * k // groups for k in range(groups + 1)]
@@ -386,7 +403,7 @@ def _ft_step_grouped(agent, prior, dataset, lo, hi, node_lo, n_global, groups, l
     if theta.grad is None:
         theta.grad = torch.zeros_like(theta)
     grads = [theta.grad] + [torch.zeros_like(theta) for _ in range(groups - 1)]
-    optimizer = FusedAdam([theta], lr=lr)  # fresh every call (:136)
+    optimizer = FusedAdam([theta], lr=lr, **(opt or {}))  # fresh every call (:136); clips the SUM of the groups' gradients
     stats = []
     # The weights only change at the optimizer step, so the node-level linears' weight gradients of a run of micro-steps are ONE
     # contraction over all their rows instead of one short contraction (1.7k rows per group at 256 x 20 atoms) per micro-step: the
@@ -441,7 +458,7 @@ def _ft_step_grouped(agent, prior, dataset, lo, hi, node_lo, n_global, groups, l
     was_groups = _lib.load().mi_set_concurrent_groups(groups)   # (each group's weight-gradient contractions take their share of the chip, not all of it)
     try:
         return _ft_step_grouped_epochs(agent, prior, batches, cuts, nodes, offs, lo, node_lo, n_global, groups, accum_steps, epochs, timesteps, sigma,
-                                       device, noise_fn, log, rank, theta, grads, streams, main, optimizer_step, stats, aux_streams)
+                                       device, noise_fn, log, rank, theta, grads, streams, main, optimizer_step, stats, aux_streams, optimizer)
     finally:
         import sys
         _lib.load().mi_set_concurrent_groups(was_groups)
@@ -456,7 +473,7 @@ def _ft_step_grouped(agent, prior, dataset, lo, hi, node_lo, n_global, groups, l
 
 
 def _ft_step_grouped_epochs(agent, prior, batches, cuts, nodes, offs, lo, node_lo, n_global, groups, accum_steps, epochs, timesteps, sigma, device,
-                            noise_fn, log, rank, theta, grads, streams, main, optimizer_step, stats, aux_streams=None):
+                            noise_fn, log, rank, theta, grads, streams, main, optimizer_step, stats, aux_streams=None, optimizer=None):
     for epoch in range(epochs):
         agent.train()
         theta.grad.zero_()
@@ -486,8 +503,7 @@ def _ft_step_grouped_epochs(agent, prior, batches, cuts, nodes, offs, lo, node_l
         for k in range(groups):
             main.wait_event(streams[k].record_event())
         acc = torch.stack(accs).sum(0)
-        a = _epoch_reduce(acc, "ft_step")
-        d = dict(loss=a[0] / timesteps, loss_diff=a[1] / timesteps / n_global, loss_kl=a[2] / timesteps / n_global)
+        d = _epoch_stats(_epoch_reduce(acc, "ft_step", optimizer), timesteps, n_global)
         stats.append(d)
         if rank == 0:
             log(f"Epoch {epoch}: " + ", ".join(f"{k}: {v:.4f}" for k, v in d.items()))

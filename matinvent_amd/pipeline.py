@@ -223,6 +223,9 @@ class MatInventPG(MatInvent):
                     "ratio mean": last.get("ratio_mean", float("nan"))})
         if float(self.finetune_cfg.get("kl_coef", 0.0) or 0.0) > 0.0:
             log["prior_kl"] = last.get("prior_kl", float("nan"))
+        for k in ("grad_norm", "skipped_steps"):   # (finetune_cfg.max_grad_norm / skip_nonfinite_steps: the optimiser's statistics)
+            if k in last:
+                log[k] = last[k]
         if self.logger is not None:
             self.logger.log(log, step=self.step)
         logging.info(f"*****   LOOP {self.step} FINISH   *****  {(time.time() - t0) / 60:.2f} min")

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from .cspnet import _ptr, _stream
-from .optim import FusedAdam
+from .optim import FusedAdam, clip_options, epoch_grad_stats
 
 # clip_range: DDPO's 1e-4 is below the rounding of the re-evaluated lattice log-probability -- at unchanged weights |log rho| reaches 0.12 over a
 # T = 1000 chain of the benchmark network -- so the default is PPO's 0.2, above that measured maximum
@@ -70,7 +70,12 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
     handle of the prior) serves the call; they are released on return.  A fresh FusedAdam per call, like ft_step.  `seed` seeds the
     timestep draws.  Returns one dict per epoch: loss (mean of L_b over micro-steps and crystals: the clipped surrogate alone), ratio_mean,
     approx_kl (mean of (lp_new - lp_old)^2 / 2) and clip_frac (fraction with |rho - 1| > eps); with kl_coef > 0 also prior_kl (mean of
-    KL_b).  kl_coef = 0 is the surrogate alone: the prior is not evaluated."""
+    KL_b).  kl_coef = 0 is the surrogate alone: the prior is not evaluated.
+    max_grad_norm (a number > 0) clips every optimiser step's gradient to that global norm (DDPO's / DPOK's max_grad_norm) and
+    skip_nonfinite_steps (bool) leaves out a step whose gradient holds inf / NaN, both on the device inside FusedAdam.step (DESIGN 27);
+    with either, the dicts also carry grad_norm (mean norm before clipping), grad_norm_max, clipped_steps and skipped_steps of the epoch,
+    read in the same transfer as the rest."""
+    opt = clip_options(cfg)
     lr, epochs = float(_cfg_get(cfg, "lr")), int(_cfg_get(cfg, "epochs"))
     timesteps, accum_steps = int(_cfg_get(cfg, "timesteps")), int(_cfg_get(cfg, "accum_steps"))
     clip_range = float(_cfg_get(cfg, "clip_range", DEFAULTS["clip_range"]))
@@ -110,7 +115,7 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
         if aux == torch.cuda.current_stream():
             aux = concurrent_streams(2, dev)[0]
     w_host = np.asarray(w, dtype=np.float32)
-    optimizer = FusedAdam([theta], lr=lr)
+    optimizer = FusedAdam([theta], lr=lr, **opt)
     if theta.grad is None:
         theta.grad = torch.zeros_like(theta)
     stats = torch.zeros(5 if use_kl else 4, B, device=dev)
@@ -135,10 +140,15 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
         if K % accum_steps:
             optimizer.step()
             optimizer.zero_grad(set_to_none=False)
-        s = (stats.sum(dim=1) / max(1, K * B)).tolist()                           # one read-back per epoch
+        s = stats.sum(dim=1) / max(1, K * B)
+        if optimizer.guarded:                                                      # (the optimiser's statistics ride in the same transfer)
+            s = torch.cat([s.double(), optimizer.grad_stats(reset=True)])
+        s = s.tolist()                                                             # one read-back per epoch
         d = dict(loss=s[0], ratio_mean=s[1], approx_kl=s[2], clip_frac=s[3])
         if use_kl:
             d["prior_kl"] = s[4]
+        if optimizer.guarded:
+            d.update(epoch_grad_stats(s[stats.shape[0]:]))
         out.append(d)
         log(f"PG epoch {epoch}: " + ", ".join(f"{k}: {v:.4g}" for k, v in d.items()))
     del b_corr, b_pred, b_prior, handles, micro_step
