@@ -181,8 +181,13 @@ OPTIM_SIGNATURES = {
     "mi_adam_step_guarded": (_I, [_P, _P, _P, _P, _L, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P]),
 }
 
+# the strided-chain extension, include/matinvent_hip_stride.h (a batch handle's step-index -> trained-time map)
+STRIDE_SIGNATURES = {
+    "mi_batch_set_time_map": (_I, [_P, C.POINTER(_I), _I]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
-EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES)
+EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES)
 
 _lib = None
 

@@ -206,6 +206,11 @@ struct mi_batch {
     float* kl_val = nullptr;                                                            // [3][B]
     float* kl_pxc = nullptr;                                                            // [N][3] (prior handle)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // fork / join of work put on an auxiliary stream (mi_ft_micro_step)
+    // strided reverse chain (stride.hip, mi_batch_set_time_map): step index k -> trained time tau_k, read by the time embedding alone
+    int* time_map = nullptr;       // [time_map_h.size()] device; NULL: no map, the step index is the time
+    int* time_map_buf = nullptr;   // its allocation (kept when the map is cleared)
+    int time_map_cap = 0;
+    std::vector<int> time_map_h;   // host copy: length checks, comparison between handles
     std::vector<void*> allocs;
 };
 
@@ -245,6 +250,11 @@ extern int g_node_cols;
 extern int g_ablate_skip;
 int edge_gemm2(mi_net* net, mi_batch* b, int layer, hipStream_t s, float* Z2 = nullptr);   // Z2: optional pre-activation output (training forward)
 int node_chain(mi_net* net, mi_batch* b, int l, hipStream_t s, bool train = false);
+// stride.hip: the time embedding of a handle that carries a time map (steps: per-crystal step indices on the device, or NULL: k_all for every
+// crystal), and the entries' host-side checks of the map (MI_EINVAL with the message set)
+int time_embedding_mapped(const mi_batch* b, const int* steps, int k_all, const float* freqs, int B, int TD, float* out, hipStream_t s);
+int time_map_check(const mi_batch* b, int T, const char* what);
+int time_map_same(const mi_batch* p, const mi_batch* q, const char* what);
 extern int g_knn_nosync;
 int knn_build(mi_batch* b, const float* frac, const float* lattices, hipStream_t s, bool nosync = false);
 }  // namespace mi

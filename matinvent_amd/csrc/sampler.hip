@@ -235,6 +235,7 @@ int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int 
     MI_CHECK(net && b && coef_host && time_freqs && atom_types && frac && lattices, MI_EINVAL, "null argument");
     MI_CHECK(T >= 1 && t_start <= T && t_stop >= 0 && t_stop <= t_start, MI_EINVAL, "bad step range T=%d start=%d stop=%d", T,
              t_start, t_stop);
+    MI_TRY(time_map_check(b, T, "the batch handle"));
     hipStream_t s = (hipStream_t)stream;
     const int N = b->N, B = b->B;
     if (N == 0 || B == 0) return MI_OK;
@@ -267,8 +268,12 @@ int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int 
     } nosync_scope(b);
     for (int t = t_start; t > t_stop; --t) {
         TraceRange range("mi_sampler_step");
-        hipLaunchKernelGGL(time_embedding_kernel, dim3(cdiv((int64_t)B * net->TD, 256)), dim3(256), 0, s, (const int*)nullptr, time_freqs, b->temb, B,
-                           net->TD, t);
+        if (b->time_map) {   // a strided chain: t is the step index, the network sees the trained time map[t]
+            MI_TRY(time_embedding_mapped(b, nullptr, t, time_freqs, B, net->TD, b->temb, s));
+        } else {
+            hipLaunchKernelGGL(time_embedding_kernel, dim3(cdiv((int64_t)B * net->TD, 256)), dim3(256), 0, s, (const int*)nullptr, time_freqs, b->temb, B,
+                               net->TD, t);
+        }
         // corrector
         // (the Langevin corrector reads the coordinate score alone, diffusion.py:310-322: the type columns of the heads and the lattice head are not evaluated)
         MI_TRY(net_forward(net, b, b->temb, atom_types, frac, lattices, b->pred_l, b->pred_x, b->pred_t, s, false, false, true));

@@ -179,7 +179,11 @@ static int traj_logprob_enqueue(mi_net* net, mi_batch* bc, mi_batch* bp, const i
         MI_TRY(traj_buffers(bp));
     }
     // time embedding of each crystal's t (diffusion.py:161), once for both evaluations
-    MI_TRY(mi_time_embedding(t_dev, time_freqs, B, net->TD, bc->temb, stream));
+    if (bc->time_map) {   // a strided chain: t_dev holds step indices, the network sees the trained times map[t]
+        MI_TRY(time_embedding_mapped(bc, t_dev, 0, time_freqs, B, net->TD, bc->temb, s));
+    } else {
+        MI_TRY(mi_time_embedding(t_dev, time_freqs, B, net->TD, bc->temb, stream));
+    }
     float* cl = pred_corr_l ? pred_corr_l : bc->pred_l;
     float* cx = pred_corr_x ? pred_corr_x : bc->pred_x;
     float* ct = pred_corr_t ? pred_corr_t : bc->pred_t;
@@ -215,6 +219,12 @@ static int traj_logprob_enqueue(mi_net* net, mi_batch* bc, mi_batch* bp, const i
 
 static bool traj_handles_ok(mi_net* net, mi_batch* bc, mi_batch* bp) {
     return bc->H == net->H && bc->L == net->L && bp->H == net->H && bp->L == net->L;
+}
+
+// strided chains: the pair shares one time map (or has none), and a map has the call's T + 1 entries
+static int traj_time_map_ok(const mi_batch* bc, const mi_batch* bp, int T) {
+    MI_TRY(time_map_same(bc, bp, "the two batch handles carry different time maps"));
+    return time_map_check(bc, T, "the batch handle");
 }
 
 // ---- the PPO-clipped policy-gradient micro-step (mi_traj_pg_step) ----------------------------------------------------------------
@@ -318,6 +328,7 @@ static int pg_check(mi_net* net, mi_batch* bc, mi_batch* bp, const float* coef_d
     MI_CHECK(coef_dev && time_freqs && traj_atom_types && traj_frac && traj_frac_mid && traj_lattices && traj_lp_old && t_host && t_dev &&
                  adv_dev && w_host && grad_theta && stats, MI_EINVAL, "null argument");
     MI_CHECK(T >= 2, MI_EINVAL, "T = %d: a recorded step needs T >= 2", T);
+    MI_TRY(traj_time_map_ok(bc, bp, T));
     MI_CHECK(clip_range >= 0.f, MI_EINVAL, "clip_range = %g: must be >= 0", (double)clip_range);
     MI_CHECK(net->W2T != nullptr, MI_ESTATE, "mi_net_set_params must run before backward");
     for (int i = 0; i < bc->B; ++i)
@@ -508,7 +519,11 @@ static int pg_enqueue(mi_net* net, mi_batch* bc, mi_batch* bp, mi_net* prior, mi
     MI_TRY(pg_gather(bc, T, t_dev, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, s));
     if (prior) {
         hipStream_t sp = aux ? (hipStream_t)aux_stream : s;
-        MI_TRY(mi_time_embedding(bc->pg_t, time_freqs, bc->B, prior->TD, pb->temb, stream));
+        if (pb->time_map) {   // (the entry has checked that it is the agent handles' map)
+            MI_TRY(time_embedding_mapped(pb, bc->pg_t, 0, time_freqs, bc->B, prior->TD, pb->temb, s));
+        } else {
+            MI_TRY(mi_time_embedding(bc->pg_t, time_freqs, bc->B, prior->TD, pb->temb, stream));
+        }
         if (aux) {
             if (!pb->ev_fork) {
                 MI_HIP(hipEventCreateWithFlags(&pb->ev_fork, hipEventDisableTiming));
@@ -550,6 +565,7 @@ int mi_traj_logprob(mi_net* net, mi_batch* bc, mi_batch* bp, const int* t_dev, c
     MI_CHECK(t_dev && coef_dev && time_freqs && atom_types && frac && frac_mid && lattices && next_atom_types && next_frac && next_lattices &&
                  log_prob, MI_EINVAL, "null argument");
     MI_CHECK(T >= 2, MI_EINVAL, "T = %d: a recorded step needs T >= 2", T);
+    MI_TRY(traj_time_map_ok(bc, bp, T));
     hipStream_t s = (hipStream_t)stream;
     const int B = bc->B;
     bc->tr_partner = nullptr;   // whatever was pending on this pair is about to be overwritten
@@ -594,6 +610,7 @@ int mi_traj_pg_kl_step(mi_net* net, mi_batch* bc, mi_batch* bp, mi_net* prior, m
     MI_CHECK(pb != bc && pb != bp, MI_EINVAL, "the prior needs a batch handle of its own");
     MI_CHECK(pb->H == prior->H && pb->L == prior->L, MI_EINVAL, "prior batch was created for a different network");
     MI_CHECK(same_counts(bc, pb), MI_EINVAL, "the prior's batch handle holds different atom counts");
+    MI_TRY(time_map_same(bc, pb, "the prior's batch handle carries another time map than the agent's (a strided chain: both, and the same)"));
     MI_CHECK(prior->TD == net->TD, MI_EINVAL, "the prior's time embedding has %d dimensions, the agent's %d (one frequency table serves both)", prior->TD, net->TD);
     MI_CHECK(kl_coef >= 0.f, MI_EINVAL, "kl_coef = %g: must be >= 0", (double)kl_coef);
     MI_CHECK(prior->theta != nullptr, MI_ESTATE, "mi_net_set_params must run on the prior before it is evaluated");

@@ -12,7 +12,8 @@ import torch.nn as nn
 
 from . import _lib
 from .cspnet import CSPNet, CrystalBatch, MAX_ATOMIC_NUM, _ptr, _stream
-from .schedules import BetaScheduler, SigmaScheduler, sampler_coefficients, time_embedding_freqs
+from .schedules import (BetaScheduler, SigmaScheduler, respaced_schedulers, respaced_times, sampler_coefficients,
+                        time_embedding_freqs)
 
 
 def _scatter_mean(src, index, dim_size):
@@ -98,6 +99,60 @@ class DiffCSPModule(nn.Module):
     def device(self):
         return self.decoder.theta.device
 
+    # ---- strided reverse chain ---------------------------------------------------------
+    base = None       # a view made by `respaced`: the module it shares its decoder with
+    time_map = None   # ... and its grid tau_0 .. tau_S (host int32 [S + 1]); None on a module of the trained grid
+
+    def respaced(self, steps=None, times=None):
+        """A light view of this module whose reverse chain runs on S of the T trained steps: `steps` = S on the default grid
+        tau_k = (2 k T + S) // (2 S), or `times` = an explicit grid (schedules.respaced_times).  The view SHARES the decoder (the same
+        theta: gradients and optimiser steps through the view land in this module), the time-embedding frequencies, the keep flags and
+        the costs; it has its OWN re-spaced schedulers (timesteps = S; schedules.respaced_schedulers), coefficient tables and batch
+        handles, and carries `.base` (this module) and `.time_map` (tau, int32 [S + 1]).  The full grid -- respaced(T), times = 0..T --
+        is this module itself.  Views are kept per grid until a scheduler buffer changes (checkpoint load).
+
+        On a view every `t`, `t_start`, `t_stop`, `timesteps`, record index and the noise stream's step field is a STEP INDEX k in
+        0..S (the initial draw uses S + 1): a strided chain's noise is keyed by step index, so the chains of two grids from one seed
+        share their initial state and nothing else.  The network alone sees the trained time tau_k, through the map every batch
+        handle of the view carries (mi_batch_set_time_map).  sample / forward_logprb / sampling.* / policy.pg_step take a view;
+        the fine-tune surface (add_noise, calc_sample_loss, calc_kl_reg) belongs to the trained grid: use `.base`."""
+        if self.base is not None:
+            raise ValueError("respaced: this module is a strided view already; re-space its .base")
+        T = self.beta_scheduler.timesteps
+        tau = respaced_times(T, steps, times)
+        if len(tau) == T + 1:
+            return self
+        key = (tuple(tau),) + tuple(b._version for b in (self.beta_scheduler.alphas_cumprod, self.sigma_scheduler.sigmas,
+                                                          self.sigma_scheduler.sigmas_norm))
+        cache = self.__dict__.setdefault("_respaced", {})
+        view = cache.get(key)
+        if view is None:
+            for k in [k for k in cache if k[0] == key[0]]:
+                del cache[k]
+            if len(cache) >= 4:
+                cache.pop(next(iter(cache)))
+            view = DiffCSPModule.__new__(DiffCSPModule)
+            nn.Module.__init__(view)
+            view.hparams = self.hparams
+            view.decoder = self.decoder
+            view.beta_scheduler, view.sigma_scheduler = respaced_schedulers(self.beta_scheduler, self.sigma_scheduler, tau)
+            view.time_dim, view.time_embedding = self.time_dim, self.time_embedding
+            view.cost_lattice, view.cost_coord, view.cost_type = self.cost_lattice, self.cost_coord, self.cost_type
+            view.keep_lattice, view.keep_coords = self.keep_lattice, self.keep_coords
+            view.time_map = torch.tensor(tau, dtype=torch.int32)
+            object.__setattr__(view, "base", self)   # (not a submodule of its own view)
+            view.train(self.training)
+            cache[key] = view
+        return view
+
+    def make_batch(self, num_atoms, node_offset=0, graph_offset=0) -> CrystalBatch:
+        """A batch handle of the decoder for THIS module's chain: a strided view's handles carry its time map (set here, once, at creation)."""
+        cb = self.decoder.make_batch(num_atoms, node_offset, graph_offset)
+        if self.time_map is not None:
+            tm = self.time_map.numpy()
+            _lib.check(_lib.load().mi_batch_set_time_map(cb._h, tm.ctypes.data_as(C.POINTER(C.c_int)), len(tm)), "mi_batch_set_time_map")
+        return cb
+
     def _coefficients(self, step_lr):
         """Per-step scalar table, cached until a scheduler buffer changes (checkpoint load)."""
         key = (float(step_lr),) + tuple(b._version for b in (self.beta_scheduler.alphas, self.beta_scheduler.alphas_cumprod,
@@ -123,7 +178,7 @@ class DiffCSPModule(nn.Module):
         key = (id(self), node_offset, graph_offset)
         cb = cache.get(key)
         if cb is None or cb.num_atoms_list != [int(x) for x in batch.num_atoms.tolist()]:
-            cb = self.decoder.make_batch(batch.num_atoms, node_offset, graph_offset)
+            cb = self.make_batch(batch.num_atoms, node_offset, graph_offset)
             cache[key] = cb
         return cb
 
@@ -218,7 +273,7 @@ class DiffCSPModule(nn.Module):
         if pair is None:
             if len(cache) >= 4:
                 cache.pop(next(iter(cache)))
-            pair = _TrajPair(self.decoder.make_batch(list(key)), self.decoder.make_batch(list(key)))
+            pair = _TrajPair(self.make_batch(list(key)), self.make_batch(list(key)))
             cache[key] = pair
         pair.calls += 1   # every call overwrites what the pair holds: a pending backward of an earlier call must refuse (TrajLogProbFunction)
         return pair
@@ -289,7 +344,7 @@ class DiffCSPModule(nn.Module):
         if cb is None:
             if len(cache) >= 8:
                 cache.pop(next(iter(cache)))
-            cb = self.decoder.make_batch(list(key[0]), off[0], off[1])
+            cb = self.make_batch(list(key[0]), off[0], off[1])
             cache[key] = cb
         return cb
 
@@ -306,6 +361,9 @@ class DiffCSPModule(nn.Module):
         HIP streams (crystals never interact, and the counter-based noise is indexed by global atom / crystal id, so the
         samples are the same as those of the unsplit batch): the node-level kernels and the partial last round of one
         group's edge GEMMs overlap the other groups' edge GEMMs.  None = automatic (2-4 for large batches).
+
+        On a strided view (`respaced`) T is the view's S and t_start / t_stop / the keys of `traj` / the first index of `noise` and of the
+        record buffers are step indices 0..S; the counter-based noise is keyed by step index (initial draw: S + 1).
         """
         if self.__dict__.get("_knn_pending"):
             self.check_graph()   # (the verdict of the previous call's chains: by now they have long finished)

@@ -603,6 +603,9 @@ class MatterGenSampler:
         from .sampling import ATOM_DIST
         batch_size, num_batches = batch_size or self.batch_size, num_batches or self.num_batches
         assert batch_size is not None and num_batches is not None
+        if kwargs.get("sample_steps") is not None:
+            raise ValueError("sample_steps is the DiffCSP sampler's strided reverse chain; this sampler's chain length is n_steps "
+                             "(the suite's `sampling_steps`)")
         rank, world = int(kwargs.get("rank", 0)), int(kwargs.get("world_size", 1))
         model.eval()
         p = ATOM_DIST["mp_20"]

@@ -28,6 +28,10 @@ class ReinL:
         self.step, self.cost = 0, 0
         self.sample_cfg = C.merge(model_suite.sample_cfg, sample_cfg)          # pipeline wins (base.py:53-59)
         self.finetune_cfg = C.merge(model_suite.finetune_cfg, finetune_cfg)
+        from .suite import MatterGenSuite
+        if isinstance(model_suite, MatterGenSuite) and self.sample_cfg.get("sample_steps") is not None:
+            raise ValueError("sample_cfg.sample_steps is the DiffCSP suite's strided reverse chain; the MatterGen suite has `sampling_steps` "
+                             "of its own")
         self.sampler = model_suite.get_sampler()
         self.models_dir = os.path.join(save_dir, "models")
         self.sample_dir = os.path.join(save_dir, "samples")
@@ -72,6 +76,8 @@ class MatInvent(ReinL):
         extxyz, optional filter callable, max_num.  MLIP relaxation / SUN metrics are out of scope."""
         rank, world = rank_world()
         kw = {k: v for k, v in self.sample_cfg.items() if k not in ("filter", "mlip_opt", "geometric_filter")}
+        if self.sample_steps is not None:   # (the sampler builds the agent's strided view; ft_step stays on the agent and its trained grid)
+            logging.info(f"sampling on {self.sample_steps} of the model's {self.agent.beta_scheduler.timesteps} steps")
         data, strucs = self.sampler.generate(model=self.agent, rank=rank, world_size=world, **kw)
         if self.sample_cfg.get("geometric_filter", True):  # the reference always filters (mat_invent.py:78-79)
             n_all = len(data)
@@ -87,6 +93,13 @@ class MatInvent(ReinL):
         if max_num and len(strucs) > max_num:
             data, strucs = data[:max_num], strucs[:max_num]
         return data, strucs, None, metrics
+
+    @property
+    def sample_steps(self):
+        """sample_cfg.sample_steps: the reverse chain runs on that many of the model's trained steps (DiffCSPModule.respaced).
+        Absent or null: all of them, nothing re-spaced."""
+        s = self.sample_cfg.get("sample_steps")
+        return None if s is None else int(s)
 
     def ft_step(self, data_list, rewards, baseline=None):
         return _ft_step(self.agent, self.prior, data_list, rewards, self.finetune_cfg, device=self.device)
@@ -157,7 +170,8 @@ class MatInventPG(MatInvent):
     the validity pre-filter, the optional filter callable and max_num, as in MatInvent -> reward_step -> pg_step over EVERY kept
     crystal.  On-policy: there is no top-k and no replay (a stored crystal's log-probabilities belong to weights that no longer exist),
     so replay=True is refused.  Single GPU, DiffCSP only (MatterGen has no log-probability path), one sampling batch per loop.
-    finetune_cfg.kl_coef > 0 anchors the agent's transitions to the frozen prior's (policy.pg_step) and logs prior_kl."""
+    finetune_cfg.kl_coef > 0 anchors the agent's transitions to the frozen prior's (policy.pg_step) and logs prior_kl.
+    sample_cfg.sample_steps = S: rollout and training run through strided views of agent and prior and `rollout steps` is logged."""
 
     def __init__(self, rl_epoch, model_suite, reward, sample_cfg, finetune_cfg, save_dir, save_freq=50, device=None, logger=None,
                  replay=False, replay_args=None, topk_ratio=1.0, **kwargs):
@@ -182,9 +196,9 @@ class MatInventPG(MatInvent):
         from .sampling import sample_rollout
         self.sampler.seed += 1
         data, rollout = sample_rollout(int(self.sample_cfg.batch_size), self.agent, seed=self.sampler.seed,
-                                       geometric_filter=bool(self.sample_cfg.get("geometric_filter", True)))
+                                       geometric_filter=bool(self.sample_cfg.get("geometric_filter", True)), sample_steps=self.sample_steps)
         strucs = [data2struc(d) for d in data]
-        logging.info(f"rollout kept {len(data)} samples")
+        logging.info(f"rollout kept {len(data)} samples" + (f" over {rollout.T} steps" if self.sample_steps is not None else ""))
         if getattr(self, "sample_dir", None):
             write_extxyz(strucs, os.path.join(self.sample_dir, f"step_{self.step:0>4d}_valid.extxyz"))
         pos = {id(d): i for i, d in enumerate(data)}
@@ -217,7 +231,11 @@ class MatInventPG(MatInvent):
                 self.logger.log(log, step=self.step)
             return
         rollout = rollout.select([self._rollout_pos[id(d)] for d in data])
-        stats = pg_step(self.agent, rollout, rewards, self.finetune_cfg, seed=self.sampler.seed, prior=self.prior)
+        agent, prior = self.agent, self.prior
+        if self.sample_steps is not None:   # the views the rollout was recorded through: same theta, the strided grid
+            agent, prior = agent.respaced(self.sample_steps), prior.respaced(self.sample_steps)
+            log["rollout steps"] = rollout.T
+        stats = pg_step(agent, rollout, rewards, self.finetune_cfg, seed=self.sampler.seed, prior=prior)
         last = stats[-1] if stats else {}
         log.update({"clip_frac": last.get("clip_frac", float("nan")), "approx_kl": last.get("approx_kl", float("nan")),
                     "ratio mean": last.get("ratio_mean", float("nan"))})

@@ -74,7 +74,10 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
     max_grad_norm (a number > 0) clips every optimiser step's gradient to that global norm (DDPO's / DPOK's max_grad_norm) and
     skip_nonfinite_steps (bool) leaves out a step whose gradient holds inf / NaN, both on the device inside FusedAdam.step (DESIGN 27);
     with either, the dicts also carry grad_norm (mean norm before clipping), grad_norm_max, clipped_steps and skipped_steps of the epoch,
-    read in the same transfer as the rest."""
+    read in the same transfer as the rest.
+    A strided chain: `agent` a view made by DiffCSPModule.respaced and `rollout` recorded through it -- T is then the view's S,
+    the draws come from 2..S and every time is a step index; with kl_coef > 0 `prior` must be a view on the same grid.  The optimiser
+    steps land in the view's base module: they share theta."""
     opt = clip_options(cfg)
     lr, epochs = float(_cfg_get(cfg, "lr")), int(_cfg_get(cfg, "epochs"))
     timesteps, accum_steps = int(_cfg_get(cfg, "timesteps")), int(_cfg_get(cfg, "accum_steps"))
@@ -97,6 +100,9 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
         raise ValueError("pg_step: the rollout holds no crystal")
     if T != agent.beta_scheduler.timesteps:
         raise ValueError(f"pg_step: the rollout's chain has T = {T}, the agent's T = {agent.beta_scheduler.timesteps}")
+    if kl_coef > 0.0 and not _same_time_map(agent, prior):
+        raise ValueError("pg_step: the prior's time map differs from the agent's: a strided agent (DiffCSPModule.respaced) needs the prior "
+                         "re-spaced to the same grid, prior=prior.respaced(times=agent.time_map)")
     dev = agent.device
     dec = agent.decoder
     theta = dec.theta
@@ -105,9 +111,9 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
     K = draws[0].shape[0] if draws else 0
     M = B * accum_steps
     na = [int(v) for v in rollout.num_atoms.tolist()]
-    b_corr, b_pred = dec.make_batch(na), dec.make_batch(na)                        # this call's pair (freed with the objects on return)
+    b_corr, b_pred = agent.make_batch(na), agent.make_batch(na)                    # this call's pair (freed with the objects on return)
     use_kl = kl_coef > 0.0
-    b_prior = prior.decoder.make_batch(na) if use_kl else None
+    b_prior = prior.make_batch(na) if use_kl else None                             # (a strided view's handles carry its time map)
     aux = None
     if use_kl and PG_KL_AUX:
         from .streams import concurrent_streams
@@ -153,6 +159,14 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
         log(f"PG epoch {epoch}: " + ", ".join(f"{k}: {v:.4g}" for k, v in d.items()))
     del b_corr, b_pred, b_prior, handles, micro_step
     return out
+
+
+def _same_time_map(a, b):
+    """Both modules on their trained grids, or both strided views (DiffCSPModule.respaced) of one grid."""
+    ta, tb = getattr(a, "time_map", None), getattr(b, "time_map", None)
+    if ta is None or tb is None:
+        return ta is None and tb is None
+    return ta.tolist() == tb.tolist()
 
 
 def _micro_step_args(agent, rollout, t_host, t_dev, w_host):

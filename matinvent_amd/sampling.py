@@ -41,8 +41,9 @@ class DiffCSPSampler:
     num_atoms_distribution: str = "mp_20"
     seed: int = 0
 
-    def generate(self, model, batch_size=None, num_batches=None, **kwargs) -> Tuple[List[CrystalData], list]:
+    def generate(self, model, batch_size=None, num_batches=None, sample_steps=None, **kwargs) -> Tuple[List[CrystalData], list]:
         """sample.py:148-201.  Extra kwargs (`max_num`, `filter`, ...) are tolerated like the reference.
+        `sample_steps` = S: the chains run on S of the model's T trained steps (model.respaced(S)); None: all of them.
         As in the reference, every batch is sampled but only the LAST batch's outputs are unpacked
         (sample.py:166-177).  `rank`/`world_size` kwargs shard the batch by crystal (DP): each rank
         samples a contiguous block with global noise offsets and the records are all-gathered."""
@@ -50,6 +51,7 @@ class DiffCSPSampler:
         num_batches = num_batches or self.num_batches
         assert batch_size is not None and num_batches is not None
         rank, world = int(kwargs.get("rank", 0)), int(kwargs.get("world_size", 1))
+        model = _strided(model, sample_steps)
         model.eval()
         dataset = SampleDataset(total_num=batch_size * num_batches, dataset=self.num_atoms_distribution)
         from .dist import collectives_on
@@ -107,6 +109,15 @@ def _draw_seed(seed):
     return int(torch.randint(0, 2 ** 62, (1,))) if seed is None else int(seed)
 
 
+def _strided(model, sample_steps):
+    """`model`, or with sample_steps = S its view on S of its T steps (DiffCSPModule.respaced; S = T is the model itself)."""
+    if sample_steps is None:
+        return model
+    if not hasattr(model, "respaced"):
+        raise ValueError(f"sample_steps = {sample_steps}: {type(model).__name__} has no strided reverse chain")
+    return model.respaced(int(sample_steps))
+
+
 def _prelude(sample_size, model, step_lr):
     """What sample_loop / sample_mdp / sample_rollout do before model.sample: eval mode, the atom-count draw (numpy's global generator) and
     the step_lr default.  Returns (counts, step_lr); the callers draw their seed (_draw_seed) after it, as before."""
@@ -122,13 +133,16 @@ def sample_loop(sample_size, model, device=None, step_lr=-1, seed=None):
     return _unpack(model, counts, outputs)
 
 
-def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None):
+def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_steps=None):
     """sample.py:249-309: sample with the trajectory recorded and return (sample_list, sample_traj), restricted to the crystals that
     pass invalid_filter.  sample_traj[k] is the step t = T - k (t = T .. 2) with the reference's keys (atom_types, lattices, frac_coords,
     frac_coords_mid, num_atoms, timesteps, log_prob_{t,x,l}; host tensors) plus next_frac_coords / next_lattices / next_atom_types --
     the state at t - 1 -- so that any element can go straight to DiffCSPModule.forward_logprb.  (The reference's own sample_mdp unpacks
-    invalid_filter into the wrong values and never builds the next_* keys that forward_logprb reads.)"""
+    invalid_filter into the wrong values and never builds the next_* keys that forward_logprb reads.)
+    A strided view (DiffCSPModule.respaced), or sample_steps = S which builds it: T is the view's S and `timesteps` are step indices --
+    what the VIEW's forward_logprb takes."""
     from .filters import invalid_filter
+    model = _strided(model, sample_steps)
     counts, step_lr = _prelude(sample_size, model, step_lr)
     outputs, traj = model.sample(counts, step_lr=step_lr, seed=_draw_seed(seed), record=True)
     data_list = _unpack(model, counts, outputs)
@@ -194,12 +208,15 @@ class Rollout:
                        torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(na, 0)]), self.T, self.step_lr)
 
 
-def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=True):
+def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=True, sample_steps=None):
     """Sample like sample_mdp (same atom-count draw, seed handling and invalid_filter; geometric_filter=False keeps every crystal) and
     keep the kept crystals' whole trajectories on the device as a Rollout -- compacted once per chain straight from the sampler's stacked
     record buffers, without the per-step dict or a host copy.  Returns (sample_list, rollout).  The policy gradient (policy.pg_step)
-    consumes it.  CSP mode (keep_lattice / keep_coords) is refused: forward_logprb does not model it."""
+    consumes it.  CSP mode (keep_lattice / keep_coords) is refused: forward_logprb does not model it.
+    A strided view (DiffCSPModule.respaced), or sample_steps = S which builds it: rollout.T = S, the arrays are [S + 1, ...] and index k is
+    the state at step index k (trained time tau_k); pg_step then takes the same view as its agent."""
     from .filters import invalid_filter
+    model = _strided(model, sample_steps)
     if getattr(model, "keep_lattice", False) or getattr(model, "keep_coords", False):
         raise ValueError("sample_rollout: CSP mode (keep_lattice / keep_coords) is not supported -- forward_logprb does not model a given "
                          "lattice or given coordinates")

@@ -151,6 +151,9 @@ class MatterGenSuite(ModelSuite):
 
     def get_sampler(self):
         from .mattergen import MatterGenSampler
+        if self.sample_cfg.get("sample_steps") is not None:
+            raise ValueError("sample_cfg.sample_steps is the DiffCSP suite's strided reverse chain; the MatterGen suite has `sampling_steps` "
+                             "of its own")
         return MatterGenSampler(batch_size=self.sample_cfg.batch_size, num_batches=self.sample_cfg.num_batches,
                                 n_steps=int(self.cfg.get("sampling_steps", 1000)))
 

@@ -2,11 +2,12 @@
 C entry (policy.pg_micro_step = mi_traj_pg_step: gather, two taped evaluations, surrogate and seeds, backward) against the unfused
 composition on the same draws (torch indexing of the rollout, forward_logprb, the surrogate in torch, autograd).
 
-    python scripts/pg_step_timing.py [--crystals 64,256] [--iters 10] [--logratio] [--json OUT]
+    python scripts/pg_step_timing.py [--crystals 64,256] [--iters 10] [--logratio] [--sample-steps S] [--json OUT]
 
 Prints one JSON line per batch size: ms per micro-step and crystal-timesteps/s for both paths, next to DESIGN 21's forward_logprb + backward
 (9.2 ms at 64 crystals, 20.7 ms at 256).  --logratio also re-evaluates EVERY step t = 2..T of the rollout at unchanged weights and reports the
 largest |log rho| (the sampler's recorded log-probabilities against the re-evaluation: pure rounding), per term and for w = (1, 1, 1).
+--sample-steps S runs all of it on the strided chain of S of the T steps (DiffCSPModule.respaced): rollout, draws and re-evaluation.
 Under `rocprofv3 --kernel-trace --stats -- python scripts/pg_step_timing.py ...` the stats file gives the gather and surrogate kernels' share
 (traj_pg_gather_kernel, traj_pg_surrogate_kernel)."""
 import argparse
@@ -60,11 +61,15 @@ def main():
     ap.add_argument("--atoms", type=int, default=20)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--logratio", action="store_true")
+    ap.add_argument("--sample-steps", type=int, default=None, help="run on the strided chain of this many of the T = 1000 steps")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     H, L, F, T = 512, 6, 128, 1000
     hp = O.CSPNetHParams(hidden_dim=H, num_layers=L, num_freqs=F)
     m = make_module(H, L, F, T, O.init_params(hp, seed=3, head_scale=0.1))
+    if a.sample_steps is not None:   # everything below through the view: T is its number of steps, every time a step index
+        m = m.respaced(a.sample_steps)
+        T = m.beta_scheduler.timesteps
     eps, w = 1e-4, np.ones(3, np.float32)
     rows = []
     for B in [int(x) for x in a.crystals.split(",")]:
@@ -76,7 +81,7 @@ def main():
         draws_dev = [torch.from_numpy(d).cuda() for d in draws]
         A = torch.from_numpy(policy.advantages(rng.random(B))).cuda()
         M = B
-        handles = (m.decoder.make_batch(na), m.decoder.make_batch(na))
+        handles = (m.make_batch(na), m.make_batch(na))
         grad = torch.zeros_like(m.decoder.theta)
         stats = torch.zeros(4, B, device="cuda")
 
@@ -102,7 +107,7 @@ def main():
 
         ms_unfused = timed(unfused, a.iters)
         m.decoder.theta.grad = None
-        row = dict(crystals=B, atoms=a.atoms, ms_fused=round(ms_fused, 3), ms_unfused=round(ms_unfused, 3),
+        row = dict(crystals=B, atoms=a.atoms, chain_steps=T, ms_fused=round(ms_fused, 3), ms_unfused=round(ms_unfused, 3),
                    fused_over_unfused=round(ms_fused / ms_unfused, 4), crystal_timesteps_per_s_fused=round(B / ms_fused * 1e3, 1),
                    crystal_timesteps_per_s_unfused=round(B / ms_unfused * 1e3, 1), design21_forward_logprb_backward_ms=DESIGN21_MS.get(B))
         if a.logratio:
