@@ -229,7 +229,7 @@ class DiffCSPModule(nn.Module):
 
     def predict(self, input_all):
         """The network evaluation of calc_sample_loss alone (diffusion.py:124-125): library kernels only, no torch arithmetic -- the part
-        that may run on a side stream beside another network's forward (finetune._ft_step_module_surface)."""
+        that may run on a side stream beside another network's forward (finetune._surface_timestep)."""
         noised_input, _, node2graph = input_all
         time_emb, atom_types, frac, lattices, num_atoms, _ = noised_input
         return self.decoder(time_emb, atom_types, frac, lattices, num_atoms, node2graph, batch=self._batch_for(num_atoms))

@@ -10,14 +10,18 @@ grid, a fresh Adam per call.  Differences from the reference, none of which chan
     1/(B_global * accum_steps) (the reference's `.mean()` over the whole batch, :163) and one flat
     all-reduce of the gradient precedes each optimizer step; every rank applies the same fused Adam.
 """
+import ctypes as C
 import logging
+import sys
+from collections import namedtuple
 
 import torch
 
-from . import _lib
+from . import _lib, streams
+from .cspnet import _ptr, _stream
 from .data import CrystalBatchData, CrystalDataset
 from .dist import allreduce_flat_, rank_world, shard_range
-from .optim import FusedAdam, clip_options, epoch_grad_stats
+from .optim import FusedAdam, cfg_get, clip_options, epoch_grad_stats, window_closes
 
 
 def _sched_host(agent):
@@ -33,80 +37,70 @@ def _sched_host(agent):
     return h[1]
 
 
-def _fused_micro_step(agent, prior, batch, time_idx, noise, sigma, n_global, accum_steps, grad, stats, call_id=None, aux_stream=None):
-    """One timestep through mi_ft_micro_step on the current stream; accumulates into `grad` (+=) and `stats` (device, 3
-    floats).  `call_id` = the noise-stream call counter (one value per timestep, shared by every crystal group)."""
-    import ctypes as C
-    from . import _lib
-    from .cspnet import _ptr, _stream
-    lib = _lib.load()
+def _host_atoms(batch):
+    """The batch's atom counts on the host, copied once per batch: no device synchronisation per timestep."""
+    return batch.__dict__.setdefault("_mi_na", batch.num_atoms.cpu())
+
+
+def _micro_step_operands(agent, prior, batch, time_idxs, noises, aux_stream):
+    """What mi_ft_micro_step and mi_ft_micro_steps_stacked share, for the k = len(time_idxs) timesteps of one call.  Returns the leading
+    arguments of both entries (both networks with their batch handles over k replicas of the set, the packed weights of both brought up to
+    date; the set's arrays on the device, repeated k times and cached on the batch per k, three entries at most; the time embedding), the k
+    chain times with their four schedule values (host lists), the injected noise (`noises`: k tuples, the replicas' rows one after the
+    other; or None) and the auxiliary stream's handle."""
     dev = agent.device
+    k = len(time_idxs)
     T = agent.beta_scheduler.timesteps
-    t = T - int(time_idx)
-    na = batch.__dict__.setdefault("_mi_na", batch.num_atoms.cpu())  # host copy made once: no device sync per timestep
+    ts = [T - int(i) for i in time_idxs]
+    na = _host_atoms(batch) if k == 1 else _host_atoms(batch).repeat(k)
     ab, pb = agent._batch_for(na), prior._batch_for(na)
     agent.decoder.sync()
     prior.decoder.sync()
-    sc0, sc1, ssig, ssn = _sched_host(agent)
-    c0, c1, sig, sn = sc0[t], sc1[t], ssig[t], ssn[t]
+    sched = [[s[t] for t in ts] for s in _sched_host(agent)]   # sqrt(alpha_bar), sqrt(1 - alpha_bar), sigma, sigma_norm
     cache = batch.__dict__.setdefault("_mi_dev", {})
-    if not cache:
+    if k not in cache:
         f = lambda x: x.to(dev, torch.float32).contiguous()
-        cache.update(lengths=f(batch.lengths), angles=f(batch.angles), frac=f(batch.frac_coords),
-                     types=batch.atom_types.to(dev, torch.int32).contiguous(), reward=f(batch.reward))
-    nz = (None, None, None) if noise is None else tuple(x.to(dev, torch.float32).contiguous() for x in noise)
+        rep = (lambda x: x) if k == 1 else (lambda x: x.repeat(k, *([1] * (x.dim() - 1))).contiguous())
+        cache[k] = dict(lengths=rep(f(batch.lengths)), angles=rep(f(batch.angles)), frac=rep(f(batch.frac_coords)),
+                        types=rep(batch.atom_types.to(dev, torch.int32).contiguous()), reward=rep(f(batch.reward)))
+        while len(cache) > 3:
+            cache.pop(next(iter(cache)))
+    c = cache[k]
+    nz = (None, None, None)
+    if noises is not None:  # injected noise (parity tests)
+        cols = ([n[j].to(dev, torch.float32) for n in noises] for j in range(3))
+        nz = tuple((col[0] if k == 1 else torch.cat(col)).contiguous() for col in cols)
+    head = (agent.decoder._h, ab._h, prior.decoder._h, pb._h, _ptr(c["lengths"]), _ptr(c["angles"]), _ptr(c["frac"]), _ptr(c["types"]),
+            _ptr(c["reward"]), _ptr(agent.time_embedding.freqs))
+    return head, ts, sched, nz, C.c_void_p(aux_stream.cuda_stream) if aux_stream is not None else None
+
+
+def _fused_micro_step(agent, prior, batch, time_idx, noise, sigma, n_global, accum_steps, grad, stats, call_id=None, aux_stream=None):
+    """One timestep through mi_ft_micro_step on the current stream; accumulates into `grad` (+=) and `stats` (device, 3
+    floats).  `call_id` = the noise-stream call counter (one value per timestep, shared by every crystal group)."""
+    head, (t,), sched, nz, aux = _micro_step_operands(agent, prior, batch, [time_idx], None if noise is None else [noise], aux_stream)
     if call_id is None:
         agent._noise_calls = getattr(agent, "_noise_calls", 0) + 1
         call_id = agent._noise_calls
-    _lib.check(lib.mi_ft_micro_step(agent.decoder._h, ab._h, prior.decoder._h, pb._h, _ptr(cache["lengths"]), _ptr(cache["angles"]),
-                                    _ptr(cache["frac"]), _ptr(cache["types"]), _ptr(cache["reward"]), _ptr(agent.time_embedding.freqs), t,
-                                    c0, c1, sig, sn, getattr(agent, "noise_seed", 0), call_id & 0xFFFFFFFF, _ptr(nz[0]),
-                                    _ptr(nz[1]), _ptr(nz[2]), agent.cost_lattice, agent.cost_coord, agent.cost_type, sigma, n_global,
-                                    accum_steps, _ptr(grad), _ptr(stats), None, None, _stream(),
-                                    C.c_void_p(aux_stream.cuda_stream) if aux_stream is not None else None), "mi_ft_micro_step")
+    _lib.check(_lib.load().mi_ft_micro_step(*head, t, *(s[0] for s in sched), getattr(agent, "noise_seed", 0), call_id & 0xFFFFFFFF,
+                                            _ptr(nz[0]), _ptr(nz[1]), _ptr(nz[2]), agent.cost_lattice, agent.cost_coord, agent.cost_type,
+                                            sigma, n_global, accum_steps, _ptr(grad), _ptr(stats), None, None, _stream(), aux),
+               "mi_ft_micro_step")
 
 
 def _stacked_micro_steps(agent, prior, batch, time_idxs, noises, sigma, n_global, accum_steps, grad, stats, aux_stream=None):
     """`len(time_idxs)` consecutive timesteps of one accumulation window as ONE micro-step over a batch holding that many replicas
     of the fine-tune set (mi_ft_micro_steps_stacked): the same gradient and statistics as calling _fused_micro_step once per
     timestep, with a fraction of the kernel launches -- a single timestep of a small set is bound by the host's launch rate."""
-    import ctypes as C
-    from . import _lib
-    from .cspnet import _ptr, _stream
-    lib = _lib.load()
-    dev = agent.device
     k = len(time_idxs)
-    T = agent.beta_scheduler.timesteps
-    ts = [T - int(i) for i in time_idxs]
-    num_atoms = batch.__dict__.setdefault("_mi_na", batch.num_atoms.cpu()).repeat(k)
-    ab, pb = agent._batch_for(num_atoms), prior._batch_for(num_atoms)
-    agent.decoder.sync()
-    prior.decoder.sync()
-    sc0, sc1, ssig, ssn = _sched_host(agent)
-    arr = lambda ctype, vals: (ctype * k)(*vals)
-    c0, c1 = arr(C.c_float, [sc0[t] for t in ts]), arr(C.c_float, [sc1[t] for t in ts])
-    sig, sn = arr(C.c_float, [ssig[t] for t in ts]), arr(C.c_float, [ssn[t] for t in ts])
-    cache = batch.__dict__.setdefault("_mi_dev_stacked", {})
-    if k not in cache:
-        f = lambda x: x.to(dev, torch.float32).contiguous()
-        rep = lambda x: x.repeat(k, *([1] * (x.dim() - 1))).contiguous()
-        cache[k] = dict(lengths=rep(f(batch.lengths)), angles=rep(f(batch.angles)), frac=rep(f(batch.frac_coords)),
-                        types=rep(batch.atom_types.to(dev, torch.int32)), reward=rep(f(batch.reward)))
-        while len(cache) > 3:
-            cache.pop(next(iter(cache)))
-    c = cache[k]
-    nz = (None, None, None)
-    if noises is not None:  # injected noise (parity tests): the replicas' arrays one after the other
-        nz = tuple(torch.cat([n[j].to(dev, torch.float32) for n in noises]).contiguous() for j in range(3))
+    head, ts, sched, nz, aux = _micro_step_operands(agent, prior, batch, time_idxs, noises, aux_stream)
     call0 = getattr(agent, "_noise_calls", 0) + 1  # replica j uses the call id of its own timestep
     agent._noise_calls = call0 + k - 1
-    _lib.check(lib.mi_ft_micro_steps_stacked(agent.decoder._h, ab._h, prior.decoder._h, pb._h, _ptr(c["lengths"]), _ptr(c["angles"]),
-                                             _ptr(c["frac"]), _ptr(c["types"]), _ptr(c["reward"]), _ptr(agent.time_embedding.freqs), k,
-                                             arr(C.c_int, ts), c0, c1, sig, sn, getattr(agent, "noise_seed", 0), call0 & 0xFFFFFFFF,
-                                             _ptr(nz[0]), _ptr(nz[1]), _ptr(nz[2]), agent.cost_lattice, agent.cost_coord, agent.cost_type,
-                                             sigma, n_global, accum_steps, _ptr(grad), _ptr(stats), _stream(),
-                                             C.c_void_p(aux_stream.cuda_stream) if aux_stream is not None else None),
-               "mi_ft_micro_steps_stacked")
+    arr = lambda ctype, vals: (ctype * k)(*vals)
+    _lib.check(_lib.load().mi_ft_micro_steps_stacked(*head, k, arr(C.c_int, ts), *(arr(C.c_float, s) for s in sched),
+                                                     getattr(agent, "noise_seed", 0), call0 & 0xFFFFFFFF, _ptr(nz[0]), _ptr(nz[1]),
+                                                     _ptr(nz[2]), agent.cost_lattice, agent.cost_coord, agent.cost_type, sigma, n_global,
+                                                     accum_steps, _ptr(grad), _ptr(stats), _stream(), aux), "mi_ft_micro_steps_stacked")
 
 
 MAX_STACK = 16  # MI_MAX_STACK of the C ABI
@@ -138,13 +132,63 @@ def _stack_plan(e_one, accum_steps, timesteps, stack):
     return plan
 
 
+_Config = namedtuple("_Config", "lr accum_steps epochs timesteps sigma opt")   # a fine-tune config as ft_step reads it; opt: FusedAdam's options
+
+
+def _grad_buffer(theta):
+    """theta.grad, allocated (zero) where there is none yet: the fused micro-steps accumulate into it, and a rank without data reduces it."""
+    if theta.grad is None:
+        theta.grad = torch.zeros_like(theta)
+    return theta.grad
+
+
+def _run_epochs(agent, c, n_global, device, log, enqueue, plan=None, start=None, collect=None, before_step=None, after_step=None):
+    """What every route of ft_step shares: a fresh fused Adam, `c.epochs` passes over the timesteps, an optimizer step -- all-reduce of the
+    flat gradient, Adam, zero -- wherever an accumulation window closes, one reduction and one host read at the end of an epoch, its dict
+    and log line.  A route plugs in what is its own:
+      enqueue(epoch, t0, k, acc)   enqueues the timesteps t0 .. t0 + k - 1 (k = the entries of `plan`, each inside one window; default:
+                                   one timestep at a time), accumulating into theta.grad and `acc`;
+      start()                      what an epoch starts with; returns its loss / loss_diff / loss_kl accumulators (default: three device floats);
+      collect(acc)                 the three sums of the epoch from what start() returned (default: `acc` itself);
+      before_step(), after_step()  what surrounds an optimizer step (default: nothing).
+    Every rank must come here with the same `c.opt`, the rank without data included: one that clips differently diverges from its peers."""
+    theta = agent.decoder.theta
+    rank = rank_world()[0]
+    optimizer = FusedAdam([theta], lr=c.lr, **c.opt)  # fresh every call (:136); the norm it clips is the all-reduced one
+    plan = [1] * c.timesteps if plan is None else plan
+    stats = []
+    for epoch in range(c.epochs):
+        agent.train()
+        if theta.grad is not None:
+            optimizer.zero_grad(set_to_none=False)
+        acc = torch.zeros(3, device=device) if start is None else start()  # loss, loss_diff, loss_kl accumulators (device side)
+        t = 0
+        for k in plan:
+            enqueue(epoch, t, k, acc)
+            t += k
+            if window_closes(t, c.accum_steps, c.timesteps):                      # :165-167, :176-177
+                if before_step is not None:
+                    before_step()
+                allreduce_flat_(theta.grad)
+                optimizer.step()
+                optimizer.zero_grad(set_to_none=False)
+                if after_step is not None:
+                    after_step()
+        d = _epoch_stats(_epoch_reduce(acc if collect is None else collect(acc), "ft_step", optimizer), c.timesteps, n_global)
+        stats.append(d)
+        if rank == 0:
+            log(f"Epoch {epoch}: " + ", ".join(f"{k}: {v:.4f}" for k, v in d.items()))
+    return stats
+
+
 def ft_step(agent, prior, data_list, rewards, cfg, device=None, noise_fn=None, log=logging.info, fused=True, groups=None, stack=None):
     """cfg needs: lr, accum_steps, epochs, timesteps, sigma (attribute or key access).
     `noise_fn(epoch, t)` -> (rand_l, rand_x, rand_t) injects noise (parity tests); default Philox.
     fused=True (default) enqueues each timestep through mi_ft_micro_step (noise, both forwards, the fused
     loss / penalty / gradient-seed kernel and the backward in one C call, no autograd graph); fused=False
     drives the same arithmetic through the reference's module surface (add_noise / calc_sample_loss /
-    calc_kl_reg + autograd), which is what the parity tests compare it with.
+    calc_kl_reg + autograd), which is what the parity tests compare it with.  A module with `collate` (the MatterGen-shaped one)
+    always takes that loop (_surface_timestep), over chunks of its set.  Every route runs under one epoch driver (_run_epochs).
     `groups` (fused path): the local fine-tune set is cut into that many contiguous crystal groups whose micro-steps are
     enqueued on separate HIP streams and run concurrently, each accumulating into its own gradient buffer (summed before
     the optimizer step) -- the same arithmetic as data-parallel ranks, inside one GPU: one group's node-level and
@@ -157,88 +201,54 @@ def ft_step(agent, prior, data_list, rewards, cfg, device=None, noise_fn=None, l
     global norm / leaves out a step whose gradient holds inf or NaN, on the device inside FusedAdam.step (optim.py); the epoch
     dicts then also carry grad_norm, grad_norm_max, clipped_steps, skipped_steps.  The norm is taken after the all-reduce of the gradient
     (and after the groups' gradients are summed), so every rank computes the same coefficient and takes the same decision."""
-    get = (lambda k: cfg[k]) if isinstance(cfg, dict) else (lambda k: getattr(cfg, k))
-    lr, accum_steps, epochs, timesteps, sigma = get("lr"), int(get("accum_steps")), int(get("epochs")), int(get("timesteps")), get("sigma")
-    opt = clip_options(cfg)   # max_grad_norm / skip_nonfinite_steps: the same on every path below, or ranks would diverge
+    v = [cfg_get(cfg, k) for k in _Config._fields[:5]]
+    if None in v:   # (before any device work)
+        raise KeyError(f"ft_step: the config has no {_Config._fields[v.index(None)]}")
+    c = _Config(v[0], int(v[1]), int(v[2]), int(v[3]), v[4], clip_options(cfg))   # opt: read once, the same on every route below
     device = device or agent.device
     rank, world = rank_world()
     n_global = len(data_list)
     lo, hi = shard_range(n_global, rank, world)
-    if hasattr(agent, "collate"):   # MatterGen-shaped module: its own records / collate, the reference's loop over the module surface
-        return _ft_step_module_surface(agent, prior, data_list, rewards, lo, hi, n_global, lr, accum_steps, epochs, timesteps, sigma, device, noise_fn,
-                                       log, rank, opt)
-    dataset = CrystalDataset(data_list, rewards)
+    surface = hasattr(agent, "collate")   # MatterGen-shaped module: its own records / collate, always over the module surface
+    dataset = None if surface else CrystalDataset(data_list, rewards)
+    theta = agent.decoder.theta
     if hi == lo:
         # fewer crystals than ranks (the fine-tune set is top-k + replay and shrinks when the validity filter keeps few samples):
         # this rank has nothing to differentiate, but must take part in every all-reduce and apply every optimizer step
-        return _ft_step_empty_shard(agent, n_global, lr, accum_steps, epochs, timesteps, log, rank, opt)
+        _grad_buffer(theta)
+
+        def start():
+            # the Philox call id advances once per timestep on the ranks that hold data: keep this rank's counter in step, so that the noise of
+            # later ft_steps does not depend on which ranks had empty shards before (world-size invariance of the global-id noise)
+            agent._noise_calls = getattr(agent, "_noise_calls", 0) + c.timesteps
+            return torch.zeros(3, device=theta.device)
+        return _run_epochs(agent, c, n_global, device, log, lambda *_: None, start=start)
+    if surface:
+        return _run_epochs(agent, c, n_global, device, log, _surface_timestep(
+            agent, prior, _surface_chunks(agent, data_list, rewards, lo, hi, device, noise_fn), c, n_global, noise_fn,
+            _surface_aux_stream(device)))
     # one batch holding the whole (local shard of the) fine-tune set (:129-133); order is irrelevant to the update
     batch = CrystalBatchData([dataset[i] for i in range(lo, hi)]).to(device)
     node_lo = sum(d.num_atoms for d in dataset.data_list[:lo])
     agent.shard_offsets = prior.shard_offsets = (node_lo, lo)
-    theta = agent.decoder.theta
-    if groups is None:
-        groups = auto_groups(sum(d.num_atoms ** 2 for d in dataset.data_list[lo:hi])) if fused else 1
-    groups = max(1, min(int(groups), hi - lo)) if fused else 1
+    if not fused:   # the parity path: the prior through calc_sample_loss on the current stream, as the reference evaluates it
+        return _run_epochs(agent, c, n_global, device, log, _surface_timestep(agent, prior, [(batch, (node_lo, lo))], c, n_global, noise_fn, None))
+    e_local = sum(d.num_atoms ** 2 for d in dataset.data_list[lo:hi])
+    groups = max(1, min(int(auto_groups(e_local) if groups is None else groups), hi - lo))
     if groups > 1:
-        return _ft_step_grouped(agent, prior, dataset, lo, hi, node_lo, n_global, groups, lr, accum_steps, epochs, timesteps, sigma, device,
-                                noise_fn, log, rank, opt)
-    optimizer = FusedAdam([theta], lr=lr, **opt)  # fresh every call (:136)
-    stats = []
-    aux = None
-    if fused:  # a single (small) group: fork the frozen prior's forward onto a second, really concurrent stream
-        from .streams import concurrent_streams
-        aux = concurrent_streams(2, device)[1]
-    for epoch in range(epochs):
-        agent.train()
-        optimizer.zero_grad(set_to_none=False) if theta.grad is not None else None
-        acc = torch.zeros(3, device=device)  # loss, loss_diff, loss_kl accumulators (device side)
-        t = -1
-        if fused:
-            if theta.grad is None:
-                theta.grad = torch.zeros_like(theta)
-            t0 = 0
-            for k in _stack_plan(sum(d.num_atoms ** 2 for d in dataset.data_list[lo:hi]), accum_steps, timesteps, stack):
-                tidx = list(range(t0, t0 + k))
-                noises = None if noise_fn is None else [noise_fn(epoch, i) for i in tidx]
-                if k == 1:
-                    _fused_micro_step(agent, prior, batch, t0, None if noises is None else noises[0], sigma, n_global, accum_steps, theta.grad,
-                                      acc, aux_stream=aux)
-                else:
-                    _stacked_micro_steps(agent, prior, batch, tidx, noises, sigma, n_global, accum_steps, theta.grad, acc, aux_stream=aux)
-                t0 += k
-                t = t0 - 1
-                if (t + 1) % accum_steps == 0:
-                    allreduce_flat_(theta.grad)
-                    optimizer.step()
-                    optimizer.zero_grad(set_to_none=False)
-        for t in (() if fused else range(timesteps)):
-            noise = None if noise_fn is None else noise_fn(epoch, t)
-            noised = agent.add_noise(batch, t, noise=noise)                       # :152
-            sample_loss, agent_pred = agent.calc_sample_loss(noised)              # :153
-            with torch.no_grad():
-                _, prior_pred = prior.calc_sample_loss(noised)                    # :154 (frozen prior)
-            adv = batch.reward
-            loss_diff = adv * sample_loss                                         # :158
-            kl_term = agent.calc_kl_reg(agent_pred, prior_pred, batch)            # :160
-            loss_kl = kl_term * (1.1 - batch.reward)                              # :161
-            loss = (loss_diff + loss_kl * sigma).sum() / (n_global * accum_steps)  # == .mean() / accum_steps (:163)
-            loss.backward()
-            with torch.no_grad():
-                acc += torch.stack([loss.detach() * accum_steps, loss_diff.detach().sum(), loss_kl.detach().sum()])
-            if (t + 1) % accum_steps == 0:                                        # :165-167
-                allreduce_flat_(theta.grad)
-                optimizer.step()
-                optimizer.zero_grad(set_to_none=False)
-        if (t + 1) % accum_steps != 0:                                            # :176-177
-            allreduce_flat_(theta.grad)
-            optimizer.step()
-            optimizer.zero_grad(set_to_none=False)
-        d = _epoch_stats(_epoch_reduce(acc, "ft_step", optimizer), timesteps, n_global)
-        stats.append(d)
-        if rank == 0:
-            log(f"Epoch {epoch}: " + ", ".join(f"{k}: {v:.4f}" for k, v in d.items()))
-    return stats
+        return _ft_step_grouped(agent, prior, dataset, lo, hi, node_lo, n_global, groups, c, device, noise_fn, log)
+    aux = streams.concurrent_streams(2, device)[1]   # a single (small) group: fork the frozen prior's forward onto a second, really concurrent stream
+    grad = _grad_buffer(theta)
+
+    def enqueue(epoch, t0, k, acc):
+        noises = None if noise_fn is None else [noise_fn(epoch, i) for i in range(t0, t0 + k)]
+        if k == 1:   # (the stacked entry with one replica sums in another order: the single entry keeps its bits)
+            _fused_micro_step(agent, prior, batch, t0, None if noises is None else noises[0], c.sigma, n_global, c.accum_steps, grad, acc,
+                              aux_stream=aux)
+        else:
+            _stacked_micro_steps(agent, prior, batch, list(range(t0, t0 + k)), noises, c.sigma, n_global, c.accum_steps, grad, acc,
+                                 aux_stream=aux)
+    return _run_epochs(agent, c, n_global, device, log, enqueue, plan=_stack_plan(e_local, c.accum_steps, c.timesteps, stack))
 
 
 def _epoch_stats(a, timesteps, n_global):
@@ -255,7 +265,6 @@ def _epoch_reduce(acc, where, optimizer=None):
     (a hang instead of an error).  Returns the accumulators as a list; raises FloatingPointError on EVERY rank when any rank saturated.
     An `optimizer` that clips or guards (FusedAdam.guarded): its statistics of the epoch ride in the same transfer and follow the
     accumulators in the list (optim.GRAD_STATS order); they are the same on every rank, so rank 0's are the ones summed."""
-    from . import _lib
     n_local = _lib.saturation_events(reset=True)   # (synchronises the device: the epoch's kernels have finished)
     if optimizer is not None and optimizer.guarded:
         g = optimizer.grad_stats(reset=True).to(torch.float32)
@@ -271,21 +280,15 @@ def _epoch_reduce(acc, where, optimizer=None):
     return a[:-1]
 
 
-PRIOR_ON_AUX_STREAM = True   # module-surface loop: the frozen prior's forward concurrently with the agent's
+PRIOR_ON_AUX_STREAM = True   # module-surface loop of a MatterGen-shaped module: the frozen prior's forward concurrently with the agent's
 
 
-def _ft_step_module_surface(agent, prior, data_list, rewards, lo, hi, n_global, lr, accum_steps, epochs, timesteps, sigma, device, noise_fn, log, rank,
-                            opt=None):
-    """pipeline/mat_invent.py:136-189 literally, over the module surface (add_noise / calc_sample_loss / calc_kl_reg; the network is
-    one differentiable op with a hand-written backward), with the fused Adam on the flat parameter vector, device-side loss
-    accumulators and the data-parallel scaling / all-reduce of ft_step."""
-    theta = agent.decoder.theta
-    if hi == lo:
-        return _ft_step_empty_shard(agent, n_global, lr, accum_steps, epochs, timesteps, log, rank, opt)
-    # The local shard as chunks of at most FT_CHUNK_ATOMS atoms: the training forward keeps every activation for the backward, and the
-    # whole benchmark set (256 crystals x 20 atoms: 171 GB of activations + as much again for their gradients) does not fit one GPU.
-    # The update is linear in the per-crystal losses (sum / (n_global * accum_steps)), the noise is indexed by global atom / crystal ids,
-    # so chunking changes nothing but the summation order of the gradient.  Injected noise (parity tests) spans the shard: one chunk.
+def _surface_chunks(agent, data_list, rewards, lo, hi, device, noise_fn):
+    """The local shard of a MatterGen-shaped module's set as [(batch, shard offsets)] chunks of at most FT_CHUNK_ATOMS atoms: the training
+    forward keeps every activation for the backward, and the whole benchmark set (256 crystals x 20 atoms: 171 GB of activations + as much
+    again for their gradients) does not fit one GPU.  The update is linear in the per-crystal losses (sum / (n_global * accum_steps)), the
+    noise is indexed by global atom / crystal ids, so chunking changes nothing but the summation order of the gradient.  Injected noise
+    (parity tests) spans the shard: one chunk."""
     from .mattergen import FT_CHUNK_ATOMS
     bounds, c0, atoms = [], lo, 0
     for i in range(lo, hi):
@@ -299,130 +302,87 @@ def _ft_step_module_surface(agent, prior, data_list, rewards, lo, hi, n_global, 
     for (a_, b_) in bounds:
         cb = agent.collate(data_list[a_:b_], None if rewards is None else list(rewards[a_:b_])).to(device)
         chunks.append((cb, (sum(d.num_atoms for d in data_list[:a_]), a_)))
-    optimizer = FusedAdam([theta], lr=lr, **(opt or {}))
-    stats = []
-    aux = None
-    if PRIOR_ON_AUX_STREAM and torch.device(device).type == "cuda":
-        from .streams import concurrent_streams
-        aux = concurrent_streams(2, device)[1]
-        if aux == torch.cuda.current_stream():
-            aux = concurrent_streams(2, device)[0]
-    for epoch in range(epochs):
-        agent.train()
-        if theta.grad is not None:
-            optimizer.zero_grad(set_to_none=False)
-        acc = torch.zeros(3, device=device)
-        t = -1
-        for t in range(timesteps):
-            noise = None if noise_fn is None else noise_fn(epoch, t)
-            calls = getattr(agent, "_noise_calls", 0)
-            for batch, offs in chunks:
-                agent.shard_offsets = prior.shard_offsets = offs
-                agent._noise_calls = calls                                            # (every chunk of a timestep draws from the same Philox step)
-                noised = agent.add_noise(batch, t, noise=noise)                       # :152
-                if aux is not None and hasattr(prior, "predict"):
-                    # the frozen prior's forward on a second stream, under the agent's (separate network and batch handle).  Only the two
-                    # NETWORK evaluations overlap -- kernels of this library, built without packed-fp32 instructions; the loss
-                    # arithmetic is torch's own elementwise kernels, which are not, and runs after the join with nothing beside it.  (The
-                    # prior's sample loss, line :154 of the reference, is computed there and never used: only its prediction is needed.)
-                    aux.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(aux), torch.no_grad():
-                        prior_pred = prior.predict(noised)                            # :154
-                    agent_out = agent.predict(noised)
-                    torch.cuda.current_stream().wait_stream(aux)
-                    for v in (prior_pred.values() if isinstance(prior_pred, dict) else prior_pred):
-                        if torch.is_tensor(v) and v.is_cuda:
-                            v.record_stream(torch.cuda.current_stream())
-                    sample_loss, agent_pred = agent.calc_sample_loss(noised, pred=agent_out)   # :153
-                else:
-                    sample_loss, agent_pred = agent.calc_sample_loss(noised)          # :153
-                    with torch.no_grad():
-                        _, prior_pred = prior.calc_sample_loss(noised)                # :154
-                loss_diff = batch.reward * sample_loss                                # :158
-                loss_kl = agent.calc_kl_reg(agent_pred, prior_pred, batch) * (1.1 - batch.reward)   # :160-161
-                loss = (loss_diff + loss_kl * sigma).sum() / (n_global * accum_steps)  # == .mean() / accum_steps (:163)
-                loss.backward()
+    return chunks
+
+
+def _surface_aux_stream(device):
+    """The stream the frozen prior's forward of the module-surface loop runs on (None: serial): one of a concurrent pair that is not the current one."""
+    if not (PRIOR_ON_AUX_STREAM and torch.device(device).type == "cuda"):
+        return None
+    aux = streams.concurrent_streams(2, device)[1]
+    return streams.concurrent_streams(2, device)[0] if aux == torch.cuda.current_stream() else aux
+
+
+def _surface_timestep(agent, prior, chunks, c, n_global, noise_fn, aux):
+    """_run_epochs' `enqueue` over the module surface: pipeline/mat_invent.py:150-164 literally (add_noise / calc_sample_loss / calc_kl_reg;
+    the network is one differentiable op with a hand-written backward) for every (batch, shard offsets) of `chunks`, with device-side loss
+    accumulators and the data-parallel scaling of ft_step.  `aux`: a stream for the frozen prior's forward (a prior with `predict`)."""
+    def enqueue(epoch, t, k, acc):
+        noise = None if noise_fn is None else noise_fn(epoch, t)
+        calls = getattr(agent, "_noise_calls", 0)
+        for batch, offs in chunks:
+            agent.shard_offsets = prior.shard_offsets = offs
+            agent._noise_calls = calls                                            # (every chunk of a timestep draws from the same Philox step)
+            noised = agent.add_noise(batch, t, noise=noise)                       # :152
+            if aux is not None and hasattr(prior, "predict"):
+                # the frozen prior's forward on a second stream, under the agent's (separate network and batch handle).  Only the two
+                # NETWORK evaluations overlap -- kernels of this library, built without packed-fp32 instructions (DESIGN 18.1); the loss
+                # arithmetic is torch's own elementwise kernels, which are not, and runs after the join with nothing beside it.  (The
+                # prior's sample loss, line :154 of the reference, is computed there and never used: only its prediction is needed.)
+                aux.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(aux), torch.no_grad():
+                    prior_pred = prior.predict(noised)                            # :154
+                agent_out = agent.predict(noised)
+                torch.cuda.current_stream().wait_stream(aux)
+                for v in (prior_pred.values() if isinstance(prior_pred, dict) else prior_pred):
+                    if torch.is_tensor(v) and v.is_cuda:
+                        v.record_stream(torch.cuda.current_stream())
+                sample_loss, agent_pred = agent.calc_sample_loss(noised, pred=agent_out)   # :153
+            else:
+                sample_loss, agent_pred = agent.calc_sample_loss(noised)          # :153
                 with torch.no_grad():
-                    acc += torch.stack([loss.detach() * accum_steps, loss_diff.detach().sum(), loss_kl.detach().sum()])
-            if (t + 1) % accum_steps == 0:                                        # :165-167
-                allreduce_flat_(theta.grad)
-                optimizer.step()
-                optimizer.zero_grad(set_to_none=False)
-        if (t + 1) % accum_steps != 0:                                            # :176-177
-            allreduce_flat_(theta.grad)
-            optimizer.step()
-            optimizer.zero_grad(set_to_none=False)
-        d = _epoch_stats(_epoch_reduce(acc, "ft_step", optimizer), timesteps, n_global)
-        stats.append(d)
-        if rank == 0:
-            log(f"Epoch {epoch}: " + ", ".join(f"{k}: {v:.4f}" for k, v in d.items()))
-    return stats
+                    _, prior_pred = prior.calc_sample_loss(noised)                # :154 (frozen prior)
+            loss_diff = batch.reward * sample_loss                                # :158
+            loss_kl = agent.calc_kl_reg(agent_pred, prior_pred, batch) * (1.1 - batch.reward)   # :160-161
+            loss = (loss_diff + loss_kl * c.sigma).sum() / (n_global * c.accum_steps)  # == .mean() / accum_steps (:163)
+            loss.backward()
+            with torch.no_grad():
+                acc += torch.stack([loss.detach() * c.accum_steps, loss_diff.detach().sum(), loss_kl.detach().sum()])
+    return enqueue
 
 
-def _ft_step_empty_shard(agent, n_global, lr, accum_steps, epochs, timesteps, log, rank, opt=None):
-    """ft_step of a rank whose shard is empty: zero gradient contribution, the same collectives and optimizer steps -- with the same
-    clipping / guard options, hence the same coefficient and the same skipped steps -- as its peers."""
-    theta = agent.decoder.theta
-    if theta.grad is None:
-        theta.grad = torch.zeros_like(theta)
-    optimizer = FusedAdam([theta], lr=lr, **(opt or {}))
-    stats = []
-    for epoch in range(epochs):
-        theta.grad.zero_()
-        # the Philox call id advances once per timestep on the ranks that hold data: keep this rank's counter in step, so that the noise of
-        # later ft_steps does not depend on which ranks had empty shards before (world-size invariance of the global-id noise)
-        agent._noise_calls = getattr(agent, "_noise_calls", 0) + timesteps
-        n_steps = timesteps // accum_steps + (1 if timesteps % accum_steps else 0)
-        for _ in range(n_steps):
-            allreduce_flat_(theta.grad)
-            optimizer.step()
-            optimizer.zero_grad(set_to_none=False)
-        acc = torch.zeros(3, device=theta.device)
-        d = _epoch_stats(_epoch_reduce(acc, "ft_step", optimizer), timesteps, n_global)
-        stats.append(d)
-        if rank == 0:
-            log(f"Epoch {epoch}: " + ", ".join(f"{k}: {v:.4f}" for k, v in d.items()))
-    return stats
-
-
-def _ft_step_grouped(agent, prior, dataset, lo, hi, node_lo, n_global, groups, lr, accum_steps, epochs, timesteps, sigma, device, noise_fn,
-                     log, rank, opt=None):
+def _ft_step_grouped(agent, prior, dataset, lo, hi, node_lo, n_global, groups, c, device, noise_fn, log):
     """ft_step's fused path with the local set cut into `groups` crystal groups on concurrent streams (see ft_step)."""
     theta = agent.decoder.theta
     cuts = [lo + (hi - lo) * k // groups for k in range(groups + 1)]
-    nodes = [node_lo]
+    offs = [(node_lo, lo)]   # (first atom, first crystal) of every group, global ids; behind them the end of the last group
     for k in range(groups):
-        nodes.append(nodes[-1] + sum(d.num_atoms for d in dataset.data_list[cuts[k]:cuts[k + 1]]))
+        offs.append((offs[-1][0] + sum(d.num_atoms for d in dataset.data_list[cuts[k]:cuts[k + 1]]), cuts[k + 1]))
     batches = [CrystalBatchData([dataset[i] for i in range(cuts[k], cuts[k + 1])]).to(device) for k in range(groups)]
-    offs = [(nodes[k], cuts[k]) for k in range(groups)]
+    # injected noise (rand_l [B,3,3], rand_x [N,3], rand_t [N,100]) of the local set -> every group's crystal rows and atom rows
+    rows = [(slice(a[1] - lo, b[1] - lo), slice(a[0] - node_lo, b[0] - node_lo)) for a, b in zip(offs, offs[1:])]
     main = torch.cuda.current_stream()
-    from .streams import concurrent_streams
-    streams = concurrent_streams(groups, device)
+    gstreams = streams.concurrent_streams(groups, device)
     # FT_PRIOR_AUX (experiment, MI_FT_PRIOR_AUX=1): every group forks its frozen prior's forward onto a stream of its own, as the single-group path does
-    aux_streams = concurrent_streams(2 * groups, device)[groups:] if FT_PRIOR_AUX else [None] * groups
-    if theta.grad is None:
-        theta.grad = torch.zeros_like(theta)
-    grads = [theta.grad] + [torch.zeros_like(theta) for _ in range(groups - 1)]
-    optimizer = FusedAdam([theta], lr=lr, **(opt or {}))  # fresh every call (:136); clips the SUM of the groups' gradients
-    stats = []
+    aux_streams = streams.concurrent_streams(2 * groups, device)[groups:] if FT_PRIOR_AUX else [None] * groups
+    grads = [_grad_buffer(theta)] + [torch.zeros_like(theta) for _ in range(groups - 1)]
     # The weights only change at the optimizer step, so the node-level linears' weight gradients of a run of micro-steps are ONE
     # contraction over all their rows instead of one short contraction (1.7k rows per group at 256 x 20 atoms) per micro-step: the
     # agent's batch handles keep the operand rows of up to WGRAD_WINDOW micro-steps (see include/matinvent_hip.h).
     # `cap`: the window a LATER call on these handles may ask for (its timesteps are not known here) -- the buffers are sized for it once, so that a short first
     # call (a warm-up of three timesteps) is not followed by a reallocation -- sixteen hipFree / hipMalloc pairs per group, each a device synchronisation -- at the
     # start of the next one (measured: a 20-timestep call behind a 3-timestep warm-up ran at 13.1 k instead of 19-21 k crystal-timesteps/s)
-    cap = min(accum_steps, WGRAD_WINDOW) if groups <= 8 else 0   # (_batch_for caches eight handles per module)
+    cap = min(c.accum_steps, WGRAD_WINDOW) if groups <= 8 else 0   # (_batch_for caches eight handles per module)
     dec = agent.decoder
-    nmax_ = max(nodes[k + 1] - nodes[k] for k in range(groups))
+    nmax_ = max(b[0] - a[0] for a, b in zip(offs, offs[1:]))
     slot_bytes = (7 * dec.hidden_dim * dec.num_layers + 4 * dec.hidden_dim + 203) * nmax_ * 4   # operand rows of one micro-step: node-level linears + heads / embedding
     # at most 8 GB of kept rows per group AND 24 GB over all groups (the windows of the groups are live together)
     cap = max(0, min(cap, (8 << 30) // max(1, slot_bytes), (24 << 30) // max(1, slot_bytes * groups)))
-    window = min(cap, timesteps)
+    window = min(cap, c.timesteps)
     handles = []
     for k in range(groups):
         agent.shard_offsets = offs[k]
-        ab = agent._batch_for(batches[k].__dict__.setdefault("_mi_na", batches[k].num_atoms.cpu()))
-        handles.append(ab)
+        handles.append(agent._batch_for(_host_atoms(batches[k])))
     try:
         for ab in handles:
             if cap > window > 1:
@@ -437,30 +397,56 @@ def _ft_step_grouped(agent, prior, dataset, lo, hi, node_lo, n_global, groups, l
 
     def flush_wgrads():
         for k in range(groups):
-            with torch.cuda.stream(streams[k]):
+            with torch.cuda.stream(gstreams[k]):
                 handles[k].wgrad_flush(agent.decoder, grads[k])
 
-    def optimizer_step():
+    def release():   # the group streams go on behind what the main stream holds now
+        ready = main.record_event()
+        for st in gstreams:
+            st.wait_event(ready)
+
+    def join():      # the main stream goes on behind what every group stream holds now
+        for st in gstreams:
+            main.wait_event(st.record_event())
+
+    def start():
+        accs = [torch.zeros(3, device=device) for _ in range(groups)]
+        agent.decoder.sync()
+        prior.decoder.sync()
+        release()
+        return accs
+
+    def enqueue(epoch, t, _, accs):   # one micro-step per group, all with the timestep's one noise call id
+        noise = None if noise_fn is None else noise_fn(epoch, t)
+        agent._noise_calls = getattr(agent, "_noise_calls", 0) + 1
+        for k in range(groups):
+            nz = None if noise is None else (noise[0][rows[k][0]], noise[1][rows[k][1]], noise[2][rows[k][1]])
+            agent.shard_offsets = prior.shard_offsets = offs[k]
+            with torch.cuda.stream(gstreams[k]):
+                _fused_micro_step(agent, prior, batches[k], t, nz, c.sigma, n_global, c.accum_steps, grads[k], accs[k],
+                                  call_id=agent._noise_calls, aux_stream=aux_streams[k])
+
+    def before_step():   # the optimizer consumes (and clips) the SUM of the groups' gradients
         flush_wgrads()
-        for k in range(groups):  # the optimizer consumes every group's gradient
-            main.wait_event(streams[k].record_event())
+        join()
         for g in grads[1:]:
             theta.grad.add_(g)
             g.zero_()
-        allreduce_flat_(theta.grad)
-        optimizer.step()
-        optimizer.zero_grad(set_to_none=False)
-        agent.decoder.sync()  # repack the updated weights once, on the main stream, before any group reads them
-        ready = main.record_event()
-        for st in streams:
-            st.wait_event(ready)
+
+    def after_step():    # repack the updated weights once, on the main stream, before any group reads them
+        agent.decoder.sync()
+        release()
+
+    def collect(accs):
+        join()
+        return torch.stack(accs).sum(0)
 
     was_groups = _lib.load().mi_set_concurrent_groups(groups)   # (each group's weight-gradient contractions take their share of the chip, not all of it)
     try:
-        return _ft_step_grouped_epochs(agent, prior, batches, cuts, nodes, offs, lo, node_lo, n_global, groups, accum_steps, epochs, timesteps, sigma,
-                                       device, noise_fn, log, rank, theta, grads, streams, main, optimizer_step, stats, aux_streams, optimizer)
+        stats = _run_epochs(agent, c, n_global, device, log, enqueue, start=start, collect=collect, before_step=before_step, after_step=after_step)
+        agent.shard_offsets = prior.shard_offsets = (node_lo, lo)
+        return stats
     finally:
-        import sys
         _lib.load().mi_set_concurrent_groups(was_groups)
         failing = sys.exc_info()[0] is not None
         try:   # (nothing pending unless an exception cut a window short -- and then its own error must not replace that exception)
@@ -470,42 +456,3 @@ def _ft_step_grouped(agent, prior, dataset, lo, hi, node_lo, n_global, groups, l
         except Exception:
             if not failing:
                 raise
-
-
-def _ft_step_grouped_epochs(agent, prior, batches, cuts, nodes, offs, lo, node_lo, n_global, groups, accum_steps, epochs, timesteps, sigma, device,
-                            noise_fn, log, rank, theta, grads, streams, main, optimizer_step, stats, aux_streams=None, optimizer=None):
-    for epoch in range(epochs):
-        agent.train()
-        theta.grad.zero_()
-        accs = [torch.zeros(3, device=device) for _ in range(groups)]
-        agent.decoder.sync()
-        prior.decoder.sync()
-        ready = main.record_event()
-        for st in streams:
-            st.wait_event(ready)
-        t = -1
-        for t in range(timesteps):
-            noise = None if noise_fn is None else noise_fn(epoch, t)
-            agent._noise_calls = getattr(agent, "_noise_calls", 0) + 1
-            for k in range(groups):
-                nz = None
-                if noise is not None:  # (rand_l [B,3,3], rand_x [N,3], rand_t [N,100]) of the local set -> this group's rows
-                    g0, g1, n0, n1 = cuts[k] - lo, cuts[k + 1] - lo, nodes[k] - node_lo, nodes[k + 1] - node_lo
-                    nz = (noise[0][g0:g1], noise[1][n0:n1], noise[2][n0:n1])
-                agent.shard_offsets = prior.shard_offsets = offs[k]
-                with torch.cuda.stream(streams[k]):
-                    _fused_micro_step(agent, prior, batches[k], t, nz, sigma, n_global, accum_steps, grads[k], accs[k], call_id=agent._noise_calls,
-                                      aux_stream=None if aux_streams is None else aux_streams[k])
-            if (t + 1) % accum_steps == 0:
-                optimizer_step()
-        if (t + 1) % accum_steps != 0:
-            optimizer_step()
-        for k in range(groups):
-            main.wait_event(streams[k].record_event())
-        acc = torch.stack(accs).sum(0)
-        d = _epoch_stats(_epoch_reduce(acc, "ft_step", optimizer), timesteps, n_global)
-        stats.append(d)
-        if rank == 0:
-            log(f"Epoch {epoch}: " + ", ".join(f"{k}: {v:.4f}" for k, v in d.items()))
-    agent.shard_offsets = prior.shard_offsets = (node_lo, lo)
-    return stats

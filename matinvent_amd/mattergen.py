@@ -137,7 +137,7 @@ class ChemGraphLoader:
 
 
 # ---- denoiser ---------------------------------------------------------------------------------------------------------------------
-# atoms per chunk of the fine-tune loop (finetune._ft_step_module_surface): the training forward keeps every activation for the
+# atoms per chunk of the fine-tune loop (finetune._surface_chunks): the training forward keeps every activation for the
 # backward (~33 MB per atom at the benchmark sizes, mirrored by the gradient arena, plus the frozen prior's workspace)
 FT_CHUNK_ATOMS = 1280
 
@@ -432,7 +432,7 @@ class MatterGenModule(nn.Module):
 
     def predict(self, noised_input):
         """The model output alone (pl_module.py:73) -- library kernels only, no torch arithmetic: the part of calc_sample_loss that may
-        run on a side stream beside another network's forward (finetune._ft_step_module_surface)."""
+        run on a side stream beside another network's forward (finetune._surface_timestep)."""
         noisy, batch, t = noised_input
         gb = self._batch_for(noisy["counts"])   # THIS module's workspace (agent and prior must not share one)
         return self.decoder(noisy["pos"], noisy["cell"], noisy["atomic_numbers"], t, gb)

@@ -29,24 +29,30 @@ GRAD_STATS = ("applied_steps", "skipped_steps", "clipped_steps", "nonfinite_step
 _W_COEF, _W_COUNTS, _W_LAST_NORM, _W_NORM_MAX, _W_STATS_END, _D_NORM_SUM = 0, 5, 9, 10, 14, 6
 
 
+def cfg_get(cfg, k, default=None):
+    """Entry `k` of a fine-tune config with key or attribute access (a dict, a namespace, a DictConfig); `default` when absent or None."""
+    v = cfg.get(k) if isinstance(cfg, dict) else getattr(cfg, k, None)
+    if v is None and not isinstance(cfg, dict) and hasattr(cfg, "get"):
+        v = cfg.get(k, None)
+    return default if v is None else v
+
+
+def window_closes(done, accum_steps, total):
+    """The optimizer steps once `done` of an epoch's `total` micro-steps are enqueued: at the end of every accumulation window of
+    `accum_steps`, and behind the last micro-step when that leaves a window partly filled (pipeline/mat_invent.py:165-167, :176-177)."""
+    return done % accum_steps == 0 or done == total
+
+
 def clip_options(cfg):
     """The optimizer options of a fine-tune config (key or attribute access): `max_grad_norm` (a number > 0, +inf included; None / absent:
     no clipping) and `skip_nonfinite_steps` (bool; None / absent: False) -> FusedAdam's keyword arguments.  ValueError, naming the key,
     for anything else: a negative number, zero, NaN, a bool or a string as max_grad_norm; a non-bool as skip_nonfinite_steps."""
-    def get(k):
-        if isinstance(cfg, dict):
-            return cfg.get(k)
-        v = getattr(cfg, k, None)
-        return cfg.get(k, None) if v is None and hasattr(cfg, "get") else v
-
-    m = get("max_grad_norm")
+    m = cfg_get(cfg, "max_grad_norm")
     if m is not None:
         if isinstance(m, bool) or not isinstance(m, numbers.Real) or math.isnan(m) or not m > 0:
             raise ValueError(f"max_grad_norm = {m!r}: must be a number > 0 (or None: no clipping)")
         m = float(m)
-    s = get("skip_nonfinite_steps")
-    if s is None:
-        s = False
+    s = cfg_get(cfg, "skip_nonfinite_steps", False)
     if not isinstance(s, bool):
         raise ValueError(f"skip_nonfinite_steps = {s!r}: must be true or false")
     return dict(max_grad_norm=m, skip_nonfinite=s)

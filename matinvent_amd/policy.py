@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from .cspnet import _ptr, _stream
-from .optim import FusedAdam, clip_options, epoch_grad_stats
+from .optim import FusedAdam, cfg_get, clip_options, epoch_grad_stats, window_closes
 
 # clip_range: DDPO's 1e-4 is below the rounding of the re-evaluated lattice log-probability -- at unchanged weights |log rho| reaches 0.12 over a
 # T = 1000 chain of the benchmark network -- so the default is PPO's 0.2, above that measured maximum
@@ -51,15 +51,6 @@ def draw_timesteps(T, B, timesteps, epochs, seed=None):
     return out
 
 
-def _cfg_get(cfg, k, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(k, default)
-    v = getattr(cfg, k, None)
-    if v is None and hasattr(cfg, "get"):
-        v = cfg.get(k, None)
-    return default if v is None else v
-
-
 def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=None):
     """One call of the PPO-clipped policy gradient over every crystal of `rollout` (sampling.Rollout) with rewards [B].
 
@@ -79,14 +70,14 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
     the draws come from 2..S and every time is a step index; with kl_coef > 0 `prior` must be a view on the same grid.  The optimiser
     steps land in the view's base module: they share theta."""
     opt = clip_options(cfg)
-    lr, epochs = float(_cfg_get(cfg, "lr")), int(_cfg_get(cfg, "epochs"))
-    timesteps, accum_steps = int(_cfg_get(cfg, "timesteps")), int(_cfg_get(cfg, "accum_steps"))
-    clip_range = float(_cfg_get(cfg, "clip_range", DEFAULTS["clip_range"]))
-    adv_clip = float(_cfg_get(cfg, "adv_clip", DEFAULTS["adv_clip"]))
-    w = [float(v) for v in _cfg_get(cfg, "logprob_weights", DEFAULTS["logprob_weights"])]
+    lr, epochs = float(cfg_get(cfg, "lr")), int(cfg_get(cfg, "epochs"))
+    timesteps, accum_steps = int(cfg_get(cfg, "timesteps")), int(cfg_get(cfg, "accum_steps"))
+    clip_range = float(cfg_get(cfg, "clip_range", DEFAULTS["clip_range"]))
+    adv_clip = float(cfg_get(cfg, "adv_clip", DEFAULTS["adv_clip"]))
+    w = [float(v) for v in cfg_get(cfg, "logprob_weights", DEFAULTS["logprob_weights"])]
     if len(w) != 3:
         raise ValueError(f"pg_step: logprob_weights needs three values (l, t, x), got {w}")
-    kl_coef = float(_cfg_get(cfg, "kl_coef", DEFAULTS["kl_coef"]))
+    kl_coef = float(cfg_get(cfg, "kl_coef", DEFAULTS["kl_coef"]))
     if not kl_coef >= 0.0:
         raise ValueError(f"pg_step: kl_coef = {kl_coef}: must be >= 0")
     if kl_coef > 0.0 and prior is None:
@@ -140,12 +131,9 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
         t_dev = torch.from_numpy(t_host).to(dev)                                   # one upload per epoch: [K, B]
         for k in range(K):
             micro_step(t_host[k], t_dev[k])
-            if (k + 1) % accum_steps == 0:
+            if window_closes(k + 1, accum_steps, K):
                 optimizer.step()
                 optimizer.zero_grad(set_to_none=False)
-        if K % accum_steps:
-            optimizer.step()
-            optimizer.zero_grad(set_to_none=False)
         s = stats.sum(dim=1) / max(1, K * B)
         if optimizer.guarded:                                                      # (the optimiser's statistics ride in the same transfer)
             s = torch.cat([s.double(), optimizer.grad_stats(reset=True)])
