@@ -186,8 +186,18 @@ STRIDE_SIGNATURES = {
     "mi_batch_set_time_map": (_I, [_P, C.POINTER(_I), _I]),
 }
 
+# the conditioning extension, include/matinvent_hip_cond.h (replacement conditioning of the reverse chain: a batch handle's known part)
+class Condition(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("known_types_host", "known_coords_host", "known_lattice_host", "types0_host", "frac0_host", "lat0_host")]
+
+
+COND_SIGNATURES = {
+    "mi_batch_set_condition": (_I, [_P, C.POINTER(Condition), C.POINTER(C.c_float), _I]),
+    "mi_condition_apply": (_I, [_P, _I, _U64, _P, _P, _P, _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
-EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES)
+EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES)
 
 _lib = None
 

@@ -182,6 +182,8 @@ enum : uint32_t {
     DRAW_X_T = 0, DRAW_L_T = 1, DRAW_T_T = 2,
     DRAW_CORR_X = 3, DRAW_PRED_L = 4, DRAW_PRED_T = 5, DRAW_PRED_X = 6,
     DRAW_FT_L = 7, DRAW_FT_X = 8, DRAW_FT_T = 9,
+    // (10 .. 20: the MatterGen-shaped path, gemnet.hip)
+    DRAW_COND_L = 21, DRAW_COND_X = 22, DRAW_COND_T = 23,   // replacement conditioning (condition.hip); step field = the noise level
 };
 
 }  // namespace mi

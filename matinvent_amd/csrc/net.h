@@ -211,6 +211,13 @@ struct mi_batch {
     int* time_map_buf = nullptr;   // its allocation (kept when the map is cleared)
     int time_map_cap = 0;
     std::vector<int> time_map_h;   // host copy: length checks, comparison between handles
+    // replacement conditioning (condition.hip, mi_batch_set_condition): masks, clean values and the level table on the device
+    bool cond_on = false;          // a condition is attached (mi_sampler_run imposes it; false: the chain's launches are those of before)
+    bool cond_any = false;         // ... and at least one element is known (nothing known: no launch)
+    int cond_levels = 0;           // rows of cond_table (= T + 1 of the chains it is for)
+    int cond_table_cap = 0;
+    int *cond_kt = nullptr, *cond_kx = nullptr, *cond_kl = nullptr, *cond_types0 = nullptr;   // [N], [N], [B], [N] (allocated on first use)
+    float *cond_frac0 = nullptr, *cond_lat0 = nullptr, *cond_table = nullptr;                  // [N][3], [B][9], [cond_levels][3]
     std::vector<void*> allocs;
 };
 
@@ -255,6 +262,11 @@ int node_chain(mi_net* net, mi_batch* b, int l, hipStream_t s, bool train = fals
 int time_embedding_mapped(const mi_batch* b, const int* steps, int k_all, const float* freqs, int B, int TD, float* out, hipStream_t s);
 int time_map_check(const mi_batch* b, int T, const char* what);
 int time_map_same(const mi_batch* p, const mi_batch* q, const char* what);
+// condition.hip: mi_sampler_run's host-side check of the handle's condition (MI_EINVAL with the message set) and the imposition at `level`
+// (one launch; rec_*: the record slices of that level, or NULL)
+int condition_check(const mi_batch* b, int T, const char* what);
+int condition_impose(const mi_batch* b, int level, uint64_t seed, float* atom_types, float* frac, float* lattices, float* rec_types, float* rec_frac,
+                     float* rec_lat, hipStream_t s);
 extern int g_knn_nosync;
 int knn_build(mi_batch* b, const float* frac, const float* lattices, hipStream_t s, bool nosync = false);
 }  // namespace mi

@@ -236,6 +236,7 @@ int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int 
     MI_CHECK(T >= 1 && t_start <= T && t_stop >= 0 && t_stop <= t_start, MI_EINVAL, "bad step range T=%d start=%d stop=%d", T,
              t_start, t_stop);
     MI_TRY(time_map_check(b, T, "the batch handle"));
+    MI_TRY(condition_check(b, T, "the batch handle"));
     hipStream_t s = (hipStream_t)stream;
     const int N = b->N, B = b->B;
     if (N == 0 || B == 0) return MI_OK;
@@ -255,6 +256,8 @@ int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int 
 
     const size_t n3 = (size_t)N * 3, nA = (size_t)N * MI_NUM_TYPES, b9 = (size_t)B * 9;
     hipLaunchKernelGGL(wrap_inplace_kernel, dim3(cdiv(n3, 256)), dim3(256), 0, s, frac, (int64_t)n3);
+    // replacement conditioning (condition.hip): the known part of the state at the level the chain starts from, before it is recorded
+    if (b->cond_on) MI_TRY(condition_impose(b, t_start, seed, atom_types, frac, lattices, nullptr, nullptr, nullptr, s));
     if (rec) {  // traj[t_start] = current state (diffusion.py:287-293)
         if (rec->atom_types) MI_HIP(hipMemcpyAsync(rec->atom_types + t_start * nA, atom_types, nA * 4, hipMemcpyDeviceToDevice, s));
         if (rec->lattices) MI_HIP(hipMemcpyAsync(rec->lattices + t_start * b9, lattices, b9 * 4, hipMemcpyDeviceToDevice, s));
@@ -312,6 +315,8 @@ int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int 
         a.keep_coords = b->keep_coords;
         hipLaunchKernelGGL(predictor_kernel, dim3(B), dim3(256), 0, s, a);
         MI_KERNEL_CHECK();
+        // ... and at the level the step arrived at: the known elements of the state and of its record are overwritten (the corrector is left alone)
+        if (b->cond_on) MI_TRY(condition_impose(b, t - 1, seed, atom_types, frac, lattices, a.rec_types, a.rec_frac, a.rec_lat, s));
     }
     return MI_OK;
 }

@@ -5,6 +5,7 @@ same buffers (`beta_scheduler.*`, `sigma_scheduler.*`), same methods
 `sample / add_noise / calc_sample_loss / calc_kl_reg`, same `decoder.*` parameter names in
 `state_dict()`.  The arithmetic runs in libmatinvent_hip.so; there is no PyTorch fallback.
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -278,7 +279,7 @@ class DiffCSPModule(nn.Module):
         pair.calls += 1   # every call overwrites what the pair holds: a pending backward of an earlier call must refuse (TrajLogProbFunction)
         return pair
 
-    def forward_logprb(self, state, step_lr=1e-5):
+    def forward_logprb(self, state, step_lr=1e-5, condition=None):
         """DiffCSPModule.forward_logprb (diffusion.py:158-227): re-evaluate one recorded step -- the corrector's network evaluation on
         (atom_types, frac_coords, lattices), the predictor's on frac_coords_mid -- under the current weights.  Returns
         (log_prob_l, log_prob_t, log_prob_x, (pred_l_corr, pred_x_corr, pred_t_corr)) like the reference, differentiable with respect
@@ -288,7 +289,10 @@ class DiffCSPModule(nn.Module):
         for every crystal.  The two agree whenever the timesteps are equal -- the only case sample_mdp produces.  t must lie in 2..T
         (ValueError otherwise; the reference's formulas give inf / NaN at t = 1).  One pending backward per atom-count vector: a later
         call with the same atom counts overwrites the tapes, and the earlier call's backward then raises instead of returning wrong
-        gradients."""
+        gradients.  A `condition` is refused (ValueError): the log-probability of a conditioned transition is not modelled."""
+        if condition is not None:
+            raise ValueError("forward_logprb: a condition is not supported -- the recorded log-probabilities of a conditioned chain are those "
+                             "of the unconditioned proposal, not a trajectory likelihood")
         for k, v in state.items():   # (the reference moves the caller's tensors to the device in place, :159-160)
             state[k] = v.to(self.device)
         dev = self.device
@@ -350,7 +354,7 @@ class DiffCSPModule(nn.Module):
 
     @torch.no_grad()
     def sample(self, batch, diff_ratio=1.0, step_lr=1e-5, seed=0, noise=None, init=None, record=False, t_start=None,
-               t_stop=0, node_offset=0, graph_offset=0, streams=None, rec_sink=None):
+               t_stop=0, node_offset=0, graph_offset=0, streams=None, rec_sink=None, condition=None):
         """DiffCSPModule.sample (diffusion.py:273-399).
 
         `rec_sink` (a list; with record=True): receives one (first crystal, first atom, buffers) per chain, in crystal order -- the
@@ -364,12 +368,23 @@ class DiffCSPModule(nn.Module):
 
         On a strided view (`respaced`) T is the view's S and t_start / t_stop / the keys of `traj` / the first index of `noise` and of the
         record buffers are step indices 0..S; the counter-based noise is keyed by step index (initial draw: S + 1).
+
+        `condition` (conditioning.Condition for the crystals of `batch`; it may BE `batch`): replacement conditioning.  The known
+        atom types / coordinates / lattices are overwritten at the start and after every step with a forward-noised copy of their clean
+        values at the level the chain has reached (on a view: the step index, through the view's tables), and are exact at t_stop = 0.  The
+        condition is attached to the chain's batch handles for this call and cleared afterwards (one device synchronisation before the
+        call's first launch, none inside the chain).  With record=True the CONDITIONED states are recorded; the recorded log-probabilities
+        are then those of the unconditioned proposal of each step -- not a trajectory likelihood, which is why sample_mdp, sample_rollout
+        and forward_logprb refuse a condition.  CSP mode together with a condition is refused by the library (MI_EINVAL).
         """
+        if condition is not None and [int(v) for v in condition.num_atoms.tolist()] != [int(v) for v in batch.num_atoms.tolist()]:
+            raise ValueError("sample: the condition's atom counts are not the batch's")
         if self.__dict__.get("_knn_pending"):
             self.check_graph()   # (the verdict of the previous call's chains: by now they have long finished)
         if isinstance(batch, CrystalBatch):
-            return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink)
-        if (self.keep_lattice or self.keep_coords) and init is None:
+            return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink,
+                                    condition=condition)
+        if (self.keep_lattice or self.keep_coords) and init is None and condition is None:
             # CSP mode (diffusion.py:283-287): the known part of the structure replaces the drawn initial state and is never moved
             cb0 = self.crystal_batch(batch, node_offset, graph_offset)
             dev = self.device
@@ -390,7 +405,8 @@ class DiffCSPModule(nn.Module):
             streams = 4 if e_total >= 98304 else 3 if e_total >= 49152 else 2 if e_total >= 16384 else 1
         streams = max(1, min(int(streams), len(na)))
         if streams == 1:
-            return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink)
+            return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink,
+                                    condition=condition)
         key = ("split", streams, tuple(na))
         parts = getattr(batch, "_mi_split", {}).get(key)
         if parts is None:  # contiguous crystal groups, cached on the batch object like its CrystalBatch
@@ -434,7 +450,12 @@ class DiffCSPModule(nn.Module):
             cur.wait_event(stream.record_event())
             return r
 
-        out = workers.run(run, streams)
+        # a condition is attached here, to every group's handle before the first chain is enqueued (the blocking copies do not wait between
+        # the chains), and cleared when all of them are: each group gets its crystals' slice
+        conds = [] if condition is None else [(self.crystal_batch(parts[k], node_offset + n0[k], graph_offset + g0[k]), condition.slice(g0[k], g0[k + 1]))
+                                              for k in range(streams)]
+        with self._conditioned(conds):
+            out = workers.run(run, streams)
         if rec_sink is not None:
             for k, sk in enumerate(sinks):
                 for _, _, bufs in sk:
@@ -476,8 +497,26 @@ class DiffCSPModule(nn.Module):
         for cb, stream in pending:
             _lib.check(lib.mi_knn_graph_status(cb._h, C.c_void_p(stream.cuda_stream)), "mi_knn_graph_status")
 
+    @contextlib.contextmanager
+    def _conditioned(self, pairs):
+        """Attach each (batch handle, Condition) of `pairs` for the duration of the block and clear the handles afterwards, whatever happens
+        inside: the cached handles of `crystal_batch` must not carry a condition into a later call.  The device is drained once first --
+        an earlier chain of a cached handle may still be reading the arrays the attach overwrites."""
+        if not pairs:
+            yield
+            return
+        from .conditioning import Condition
+        torch.cuda.synchronize(self.device)
+        try:
+            for cb, c in pairs:
+                c.attach(self, cb)
+            yield
+        finally:
+            for cb, _ in pairs:
+                Condition.clear(cb)
+
     def _sample_one(self, batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, inplace=None, drawn=False,
-                    rec_sink=None):
+                    rec_sink=None, condition=None):
         """One chain over one CrystalBatch on the current stream.
 
         Returns (traj[t_stop], traj) like the reference.  `traj` holds every step only when
@@ -520,10 +559,11 @@ class DiffCSPModule(nn.Module):
                          frac_coords_mid=z(T + 1, N, 3), log_prob_l=z(T + 1, B), log_prob_t=z(T + 1, B), log_prob_x=z(T + 1, B))
             rec = _lib.SamplerRecord(*(rec_t[k].data_ptr() for k in ("atom_types", "frac_coords", "lattices", "frac_coords_mid",
                                                                      "log_prob_l", "log_prob_t", "log_prob_x")))
-        _lib.check(lib.mi_sampler_run(self.decoder._h, cb._h, coef.numpy().ctypes.data_as(C.POINTER(C.c_float)), T, t_start, t_stop,
-                                      _ptr(self.time_embedding.freqs), seed, C.byref(nz) if nz is not None else None,
-                                      C.byref(rec) if rec is not None else None, _ptr(a), _ptr(x), _ptr(l), _stream()),
-                   "mi_sampler_run")
+        with self._conditioned([] if condition is None else [(cb, condition)]):
+            _lib.check(lib.mi_sampler_run(self.decoder._h, cb._h, coef.numpy().ctypes.data_as(C.POINTER(C.c_float)), T, t_start, t_stop,
+                                          _ptr(self.time_embedding.freqs), seed, C.byref(nz) if nz is not None else None,
+                                          C.byref(rec) if rec is not None else None, _ptr(a), _ptr(x), _ptr(l), _stream()),
+                       "mi_sampler_run")
         if cb.edge_style == "knn":
             # the chain rebuilt its periodic neighbour list in every evaluation WITHOUT a host round trip (the reference synchronises per evaluation:
             # cspnet.py:243-257); a list over capacity could not raise inside the enqueued chain -- its verdict waits on the batch handle for check_graph()

@@ -73,7 +73,9 @@ class MatInvent(ReinL):
 
     def sample_step(self):
         """mat_invent.py:74-123: sample, geometric validity pre-filter (device-side quantities), save the valid set as
-        extxyz, optional filter callable, max_num.  MLIP relaxation / SUN metrics are out of scope."""
+        extxyz, optional filter callable, max_num.  MLIP relaxation / SUN metrics are out of scope.
+        sample_cfg.target_compositions_dict (a list of {symbol: count}) reaches the sampler with the other keys: the loop then samples
+        crystals of those formulas only (replacement conditioning) and fine-tunes on them -- a fixed-formula RL loop."""
         rank, world = rank_world()
         kw = {k: v for k, v in self.sample_cfg.items() if k not in ("filter", "mlip_opt", "geometric_filter")}
         if self.sample_steps is not None:   # (the sampler builds the agent's strided view; ft_step stays on the agent and its trained grid)
@@ -171,7 +173,8 @@ class MatInventPG(MatInvent):
     crystal.  On-policy: there is no top-k and no replay (a stored crystal's log-probabilities belong to weights that no longer exist),
     so replay=True is refused.  Single GPU, DiffCSP only (MatterGen has no log-probability path), one sampling batch per loop.
     finetune_cfg.kl_coef > 0 anchors the agent's transitions to the frozen prior's (policy.pg_step) and logs prior_kl.
-    sample_cfg.sample_steps = S: rollout and training run through strided views of agent and prior and `rollout steps` is logged."""
+    sample_cfg.sample_steps = S: rollout and training run through strided views of agent and prior and `rollout steps` is logged.
+    sample_cfg.target_compositions_dict / condition (conditioned sampling) are refused: MatInvent has them."""
 
     def __init__(self, rl_epoch, model_suite, reward, sample_cfg, finetune_cfg, save_dir, save_freq=50, device=None, logger=None,
                  replay=False, replay_args=None, topk_ratio=1.0, **kwargs):
@@ -183,7 +186,12 @@ class MatInventPG(MatInvent):
             raise ValueError("MatInventPG needs the DiffCSP suite: the MatterGen suite has no trajectory log-probability path")
         if rank_world()[1] > 1:
             raise ValueError("MatInventPG runs on one GPU: world_size > 1 is not supported")
-        nb = C.merge(model_suite.sample_cfg, sample_cfg).get("num_batches", 1)
+        merged = C.merge(model_suite.sample_cfg, sample_cfg)
+        for k in ("target_compositions_dict", "condition"):
+            if merged.get(k) is not None:
+                raise ValueError(f"MatInventPG: sample_cfg.{k} is not supported -- a conditioned chain's recorded log-probabilities are those "
+                                 "of the unconditioned proposal, not a trajectory likelihood (use pipeline=mat_invent)")
+        nb = merged.get("num_batches", 1)
         if int(nb or 1) != 1:
             raise ValueError(f"MatInventPG samples one batch per loop: num_batches = {nb} is not supported")
         super().__init__(rl_epoch=rl_epoch, model_suite=model_suite, reward=reward, sample_cfg=sample_cfg, finetune_cfg=finetune_cfg,

@@ -41,21 +41,42 @@ class DiffCSPSampler:
     num_atoms_distribution: str = "mp_20"
     seed: int = 0
 
-    def generate(self, model, batch_size=None, num_batches=None, sample_steps=None, **kwargs) -> Tuple[List[CrystalData], list]:
+    def generate(self, model, batch_size=None, num_batches=None, sample_steps=None, condition=None, target_compositions_dict=None,
+                 **kwargs) -> Tuple[List[CrystalData], list]:
         """sample.py:148-201.  Extra kwargs (`max_num`, `filter`, ...) are tolerated like the reference.
         `sample_steps` = S: the chains run on S of the model's T trained steps (model.respaced(S)); None: all of them.
         As in the reference, every batch is sampled but only the LAST batch's outputs are unpacked
         (sample.py:166-177).  `rank`/`world_size` kwargs shard the batch by crystal (DP): each rank
-        samples a contiguous block with global noise offsets and the records are all-gathered."""
+        samples a contiguous block with global noise offsets and the records are all-gathered.
+
+        Conditioned generation (DiffCSPModule.sample's `condition`): `target_compositions_dict` -- this keyword, else the
+        field -- is a list of {symbol: count} mappings; the batch_size x num_batches crystals cycle through it, every atom type is
+        fixed (Condition.composition) and the atom counts come from the compositions instead of the mp_20 draw.  `condition`: an explicit
+        conditioning.Condition for all batch_size x num_batches crystals, or for batch_size of them (then used for every batch)."""
         batch_size = batch_size or self.batch_size
         num_batches = num_batches or self.num_batches
         assert batch_size is not None and num_batches is not None
+        targets = target_compositions_dict if target_compositions_dict is not None else self.target_compositions_dict
+        if targets is not None and len(targets) == 0:
+            targets = None
+        if targets is not None:
+            if condition is not None:
+                raise ValueError("DiffCSPSampler.generate: give target_compositions_dict or condition, not both")
+            from .conditioning import Condition
+            condition = Condition.composition(list(targets), batch_size * num_batches)
+        elif condition is not None and len(condition) not in (batch_size, batch_size * num_batches):
+            raise ValueError(f"DiffCSPSampler.generate: the condition covers {len(condition)} crystals, not batch_size = {batch_size} or "
+                             f"batch_size x num_batches = {batch_size * num_batches}")
         rank, world = int(kwargs.get("rank", 0)), int(kwargs.get("world_size", 1))
         model = _strided(model, sample_steps)
         model.eval()
-        dataset = SampleDataset(total_num=batch_size * num_batches, dataset=self.num_atoms_distribution)
         from .dist import collectives_on
-        if world > 1 or collectives_on():
+        if condition is not None:   # the atom counts are the condition's: nothing is drawn, so every rank holds the same vector
+            from types import SimpleNamespace
+            dataset = SimpleNamespace(num_atoms=np.tile(condition.num_atoms.numpy(), batch_size * num_batches // len(condition)))
+        else:
+            dataset = SampleDataset(total_num=batch_size * num_batches, dataset=self.num_atoms_distribution)
+        if condition is None and (world > 1 or collectives_on()):
             # the atom counts come from numpy's unseeded GLOBAL generator (sample.py:123): every rank would draw a different
             # vector, while the shard ranges and the global noise offsets below assume ONE.  Rank 0's draw is the batch.
             from .dist import broadcast_object
@@ -69,7 +90,11 @@ class DiffCSPSampler:
             node_off = int(np.sum(na[:lo]))
             self.seed += 1
             counts = _AtomCounts(na[lo:hi])
-            outputs, _ = model.sample(counts, step_lr=step_lr, seed=self.seed, node_offset=node_off, graph_offset=lo)
+            cond = None
+            if condition is not None:
+                c0 = bi * batch_size % len(condition)
+                cond = condition.slice(c0 + lo, c0 + hi)
+            outputs, _ = model.sample(counts, step_lr=step_lr, seed=self.seed, node_offset=node_off, graph_offset=lo, condition=cond)
         data_list = _unpack(model, counts, outputs, node_off, lo, where="DiffCSPSampler.generate")
         struc_list = [data2struc(d) for d in data_list]
         if world > 1 or collectives_on():
@@ -133,15 +158,22 @@ def sample_loop(sample_size, model, device=None, step_lr=-1, seed=None):
     return _unpack(model, counts, outputs)
 
 
-def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_steps=None):
+def _refuse_condition(where, condition):
+    if condition is not None:
+        raise ValueError(f"{where}: a condition is not supported -- a conditioned chain's recorded log-probabilities are those of the "
+                         "unconditioned proposal, not a trajectory likelihood (DESIGN 31)")
+
+
+def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_steps=None, condition=None):
     """sample.py:249-309: sample with the trajectory recorded and return (sample_list, sample_traj), restricted to the crystals that
     pass invalid_filter.  sample_traj[k] is the step t = T - k (t = T .. 2) with the reference's keys (atom_types, lattices, frac_coords,
     frac_coords_mid, num_atoms, timesteps, log_prob_{t,x,l}; host tensors) plus next_frac_coords / next_lattices / next_atom_types --
     the state at t - 1 -- so that any element can go straight to DiffCSPModule.forward_logprb.  (The reference's own sample_mdp unpacks
     invalid_filter into the wrong values and never builds the next_* keys that forward_logprb reads.)
     A strided view (DiffCSPModule.respaced), or sample_steps = S which builds it: T is the view's S and `timesteps` are step indices --
-    what the VIEW's forward_logprb takes."""
+    what the VIEW's forward_logprb takes.  A `condition` is refused (ValueError)."""
     from .filters import invalid_filter
+    _refuse_condition("sample_mdp", condition)
     model = _strided(model, sample_steps)
     counts, step_lr = _prelude(sample_size, model, step_lr)
     outputs, traj = model.sample(counts, step_lr=step_lr, seed=_draw_seed(seed), record=True)
@@ -208,14 +240,16 @@ class Rollout:
                        torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(na, 0)]), self.T, self.step_lr)
 
 
-def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=True, sample_steps=None):
+def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=True, sample_steps=None, condition=None):
     """Sample like sample_mdp (same atom-count draw, seed handling and invalid_filter; geometric_filter=False keeps every crystal) and
     keep the kept crystals' whole trajectories on the device as a Rollout -- compacted once per chain straight from the sampler's stacked
     record buffers, without the per-step dict or a host copy.  Returns (sample_list, rollout).  The policy gradient (policy.pg_step)
     consumes it.  CSP mode (keep_lattice / keep_coords) is refused: forward_logprb does not model it.
     A strided view (DiffCSPModule.respaced), or sample_steps = S which builds it: rollout.T = S, the arrays are [S + 1, ...] and index k is
-    the state at step index k (trained time tau_k); pg_step then takes the same view as its agent."""
+    the state at step index k (trained time tau_k); pg_step then takes the same view as its agent.  A `condition` is refused (ValueError),
+    like CSP mode."""
     from .filters import invalid_filter
+    _refuse_condition("sample_rollout", condition)
     model = _strided(model, sample_steps)
     if getattr(model, "keep_lattice", False) or getattr(model, "keep_coords", False):
         raise ValueError("sample_rollout: CSP mode (keep_lattice / keep_coords) is not supported -- forward_logprb does not model a given "
