@@ -1,2 +1,1 @@
 from matinvent_amd.memory import LongTimeMem  # noqa: F401
-from matinvent_amd.pipeline import MatInvent  # noqa: F401

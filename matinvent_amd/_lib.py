@@ -196,8 +196,21 @@ COND_SIGNATURES = {
     "mi_condition_apply": (_I, [_P, _I, _U64, _P, _P, _P, _P]),
 }
 
+# the structure-fingerprint extension, include/matinvent_hip_fp.h (the key of the structure-resolved long-term memory and replay buffer)
+class FpParams(C.Structure):
+    _fields_ = [("r_max", C.c_float), ("sigma", C.c_float), ("nbins", C.c_int)]
+
+
+FP_MAX_SPECIES, FP_MAX_BLOCKS, FP_MAX_BINS, FP_MAX_REACH, FP_CUT = 8, 36, 64, 16, 6.0   # include/matinvent_hip_fp.h
+FP_OK, FP_SPECIES, FP_NONFINITE, FP_VOLUME, FP_REACH, FP_ATOMS = 0, 1, 2, 3, 4, 5
+
+FP_SIGNATURES = {
+    "mi_structure_fingerprint_offsets": (_I, [_P, _I, _P, _P, _P, C.POINTER(FpParams), _P, _P, _P]),
+    "mi_structure_fingerprint": (_I, [_P, _P, _P, _P, C.POINTER(FpParams), _P, _P, _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
-EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES)
+EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES)
 
 _lib = None
 

@@ -1,7 +1,8 @@
 """RL pipelines with the reference's class names, constructor arguments and method surface
 (pipeline/base.py:27-136 ReinL, pipeline/mat_invent.py:17-290 MatInvent, pipeline/baseline.py Baseline).
-Sampling and fine-tuning run on the HIP path; scoring, filtering and memory are the caller's plug-ins
-(rewards / filters are out of scope and optional here)."""
+Sampling and fine-tuning run on the HIP path; scoring and filtering are the caller's plug-ins (rewards / filters are out of scope and
+optional here); the long-term memory and its diversity filter are memory.LongTimeMem, by formula as in the reference or by structure
+(DESIGN 32)."""
 import logging
 import os
 import time
@@ -13,7 +14,7 @@ from . import config as C
 from .dist import broadcast_object, rank_world
 from .filters import invalid_filter
 from .finetune import ft_step as _ft_step
-from .memory import ReplayBuffer
+from .memory import LongTimeMem, ReplayBuffer
 from .structure import write_extxyz
 from .suite import get_device
 
@@ -38,6 +39,7 @@ class ReinL:
         os.makedirs(self.models_dir, exist_ok=True)
         os.makedirs(self.sample_dir, exist_ok=True)
         self.replay = ReplayBuffer(**(replay_args or {})) if replay else None
+        self.ltm = LongTimeMem()   # base.py:64
 
     def reward_step(self, sample_data, sample_struc, xyz_path=None, label="tmp"):
         """base.py:98-127: score, drop failed samples."""
@@ -57,7 +59,14 @@ class MatInvent(ReinL):
                          **kwargs)
         assert 0.0 < topk_ratio <= 1.0
         self.topk_ratio = topk_ratio
-        self.div_filter = div_filter  # the LTM diversity filter is out of scope; ignored
+        self.div_filter = bool(div_filter)
+        self.df_args = dict(df_args or {})   # tol, buff, method ("composition" | "element_comb" | "structure"), fp_tol: LongTimeMem.div_filter's
+        fp_args = self.df_args.pop("fp_args", None)   # r_max / nbins / sigma of the fingerprint, for the memory's clustering
+        by_structure = self.replay is not None and self.replay.key == "structure"
+        if self.df_args.get("method") == "structure" or by_structure:   # the memory clusters its rows by fingerprint as they come in (rank 0)
+            fp_tol = self.df_args.get("fp_tol", self.replay.fp_tol if by_structure else None)
+            self.ltm = LongTimeMem(structure=True, fp_args=dict(fp_args or (self.replay.fp_args if by_structure else {})),
+                                   **({} if fp_tol is None else {"fp_tol": fp_tol}))
         self.load_model()
 
     def load_model(self):
@@ -118,12 +127,29 @@ class MatInvent(ReinL):
             data, strucs, rewards, props = self.reward_step(data, strucs, xyz, f"step_{self.step:0>4d}")
             log = {f"{k} mean": v.mean() for k, v in props.items()}
             log.update({"reward mean": rewards.mean(), "reward std": rewards.std(), "cost": self.cost}, **metrics)
+            # long-term memory (mat_invent.py:209-226): bookkeeping and five log keys, whether or not the filter is on
+            self.ltm.extend(strucs, rewards, self.step)
+            thred = getattr(self.reward, "threshold", getattr(self.reward, "reward_threshold", 0.0))
+            burden, div_ratio = self.ltm.calc_metrics(thred)
+            self.ltm.save(os.path.join(self.sample_dir, "long_term_memory.csv"))
+            logging.info(f"{len(self.ltm)} crystals generated so far, {len(self.ltm.unique_comps)} unique components.  Burden: {burden}, "
+                         f"Div. Ratio: {div_ratio}.")
+            log.update({"crystal_num": len(self.ltm), "unique_comps": len(self.ltm.unique_comps), "burden": burden, "div_ratio": div_ratio})
+            if self.ltm.structure:
+                log["unique_structures"] = self.ltm.unique_structures
             if self.logger is not None:
                 self.logger.log(log, step=self.step)
+            penalty_strucs = []
+            if self.div_filter:   # (mat_invent.py:230-237: the penalised rewards rank the top-k)
+                rewards, penalty_idx, tol_n, buff_n = self.ltm.div_filter(strucs, rewards, **self.df_args)
+                penalty_strucs = [strucs[p] for p in penalty_idx]
+                logging.info(f"Diversity filter: tol_n={tol_n}, buff_n={buff_n}")
             order = np.argsort(rewards)[::-1]
             topk = order[: int(self.finetune_cfg.batch_size * self.topk_ratio)]
             ft_data, ft_reward = [data[i] for i in topk], rewards[topk]
             if self.replay is not None:
+                if penalty_strucs:
+                    self.replay.memory_purge(penalty_strucs)
                 rd, rr = self.replay.sample()
                 self.replay.extend(ft_data, None, ft_reward)
                 ft_data, ft_reward = ft_data + rd, np.concatenate((ft_reward, rr))
@@ -191,6 +217,9 @@ class MatInventPG(MatInvent):
             if merged.get(k) is not None:
                 raise ValueError(f"MatInventPG: sample_cfg.{k} is not supported -- a conditioned chain's recorded log-probabilities are those "
                                  "of the unconditioned proposal, not a trajectory likelihood (use pipeline=mat_invent)")
+        if kwargs.get("div_filter"):
+            raise ValueError("MatInventPG: div_filter=True is not built -- the diversity filter penalises the rewards that rank a top-k, and the "
+                             "policy gradient has no top-k (use pipeline=mat_invent)")
         nb = merged.get("num_batches", 1)
         if int(nb or 1) != 1:
             raise ValueError(f"MatInventPG samples one batch per loop: num_batches = {nb} is not supported")

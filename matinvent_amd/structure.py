@@ -9,6 +9,8 @@ What the reference gets from pymatgen / ase on the sampler -> filter -> reward h
   * `lattice_matrix` (pymatgen `Lattice.from_parameters` orientation), `volume`, `density`, `composition`,
     `reduced_formula` -- the keys memory/replay_buffer.py:38 and memory/ltm.py:31 dedupe on;
   * `write_extxyz` / `write_cif` -- pipeline/utils/save.py:32-41 writes extxyz through ase.
+  * `fingerprints`: a permutation-, translation-, basis- and supercell-invariant unit vector per crystal (species-resolved Oganov-Valle
+    fingerprint, `mi_structure_fingerprint_offsets`) and `fingerprint_distance`, the key of the structure-resolved memories.
 """
 import ctypes as C
 import math
@@ -96,8 +98,8 @@ def write_extxyz(structures, path: str, infos: List[dict] = None) -> str:
     return path
 
 
-def write_cif(structure, path: str, name: str = "generated") -> str:
-    """Minimal P1 CIF (cell parameters + fractional sites)."""
+def cif_text(structure, name: str = "generated") -> str:
+    """Minimal P1 CIF (cell parameters + fractional sites) as a string."""
     lengths, angles, species, frac = _fields(structure)
     lines = [f"data_{name}", "_symmetry_space_group_name_H-M   'P 1'", "_symmetry_Int_Tables_number   1",
              f"_cell_length_a   {lengths[0]:.6f}", f"_cell_length_b   {lengths[1]:.6f}", f"_cell_length_c   {lengths[2]:.6f}",
@@ -107,8 +109,12 @@ def write_cif(structure, path: str, name: str = "generated") -> str:
              " _atom_site_occupancy"]
     for k, (z, p) in enumerate(zip(species, frac)):
         lines.append(f"  {SYMBOLS[z]}  {SYMBOLS[z]}{k}  {p[0] % 1.0:.8f}  {p[1] % 1.0:.8f}  {p[2] % 1.0:.8f}  1")
+    return "\n".join(lines) + "\n"
+
+
+def write_cif(structure, path: str, name: str = "generated") -> str:
     with open(path, "w") as f:
-        f.write("\n".join(lines) + "\n")
+        f.write(cif_text(structure, name))
     return path
 
 
@@ -143,3 +149,68 @@ def check_structures_counts(num_atoms: torch.Tensor, frac_coords: torch.Tensor, 
 def geometric_mask(check: torch.Tensor, max_cell: float = 25.0, min_dist: float = 0.5, min_volume: float = 0.1) -> torch.Tensor:
     """max(abc) < 25 (opt_filter.py:53-55) and the distance / volume thresholds of `structure_validity`."""
     return (check[:, 0] < max_cell) & (check[:, 1] > min_dist) & (check[:, 2] > min_volume)
+
+
+# ---- structure fingerprints (DESIGN 32) ---------------------------------------------------------------------------------------------------
+FP_R_MAX, FP_NBINS, FP_SIGMA = 8.0, 64, 0.15
+FP_TOL = 0.02   # default cluster radius of the structure-resolved memories (cosine distance; measured in DESIGN 32)
+
+
+def fingerprints(num_atoms: torch.Tensor, atom_types: torch.Tensor, frac_coords: torch.Tensor, lattices: torch.Tensor, r_max: float = FP_R_MAX,
+                 nbins: int = FP_NBINS, sigma: float = FP_SIGMA):
+    """(fp [B, 36 nbins], info [B, 4]) on the device for a batch described by its atom counts: per crystal the unit fingerprint row and
+    (species count, status, norm before normalisation, translations visited).  A crystal whose status is not 0 (_lib.FP_*: more than 8
+    species, a non-finite entry, volume below 0.1 A^3, a collapsed cell, no or unknown atoms) has a zero row."""
+    from . import _lib
+    lib = _lib.load()
+    fr, lat = frac_coords.detach().float().contiguous(), lattices.detach().float().contiguous()
+    assert fr.is_cuda and lat.is_cuda
+    types = atom_types.detach().to(device=fr.device, dtype=torch.int32).contiguous()
+    B = len(num_atoms)
+    off = torch.zeros(B + 1, dtype=torch.int32, device=fr.device)
+    off[1:] = torch.cumsum(num_atoms.to(fr.device), 0)
+    if types.numel() != fr.numel() // 3 or lat.numel() != 9 * B:
+        raise ValueError(f"fingerprints: {types.numel()} atom types, {fr.numel() // 3} coordinates and {lat.numel() // 9} lattices for {B} crystals")
+    if B and int(num_atoms.sum()) != types.numel():
+        raise ValueError(f"fingerprints: num_atoms sums to {int(num_atoms.sum())}, {types.numel()} atoms given")
+    par = _lib.FpParams(float(r_max), float(sigma), int(nbins))
+    if not 1 <= int(nbins) <= _lib.FP_MAX_BINS:
+        raise ValueError(f"fingerprints: nbins = {nbins} outside 1..{_lib.FP_MAX_BINS}")
+    fp = torch.empty(B, _lib.FP_MAX_BLOCKS * int(nbins), device=fr.device)
+    info = torch.empty(B, 4, device=fr.device)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    _lib.check(lib.mi_structure_fingerprint_offsets(p(off), B, p(types), p(fr), p(lat), C.byref(par), p(fp), p(info),
+                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), "mi_structure_fingerprint_offsets")
+    return fp, info
+
+
+def fingerprint_distance(u1, u2):
+    """d = (1 - u1 . u2) / 2 in [0, 1] between unit fingerprint rows of one species set (numpy arrays or tensors; rows broadcast)."""
+    if torch.is_tensor(u1) or torch.is_tensor(u2):
+        return 0.5 * (1.0 - (torch.as_tensor(u1).double() * torch.as_tensor(u2).double()).sum(-1))
+    return 0.5 * (1.0 - (np.asarray(u1, np.float64) * np.asarray(u2, np.float64)).sum(-1))
+
+
+def record_arrays(records):
+    """(num_atoms [B], atom_types [N], frac_coords [N, 3], lattices [B, 3, 3]) as host tensors from SimpleStructure / CrystalData-like
+    records: what `fingerprints` takes, uploaded once per call by its callers."""
+    na, types, frac, lat = [], [], [], []
+    for r in records:
+        lengths, angles, species, fc = _fields(r)
+        na.append(len(species))
+        types += species
+        frac.append(np.asarray(fc, np.float64).reshape(-1, 3))
+        lat.append(lattice_matrix(lengths, angles))
+    return (torch.tensor(na, dtype=torch.long), torch.tensor(types, dtype=torch.int32),
+            torch.from_numpy(np.concatenate(frac) if frac else np.zeros((0, 3))).float(),
+            torch.from_numpy(np.stack(lat) if lat else np.zeros((0, 3, 3))).float())
+
+
+def record_fingerprints(records, device=None, **kw):
+    """(fp [B, 36 nbins] float32, status [B] int) as numpy arrays for host records: one upload, one kernel, one read-back."""
+    if len(records) == 0:
+        return np.zeros((0, 36 * int(kw.get("nbins", FP_NBINS))), np.float32), np.zeros(0, np.int64)
+    dev = torch.device(device if device is not None else "cuda")
+    na, types, frac, lat = record_arrays(records)
+    fp, info = fingerprints(na, types.to(dev), frac.to(dev), lat.to(dev), **kw)
+    return fp.cpu().numpy(), info[:, 1].cpu().numpy().astype(np.int64)
