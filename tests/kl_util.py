@@ -8,10 +8,11 @@ from oracle import diffcsp_oracle as O
 from tests.traj_util import time_embedding
 
 
-def step_scalars(beta, sigma, sigma_begin, t, step_lr):
-    """Crystal b's step scalars at t[b] (the quantities of tests/traj_util.forward_logprb), float64 [B] each."""
+def step_scalars(beta, sigma, sigma_begin, t, step_lr, dtype=torch.float64):
+    """Crystal b's step scalars at t[b] (the quantities of tests/traj_util.forward_logprb), float64 [B] each.  dtype=torch.float32: the
+    same expressions as separately rounded float32 tensor ops on the float32 tables, as the reference and sampler_coefficients form them."""
     t = torch.as_tensor(t).long()
-    d = lambda v: v.double()
+    d = lambda v: v.to(dtype)
     alphas, alphas_cumprod = d(beta["alphas"][t]), d(beta["alphas_cumprod"][t])
     sx, sn, adj = d(sigma["sigmas"][t]), d(sigma["sigmas_norm"][t]), d(sigma["sigmas"][t - 1])
     step_corr = step_lr * (sx / sigma_begin) ** 2
