@@ -209,8 +209,17 @@ FP_SIGNATURES = {
     "mi_structure_fingerprint": (_I, [_P, _P, _P, _P, C.POINTER(FpParams), _P, _P, _P]),
 }
 
+# the preference extension, include/matinvent_hip_dpo.h (a batch handle's ranked pairs and the Diffusion-DPO micro-step)
+DPO_SIGNATURES = {
+    "mi_batch_set_pairs": (_I, [_P, C.POINTER(_I), C.POINTER(_I), _I]),
+    "mi_batch_num_pairs": (_I, [_P]),
+    "mi_dpo_micro_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, C.c_float, C.c_float, C.c_float, C.c_float, _U64, _U32, _P, _P, _P,
+                               C.c_float, C.c_float, C.c_float, C.c_float, _I, _I, _P, _P, _P, _P, _P, _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
-EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES)
+EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
+                        DPO_SIGNATURES)
 
 _lib = None
 

@@ -98,6 +98,20 @@ class CrystalBatch:
         """grad (flat, the network's theta layout) += the pending micro-steps' node-level weight gradients, on the current stream."""
         _lib.check(self._lib.mi_cspnet_wgrad_flush(net._h, self._h, _ptr(grad), _stream()), "mi_cspnet_wgrad_flush")
 
+    # ---- preference pairs (mi_batch_set_pairs; preference.dpo_step) ----
+    def set_pairs(self, pairs):
+        """Attach the (winner, loser) crystal-index pairs `pairs` ([P, 2]; None or empty: clear them) to the handle: blocking copies, no work
+        of this handle may be in flight.  A bad pair raises MIError (MI_EINVAL) and the handle keeps what it had."""
+        import numpy as np
+        arr = np.zeros((0, 2), dtype=np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2).T, dtype=np.int32)
+        n = 0 if pairs is None else arr.shape[1]
+        ip = lambda row: None if n == 0 else arr[row].ctypes.data_as(C.POINTER(C.c_int))
+        _lib.check(self._lib.mi_batch_set_pairs(self._h, ip(0), ip(1), n), "mi_batch_set_pairs")
+
+    @property
+    def num_pairs(self) -> int:
+        return int(self._lib.mi_batch_num_pairs(self._h))
+
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h is not None and getattr(self, "_lib", None) is not None:

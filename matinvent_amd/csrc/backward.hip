@@ -1510,21 +1510,22 @@ int mi_add_noise_per_crystal(mi_batch* b, const float* lengths, const float* ang
     return MI_OK;
 }
 
-// One fine-tune micro-step; `copies` > 0: stacked timesteps (see mi_ft_micro_steps_stacked), the schedule arrays then hold one value
-// per replica and t / c0 / c1 / sigma_t / sigma_norm are ignored.
-static int ft_micro_impl(mi_net* agent, mi_batch* ab, mi_net* prior, mi_batch* pb, const float* lengths, const float* angles,
-                         const float* frac0, const int* atom_types, const float* reward, const float* time_freqs, int t, float c0, float c1,
-                         float sigma_t, float sigma_norm, int copies, const int* ts, const float* c0s, const float* c1s, const float* sigmas,
-                         const float* sigma_norms, uint64_t seed, uint32_t noise_step, const float* rand_l, const float* rand_x,
-                         const float* rand_t, float cost_lattice, float cost_coord, float cost_type, float kl_sigma, int b_global,
-                         int accum_steps, float* grad_theta, float* stats, float* out_sample_loss, float* out_kl, void* stream,
-                         void* aux_stream) {
-    MI_CHECK(agent && ab && prior && pb && lengths && angles && frac0 && atom_types && reward && time_freqs && grad_theta, MI_EINVAL,
+}  // extern "C"
+
+namespace mi {
+
+// One fine-tune micro-step with the loss stage passed in (net.h: ft_micro_run); `copies` > 0: stacked timesteps (see
+// mi_ft_micro_steps_stacked), the schedule arrays then hold one value per replica and t / c0 / c1 / sigma_t / sigma_norm are ignored.
+int ft_micro_run(const char* what, mi_net* agent, mi_batch* ab, mi_net* prior, mi_batch* pb, const float* lengths, const float* angles,
+                 const float* frac0, const int* atom_types, const float* time_freqs, int t, float c0, float c1, float sigma_t, float sigma_norm,
+                 int copies, const int* ts, const float* c0s, const float* c1s, const float* sigmas, const float* sigma_norms, uint64_t seed,
+                 uint32_t noise_step, const float* rand_l, const float* rand_x, const float* rand_t, float cost_lattice, float cost_coord,
+                 float cost_type, int accum_steps, float* grad_theta, ft_loss_stage_fn stage, void* stage_ctx, void* stream, void* aux_stream) {
+    MI_CHECK(agent && ab && prior && pb && lengths && angles && frac0 && atom_types && time_freqs && grad_theta && stage, MI_EINVAL,
              "null argument");
-    TraceRange range("mi_ft_micro_step");
+    TraceRange range(what);
     MI_CHECK(ab != pb, MI_EINVAL, "agent and prior need separate batch handles (separate workspace)");
-    MI_CHECK(ab->B == pb->B && ab->N == pb->N && b_global >= ab->B / (copies > 0 ? copies : 1) && accum_steps >= 1, MI_EINVAL,
-             "inconsistent batch arguments");
+    MI_CHECK(ab->B == pb->B && ab->N == pb->N && accum_steps >= 1, MI_EINVAL, "inconsistent batch arguments");
     hipStream_t s = (hipStream_t)stream;
     const int B = ab->B, N = ab->N;
     if (B == 0 || N == 0) return MI_OK;
@@ -1584,16 +1585,51 @@ static int ft_micro_impl(mi_net* agent, mi_batch* ab, mi_net* prior, mi_batch* p
         MI_TRY(rc);
         MI_TRY(net_forward(prior, pb, temb, nz_types, tp.nz_frac, tp.nz_lat, pb->pred_l, pb->pred_x, pb->pred_t, s, false));
     }
-    LossArgs la{ab->pred_l, ab->pred_x, ab->pred_t, pb->pred_l, pb->pred_x, pb->pred_t, tp.rnd_l, tp.tar_x, tp.rnd_t, reward, ab->node_off,
-                tp.d_l, d_x, d_t, tp.Lb, tp.KLb, cost_lattice, cost_coord, cost_type, kl_sigma,
-                1.0f / ((float)b_global * (float)accum_steps)};
-    hipLaunchKernelGGL(ft_loss_kernel, dim3(B), dim3(256), 0, s, la);
-    if (stats) hipLaunchKernelGGL(ft_stats_kernel, dim3(1), dim3(64), 0, s, tp.Lb, tp.KLb, reward, B, kl_sigma, 1.0f / (float)b_global, stats);
-    MI_KERNEL_CHECK();
-    if (out_sample_loss) MI_HIP(hipMemcpyAsync(out_sample_loss, tp.Lb, B * 4, hipMemcpyDeviceToDevice, s));
-    if (out_kl) MI_HIP(hipMemcpyAsync(out_kl, tp.KLb, B * 4, hipMemcpyDeviceToDevice, s));
+    FtStageIO io{ab->pred_l, ab->pred_x, ab->pred_t, pb->pred_l, pb->pred_x, pb->pred_t, tp.rnd_l, tp.tar_x, tp.rnd_t, ab->node_off,
+                 tp.d_l, d_x, d_t, tp.Lb, tp.KLb, B, N, cost_lattice, cost_coord, cost_type, accum_steps};
+    MI_TRY(stage(io, stage_ctx, s));
     return net_backward(agent, ab, tp.d_l, d_x, d_t, grad_theta, s);
 }
+
+}  // namespace mi
+
+// the reward-weighted loss stage of mi_ft_micro_step / mi_ft_micro_steps_stacked: ft_loss_kernel, the statistics, the optional copies
+struct FtRewardStage {
+    const float* reward;
+    float kl_sigma;
+    int b_global;
+    float *stats, *out_sample_loss, *out_kl;
+};
+static int ft_reward_stage(const FtStageIO& io, void* ctx, hipStream_t s) {
+    const FtRewardStage& c = *(const FtRewardStage*)ctx;
+    const int B = io.B;
+    LossArgs la{io.pl, io.px, io.pt, io.plp, io.pxp, io.ptp, io.rl, io.tx, io.rt, c.reward, io.node_off,
+                io.dl, io.dx, io.dt, io.Lb, io.KLb, io.cl, io.cx, io.ct, c.kl_sigma,
+                1.0f / ((float)c.b_global * (float)io.accum_steps)};
+    hipLaunchKernelGGL(ft_loss_kernel, dim3(B), dim3(256), 0, s, la);
+    if (c.stats) hipLaunchKernelGGL(ft_stats_kernel, dim3(1), dim3(64), 0, s, io.Lb, io.KLb, c.reward, B, c.kl_sigma, 1.0f / (float)c.b_global, c.stats);
+    MI_KERNEL_CHECK();
+    if (c.out_sample_loss) MI_HIP(hipMemcpyAsync(c.out_sample_loss, io.Lb, B * 4, hipMemcpyDeviceToDevice, s));
+    if (c.out_kl) MI_HIP(hipMemcpyAsync(c.out_kl, io.KLb, B * 4, hipMemcpyDeviceToDevice, s));
+    return MI_OK;
+}
+
+static int ft_micro_impl(mi_net* agent, mi_batch* ab, mi_net* prior, mi_batch* pb, const float* lengths, const float* angles,
+                         const float* frac0, const int* atom_types, const float* reward, const float* time_freqs, int t, float c0, float c1,
+                         float sigma_t, float sigma_norm, int copies, const int* ts, const float* c0s, const float* c1s, const float* sigmas,
+                         const float* sigma_norms, uint64_t seed, uint32_t noise_step, const float* rand_l, const float* rand_x,
+                         const float* rand_t, float cost_lattice, float cost_coord, float cost_type, float kl_sigma, int b_global,
+                         int accum_steps, float* grad_theta, float* stats, float* out_sample_loss, float* out_kl, void* stream,
+                         void* aux_stream) {
+    MI_CHECK(reward, MI_EINVAL, "null argument");
+    MI_CHECK(!ab || b_global >= ab->B / (copies > 0 ? copies : 1), MI_EINVAL, "inconsistent batch arguments");
+    FtRewardStage st{reward, kl_sigma, b_global, stats, out_sample_loss, out_kl};
+    return ft_micro_run("mi_ft_micro_step", agent, ab, prior, pb, lengths, angles, frac0, atom_types, time_freqs, t, c0, c1, sigma_t, sigma_norm,
+                        copies, ts, c0s, c1s, sigmas, sigma_norms, seed, noise_step, rand_l, rand_x, rand_t, cost_lattice, cost_coord, cost_type,
+                        accum_steps, grad_theta, ft_reward_stage, &st, stream, aux_stream);
+}
+
+extern "C" {
 
 int mi_ft_micro_step(mi_net* agent, mi_batch* ab, mi_net* prior, mi_batch* pb, const float* lengths, const float* angles,
                      const float* frac0, const int* atom_types, const float* reward, const float* time_freqs, int t, float c0, float c1,

@@ -218,6 +218,14 @@ struct mi_batch {
     int cond_table_cap = 0;
     int *cond_kt = nullptr, *cond_kx = nullptr, *cond_kl = nullptr, *cond_types0 = nullptr;   // [N], [N], [B], [N] (allocated on first use)
     float *cond_frac0 = nullptr, *cond_lat0 = nullptr, *cond_table = nullptr;                  // [N][3], [B][9], [cond_levels][3]
+    // preference pairs (dpo.hip, mi_batch_set_pairs): (winner, loser) crystal indices, and per crystal the list of its pair slots in
+    // ascending pair index -- entry 2 p: crystal is pair p's winner, 2 p + 1: its loser
+    int n_pairs = 0, pairs_cap = 0;
+    int *dpo_w = nullptr, *dpo_l = nullptr;          // [n_pairs]
+    int *dpo_off = nullptr, *dpo_slots = nullptr;    // [B + 1], [2 n_pairs]
+    float* dpo_delta = nullptr;                      // [B]: d_b
+    float *dpo_m = nullptr, *dpo_g = nullptr;        // [n_pairs]: m_p, g_p
+    std::vector<int> dpo_w_h, dpo_l_h;
     std::vector<void*> allocs;
 };
 
@@ -232,6 +240,26 @@ int net_forward(mi_net* net, mi_batch* b, const float* t_emb, const float* atom_
 int net_tape_prepare(mi_net* net, mi_batch* b);
 int net_pack_transposes(mi_net* net, hipStream_t s);
 int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_coord, const float* d_type, float* grad, hipStream_t s);
+// backward.hip: the fine-tune micro-step's sequence -- time fill and embedding, add_noise_kernel (draw ids 7-9 at call `noise_step`, or the
+// injected noise), the agent's training forward, the frozen prior's forward (forked onto aux_stream when given), the LOSS STAGE, net_backward
+// into grad_theta -- with the loss stage passed in: it reads both networks' predictions and the targets, writes the three gradient seeds
+// (and the per-crystal Lb / KLb scratch of the tape), enqueues on `s` only.  mi_ft_micro_step's stage is in backward.hip, mi_dpo_micro_step's in dpo.hip.
+struct FtStageIO {
+    const float *pl, *px, *pt, *plp, *pxp, *ptp;   // agent / prior predictions [B][9], [N][3], [N][100]
+    const float *rl, *tx, *rt;                     // targets
+    const int* node_off;                           // [B + 1]
+    float *dl, *dx, *dt;                           // the seeds of the network backward, to be written for every row
+    float *Lb, *KLb;                               // [B] each (the tape's)
+    int B, N;
+    float cl, cx, ct;
+    int accum_steps;
+};
+typedef int (*ft_loss_stage_fn)(const FtStageIO& io, void* ctx, hipStream_t s);
+int ft_micro_run(const char* what, mi_net* agent, mi_batch* ab, mi_net* prior, mi_batch* pb, const float* lengths, const float* angles,
+                 const float* frac0, const int* atom_types, const float* time_freqs, int t, float c0, float c1, float sigma_t, float sigma_norm,
+                 int copies, const int* ts, const float* c0s, const float* c1s, const float* sigmas, const float* sigma_norms, uint64_t seed,
+                 uint32_t noise_step, const float* rand_l, const float* rand_x, const float* rand_t, float cost_lattice, float cost_coord,
+                 float cost_type, int accum_steps, float* grad_theta, ft_loss_stage_fn stage, void* stage_ctx, void* stream, void* aux_stream);
 int net_wgrad_window(mi_net* net, mi_batch* b, int slots);                   // 0: every backward contracts its own rows (default)
 int net_wgrad_flush(mi_net* net, mi_batch* b, float* grad, hipStream_t s);   // grad += the pending micro-steps' node-level weight gradients
 template <typename T>

@@ -142,7 +142,8 @@ def _grad_buffer(theta):
     return theta.grad
 
 
-def _run_epochs(agent, c, n_global, device, log, enqueue, plan=None, start=None, collect=None, before_step=None, after_step=None):
+def _run_epochs(agent, c, n_global, device, log, enqueue, plan=None, start=None, collect=None, before_step=None, after_step=None,
+                keys=None, where="ft_step"):
     """What every route of ft_step shares: a fresh fused Adam, `c.epochs` passes over the timesteps, an optimizer step -- all-reduce of the
     flat gradient, Adam, zero -- wherever an accumulation window closes, one reduction and one host read at the end of an epoch, its dict
     and log line.  A route plugs in what is its own:
@@ -150,7 +151,9 @@ def _run_epochs(agent, c, n_global, device, log, enqueue, plan=None, start=None,
                                    one timestep at a time), accumulating into theta.grad and `acc`;
       start()                      what an epoch starts with; returns its loss / loss_diff / loss_kl accumulators (default: three device floats);
       collect(acc)                 the three sums of the epoch from what start() returned (default: `acc` itself);
-      before_step(), after_step()  what surrounds an optimizer step (default: nothing).
+      before_step(), after_step()  what surrounds an optimizer step (default: nothing);
+      keys, where                  the names of its three accumulators in the epoch dicts (default: ft_step's loss / loss_diff / loss_kl) and
+                                   its name in an error message.
     Every rank must come here with the same `c.opt`, the rank without data included: one that clips differently diverges from its peers."""
     theta = agent.decoder.theta
     rank = rank_world()[0]
@@ -174,7 +177,8 @@ def _run_epochs(agent, c, n_global, device, log, enqueue, plan=None, start=None,
                 optimizer.zero_grad(set_to_none=False)
                 if after_step is not None:
                     after_step()
-        d = _epoch_stats(_epoch_reduce(acc if collect is None else collect(acc), "ft_step", optimizer), c.timesteps, n_global)
+        d = _epoch_stats(_epoch_reduce(acc if collect is None else collect(acc), where, optimizer), c.timesteps, n_global,
+                         *(() if keys is None else (keys,)))
         stats.append(d)
         if rank == 0:
             log(f"Epoch {epoch}: " + ", ".join(f"{k}: {v:.4f}" for k, v in d.items()))
@@ -251,9 +255,10 @@ def ft_step(agent, prior, data_list, rewards, cfg, device=None, noise_fn=None, l
     return _run_epochs(agent, c, n_global, device, log, enqueue, plan=_stack_plan(e_local, c.accum_steps, c.timesteps, stack))
 
 
-def _epoch_stats(a, timesteps, n_global):
-    """An epoch's dict from _epoch_reduce's list: the three losses; behind them, when the optimizer clips or guards, its statistics."""
-    d = dict(loss=a[0] / timesteps, loss_diff=a[1] / timesteps / n_global, loss_kl=a[2] / timesteps / n_global)
+def _epoch_stats(a, timesteps, n_global, keys=("loss", "loss_diff", "loss_kl")):
+    """An epoch's dict from _epoch_reduce's list: the three losses under the route's `keys` (the first a mean over the timesteps, the other
+    two also over n_global); behind them, when the optimizer clips or guards, its statistics."""
+    d = {keys[0]: a[0] / timesteps, keys[1]: a[1] / timesteps / n_global, keys[2]: a[2] / timesteps / n_global}
     if len(a) > 3:
         d.update(epoch_grad_stats(a[3:]))
     return d

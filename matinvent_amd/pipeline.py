@@ -115,6 +115,32 @@ class MatInvent(ReinL):
     def ft_step(self, data_list, rewards, baseline=None):
         return _ft_step(self.agent, self.prior, data_list, rewards, self.finetune_cfg, device=self.device)
 
+    def _score_and_remember(self, data, strucs, xyz, metrics, log_now=True):
+        """Rank 0's bookkeeping between sampling and the update: reward_step, the long-term memory with its five log keys, the logger's row
+        (log_now=False: the caller adds its own keys and logs), then the diversity filter (mat_invent.py:230-237).  Returns (data, strucs,
+        rewards -- penalised when the filter is on --, the log dict, the structures the filter zeroed)."""
+        data, strucs, rewards, props = self.reward_step(data, strucs, xyz, f"step_{self.step:0>4d}")
+        log = {f"{k} mean": v.mean() for k, v in props.items()}
+        log.update({"reward mean": rewards.mean(), "reward std": rewards.std(), "cost": self.cost}, **metrics)
+        # long-term memory (mat_invent.py:209-226): bookkeeping and five log keys, whether or not the filter is on
+        self.ltm.extend(strucs, rewards, self.step)
+        thred = getattr(self.reward, "threshold", getattr(self.reward, "reward_threshold", 0.0))
+        burden, div_ratio = self.ltm.calc_metrics(thred)
+        self.ltm.save(os.path.join(self.sample_dir, "long_term_memory.csv"))
+        logging.info(f"{len(self.ltm)} crystals generated so far, {len(self.ltm.unique_comps)} unique components.  Burden: {burden}, "
+                     f"Div. Ratio: {div_ratio}.")
+        log.update({"crystal_num": len(self.ltm), "unique_comps": len(self.ltm.unique_comps), "burden": burden, "div_ratio": div_ratio})
+        if self.ltm.structure:
+            log["unique_structures"] = self.ltm.unique_structures
+        if log_now and self.logger is not None:
+            self.logger.log(log, step=self.step)
+        penalty_strucs = []
+        if self.div_filter:   # (mat_invent.py:230-237: the penalised rewards rank the top-k)
+            rewards, penalty_idx, tol_n, buff_n = self.ltm.div_filter(strucs, rewards, **self.df_args)
+            penalty_strucs = [strucs[p] for p in penalty_idx]
+            logging.info(f"Diversity filter: tol_n={tol_n}, buff_n={buff_n}")
+        return data, strucs, rewards, log, penalty_strucs
+
     def rl_step(self):
         t0 = time.time()
         rank, world = rank_world()
@@ -124,26 +150,7 @@ class MatInvent(ReinL):
             logging.warning("no sample passed the validity pre-filter; skipping scoring and fine-tuning for this loop")
             return
         if rank == 0:  # scoring / ranking / replay are rank-0 CPU bookkeeping; the chosen set is broadcast
-            data, strucs, rewards, props = self.reward_step(data, strucs, xyz, f"step_{self.step:0>4d}")
-            log = {f"{k} mean": v.mean() for k, v in props.items()}
-            log.update({"reward mean": rewards.mean(), "reward std": rewards.std(), "cost": self.cost}, **metrics)
-            # long-term memory (mat_invent.py:209-226): bookkeeping and five log keys, whether or not the filter is on
-            self.ltm.extend(strucs, rewards, self.step)
-            thred = getattr(self.reward, "threshold", getattr(self.reward, "reward_threshold", 0.0))
-            burden, div_ratio = self.ltm.calc_metrics(thred)
-            self.ltm.save(os.path.join(self.sample_dir, "long_term_memory.csv"))
-            logging.info(f"{len(self.ltm)} crystals generated so far, {len(self.ltm.unique_comps)} unique components.  Burden: {burden}, "
-                         f"Div. Ratio: {div_ratio}.")
-            log.update({"crystal_num": len(self.ltm), "unique_comps": len(self.ltm.unique_comps), "burden": burden, "div_ratio": div_ratio})
-            if self.ltm.structure:
-                log["unique_structures"] = self.ltm.unique_structures
-            if self.logger is not None:
-                self.logger.log(log, step=self.step)
-            penalty_strucs = []
-            if self.div_filter:   # (mat_invent.py:230-237: the penalised rewards rank the top-k)
-                rewards, penalty_idx, tol_n, buff_n = self.ltm.div_filter(strucs, rewards, **self.df_args)
-                penalty_strucs = [strucs[p] for p in penalty_idx]
-                logging.info(f"Diversity filter: tol_n={tol_n}, buff_n={buff_n}")
+            data, strucs, rewards, _, penalty_strucs = self._score_and_remember(data, strucs, xyz, metrics)
             order = np.argsort(rewards)[::-1]
             topk = order[: int(self.finetune_cfg.batch_size * self.topk_ratio)]
             ft_data, ft_reward = [data[i] for i in topk], rewards[topk]
@@ -281,6 +288,76 @@ class MatInventPG(MatInvent):
         for k in ("grad_norm", "skipped_steps"):   # (finetune_cfg.max_grad_norm / skip_nonfinite_steps: the optimiser's statistics)
             if k in last:
                 log[k] = last[k]
+        if self.logger is not None:
+            self.logger.log(log, step=self.step)
+        logging.info(f"*****   LOOP {self.step} FINISH   *****  {(time.time() - t0) / 60:.2f} min")
+
+
+class MatInventDPO(MatInvent):
+    """MatInvent with the preference loss on ranked pairs of final crystals (preference.dpo_step, Diffusion-DPO) in place of the
+    reward-weighted denoising loss.  sample_step, reward_step, the long-term memory and the diversity filter are MatInvent's; each loop's
+    pool is its scored crystals (with the penalised rewards when div_filter is on) plus replay.sample() when replay=True, and the loop's
+    crystals then go into the replay buffer.  Pairs: preference.build_pairs over the pool with finetune_cfg.dpo_margin (default 0),
+    finetune_cfg.dpo_pairs (the cap; default finetune_cfg.batch_size), finetune_cfg.dpo_within (null | formula: both crystals of a pair
+    share the reduced formula), winners among the top `topk_ratio` share of the pool by reward (1.0: any), seed = the loop index.  The loss
+    needs no trajectory and no on-policy data: conditioned sampling, sample_steps, num_batches > 1, replay and div_filter are all allowed.
+    One GPU, DiffCSP only.  finetune_cfg.dpo_beta is required (preference.dpo_step)."""
+
+    def __init__(self, rl_epoch, model_suite, reward, sample_cfg, finetune_cfg, save_dir, topk_ratio=1.0, **kwargs):
+        from .suite import MatterGenSuite
+        if isinstance(model_suite, MatterGenSuite):
+            raise ValueError("MatInventDPO needs the DiffCSP suite: the MatterGen-shaped module has no fused micro-step to put the "
+                             "preference loss in")
+        if rank_world()[1] > 1:
+            raise ValueError("MatInventDPO runs on one GPU: world_size > 1 is not supported (pairs cross shards)")
+        super().__init__(rl_epoch=rl_epoch, model_suite=model_suite, reward=reward, sample_cfg=sample_cfg, finetune_cfg=finetune_cfg,
+                         topk_ratio=topk_ratio, save_dir=save_dir, **kwargs)
+        within = self.finetune_cfg.get("dpo_within")
+        if within not in (None, "formula"):
+            raise ValueError(f"MatInventDPO: finetune_cfg.dpo_within = {within!r} is neither null nor 'formula'")
+
+    def make_pairs(self, pool, rewards):
+        """preference.build_pairs over the pool under finetune_cfg's dpo_* keys and topk_ratio (see the class)."""
+        from .memory import _formula
+        from .preference import build_pairs
+        fc = self.finetune_cfg
+        rewards = np.asarray(rewards, dtype=float)
+        winners = None
+        if self.topk_ratio < 1.0:
+            winners = np.zeros(len(pool), dtype=bool)
+            winners[np.argsort(-rewards, kind="stable")[: max(1, int(len(pool) * self.topk_ratio))]] = True
+        cap = fc.get("dpo_pairs")
+        return build_pairs(rewards, keys=[_formula(d) for d in pool] if fc.get("dpo_within") == "formula" else None,
+                           margin=float(fc.get("dpo_margin") or 0.0), max_pairs=int(fc.batch_size if cap is None else cap), winners=winners,
+                           seed=self.step)
+
+    def rl_step(self):
+        from .preference import dpo_step
+        t0 = time.time()
+        logging.info(f"*****   LOOP {self.step} START   *****")
+        data, strucs, xyz, metrics = self.sample_step()
+        if len(data) == 0:
+            logging.warning("no sample passed the validity pre-filter; skipping scoring and the preference update for this loop")
+            return
+        data, strucs, rewards, log, penalty_strucs = self._score_and_remember(data, strucs, xyz, metrics, log_now=False)
+        pool, pool_rewards = list(data), np.asarray(rewards, dtype=float)
+        if self.replay is not None:
+            if penalty_strucs:
+                self.replay.memory_purge(penalty_strucs)
+            rd, rr = self.replay.sample()
+            self.replay.extend(data, None, rewards)
+            pool, pool_rewards = pool + rd, np.concatenate((pool_rewards, rr))
+        pairs = self.make_pairs(pool, pool_rewards)
+        log["pairs"] = len(pairs)
+        if len(pairs) == 0:
+            logging.warning(f"no pair among {len(pool)} crystals passes the margin / key / winner rules; skipping the preference update for "
+                            "this loop")
+        else:
+            last = dpo_step(self.agent, self.prior, pool, pairs, self.finetune_cfg, device=self.device)[-1]
+            log.update({"dpo_loss": last["loss"], "pref_acc": last["pref_acc"], "margin": last["margin"]})
+            for k in ("grad_norm", "skipped_steps"):   # (finetune_cfg.max_grad_norm / skip_nonfinite_steps: the optimiser's statistics)
+                if k in last:
+                    log[k] = last[k]
         if self.logger is not None:
             self.logger.log(log, step=self.step)
         logging.info(f"*****   LOOP {self.step} FINISH   *****  {(time.time() - t0) / 60:.2f} min")
