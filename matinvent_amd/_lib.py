@@ -217,9 +217,25 @@ DPO_SIGNATURES = {
                                C.c_float, C.c_float, C.c_float, C.c_float, _I, _I, _P, _P, _P, _P, _P, _P]),
 }
 
+# the fingerprint-matching extension, include/matinvent_hip_match.h (nearest bank row, count within a tolerance, pair distances)
+class FpMatchArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("query", "bank", "bank_start", "bank_len", "grp_q_off", "q_idx", "grp_c_off", "c_idx", "grp_ncols", "items",
+                                           "grp_part_off", "workspace", "best_dist", "best_idx", "n_within", "status", "pair_dist", "pair_off")] +
+                [("bank_floats", C.c_int64), ("pair_floats", C.c_int64)] +
+                [(k, C.c_int) for k in ("Q", "row_stride", "M", "G", "nnz_q", "nnz_c", "n_items", "n_partials", "max_ncols")] + [("tol", C.c_float)])
+
+
+FP_MATCH_TILE, FP_MATCH_ITEM_INTS = 8, 5   # include/matinvent_hip_match.h
+
+MATCH_SIGNATURES = {
+    "mi_fp_match_plan": (_I, [C.POINTER(_I), C.POINTER(_I), _I, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_L), C.POINTER(_L)]),
+    "mi_fp_match_workspace": (_L, [_L]),
+    "mi_fp_match": (_I, [C.POINTER(FpMatchArgs), _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
-                        DPO_SIGNATURES)
+                        DPO_SIGNATURES, MATCH_SIGNATURES)
 
 _lib = None
 

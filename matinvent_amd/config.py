@@ -186,11 +186,13 @@ def compose(config_dir: str, config_name: str = "base", overrides: List[str] = (
                 order.append(g)
         else:
             raise ValueError(f"unsupported defaults entry {item!r}")
-    plain = []
+    plain, placed = [], []
     for ov in overrides:
         key, eq, val = ov.partition("=")
         if eq and key in groups and not key.startswith(("+", "~")):
             groups[key] = val  # config-group selection, e.g. model=diffcsp
+        elif eq and "@" in key and key.startswith("+"):
+            placed.append((key[1:].partition("@")[0], key.partition("@")[2], val))  # +group@package=option, e.g. +filter@sample_cfg.filter=un
         else:
             plain.append(ov)
     cfg = Config()
@@ -199,6 +201,8 @@ def compose(config_dir: str, config_name: str = "base", overrides: List[str] = (
             continue
         cfg[g] = load(os.path.join(config_dir, g, str(groups[g]) + ".yaml"))
     cfg = merge(cfg, primary)
+    for g, package, opt in placed:   # a group file placed at a package path of its own (Hydra's group@package syntax)
+        _set_path(cfg, package, load(os.path.join(config_dir, g, opt + ".yaml")), create_missing=True)
     for ov in plain:
         if ov.startswith("~"):
             node, _, leaf = ov[1:].rpartition(".")

@@ -8,7 +8,7 @@ What the reference gets from pymatgen / ase on the sampler -> filter -> reward h
     neutrality test (SMACT) of `invalid_filter` needs its element database and is not reproduced.
   * `lattice_matrix` (pymatgen `Lattice.from_parameters` orientation), `volume`, `density`, `composition`,
     `reduced_formula` -- the keys memory/replay_buffer.py:38 and memory/ltm.py:31 dedupe on;
-  * `write_extxyz` / `write_cif` -- pipeline/utils/save.py:32-41 writes extxyz through ase.
+  * `write_extxyz` / `write_cif` -- pipeline/utils/save.py:32-41 writes extxyz through ase; `read_extxyz`, the inverse of the former.
   * `fingerprints`: a permutation-, translation-, basis- and supercell-invariant unit vector per crystal (species-resolved Oganov-Valle
     fingerprint, `mi_structure_fingerprint_offsets`) and `fingerprint_distance`, the key of the structure-resolved memories.
 """
@@ -96,6 +96,42 @@ def write_extxyz(structures, path: str, infos: List[dict] = None) -> str:
             for z, p in zip(species, cart):
                 f.write(f"{SYMBOLS[z]:<2s} {p[0]:16.8f} {p[1]:16.8f} {p[2]:16.8f}\n")
     return path
+
+
+def read_extxyz(path: str):
+    """The inverse of `write_extxyz`: a list of dict(species, frac_coords, lengths, angles, lattice, info) per frame -- species as atomic
+    numbers, fractional coordinates from the Cartesian ones, lengths and angles (degrees) from the lattice rows."""
+    import re
+    from types import SimpleNamespace
+    out = []
+    with open(path) as f:
+        lines = f.read().splitlines()
+    at = 0
+    while at < len(lines):
+        if not lines[at].strip():
+            at += 1
+            continue
+        n = int(lines[at].split()[0])
+        head = lines[at + 1]
+        m = re.search(r'Lattice="([^"]*)"', head)
+        if m is None or at + 2 + n > len(lines):
+            raise ValueError(f"{path}: frame at line {at + 1} has no Lattice= or is cut short")
+        L = np.array([float(x) for x in m.group(1).split()], np.float64).reshape(3, 3)
+        species, cart = [], []
+        for ln in lines[at + 2: at + 2 + n]:
+            p = ln.split()
+            if p[0] not in SYMBOLS[1:]:
+                raise ValueError(f"{path}: unknown element {p[0]!r}")
+            species.append(SYMBOLS.index(p[0]))
+            cart.append([float(p[1]), float(p[2]), float(p[3])])
+        cart = np.asarray(cart, np.float64).reshape(n, 3)
+        lengths = np.linalg.norm(L, axis=1)
+        cosang = [float(np.dot(L[(k + 1) % 3], L[(k + 2) % 3]) / (lengths[(k + 1) % 3] * lengths[(k + 2) % 3])) for k in range(3)]
+        angles = [math.degrees(math.acos(max(-1.0, min(1.0, c)))) for c in cosang]
+        info = {k: v for k, v in re.findall(r'(\w+)=([^\s"]+)', re.sub(r'\w+="[^"]*"', "", head)) if k != "Properties"}
+        out.append(SimpleNamespace(species=species, frac_coords=cart @ np.linalg.inv(L), lengths=lengths.tolist(), angles=angles, lattice=L, info=info))
+        at += 2 + n
+    return out
 
 
 def cif_text(structure, name: str = "generated") -> str:
