@@ -196,6 +196,13 @@ COND_SIGNATURES = {
     "mi_condition_apply": (_I, [_P, _I, _U64, _P, _P, _P, _P]),
 }
 
+# the likelihood-mask extension, include/matinvent_hip_lik.h (the trajectory likelihood of a conditioned chain: which predictor terms leave it)
+LIK_SIGNATURES = {
+    "mi_batch_set_likelihood_mask": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "mi_batch_has_likelihood_mask": (_I, [_P]),
+    "mi_traj_read_derivatives": (_I, [_P, _P, _P, _P, _P]),
+}
+
 # the structure-fingerprint extension, include/matinvent_hip_fp.h (the key of the structure-resolved long-term memory and replay buffer)
 class FpParams(C.Structure):
     _fields_ = [("r_max", C.c_float), ("sigma", C.c_float), ("nbins", C.c_int)]
@@ -235,7 +242,7 @@ MATCH_SIGNATURES = {
 
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
-                        DPO_SIGNATURES, MATCH_SIGNATURES)
+                        DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES)
 
 _lib = None
 

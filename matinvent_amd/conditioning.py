@@ -140,6 +140,15 @@ class Condition:
                          frac_coords=self.frac_coords[a0:a1], known_coords=self.known_coords[a0:a1], lattices=self.lattices[g0:g1],
                          known_lattice=self.known_lattice[g0:g1])
 
+    def select(self, idx):
+        """The condition of the crystals `idx`, in that order (any subset: the kept crystals of a filtered rollout)."""
+        idx = [int(i) for i in idx]
+        off = torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(self.num_atoms, 0)])
+        gi = torch.as_tensor(idx, dtype=torch.long)
+        ai = torch.cat([torch.arange(int(off[i]), int(off[i + 1])) for i in idx]) if idx else torch.zeros(0, dtype=torch.long)
+        return Condition(self.num_atoms[gi], atom_types=self.atom_types[ai], known_types=self.known_types[ai], frac_coords=self.frac_coords[ai],
+                         known_coords=self.known_coords[ai], lattices=self.lattices[gi], known_lattice=self.known_lattice[gi])
+
     # ---- the handle ----------------------------------------------------------------------------------
     def attach(self, module, cb, table=None):
         """Copy this condition and `module`'s level table to the batch handle `cb` (mi_batch_set_condition: blocking copies; no work of
@@ -159,6 +168,36 @@ class Condition:
     def clear(cb):
         from . import _lib
         _lib.check(_lib.load().mi_batch_set_condition(cb._h, None, None, 0), "mi_batch_set_condition")
+
+
+    # ---- the likelihood mask (include/matinvent_hip_lik.h) -----------------------------------
+    def attach_likelihood(self, module, cb):
+        """Copy this condition's three masks to the batch handle `cb` as its likelihood mask (mi_batch_set_likelihood_mask: blocking
+        copies; no work of the handle may be in flight): the predictor terms of the known elements leave the log-probabilities that
+        mi_traj_logprob / mi_traj_pg_step / mi_traj_pg_kl_step compute on the handle and, with the condition attached too, the ones a
+        recording chain records.  `module` is the handle's module, as for `attach` (the mask itself needs nothing of it)."""
+        from . import _lib
+        if cb.num_atoms_list != [int(v) for v in self.num_atoms.tolist()]:
+            raise ValueError("Condition: its atom counts are not those of the batch it is attached to")
+        i32 = lambda v: np.ascontiguousarray(v.numpy().astype(np.int32))
+        keep = [i32(self.known_types), i32(self.known_coords), i32(self.known_lattice)]
+        _lib.check(_lib.load().mi_batch_set_likelihood_mask(cb._h, *(a.ctypes.data_as(C.POINTER(C.c_int)) for a in keep)),
+                   "mi_batch_set_likelihood_mask")
+
+    @staticmethod
+    def clear_likelihood(cb):
+        from . import _lib
+        _lib.check(_lib.load().mi_batch_set_likelihood_mask(cb._h, None, None, None), "mi_batch_set_likelihood_mask")
+
+
+def check_likelihood(where, likelihood, condition):
+    """The `likelihood` keyword of sample / sample_rollout / forward_logprb: None (the default) or "free" -- the trajectory likelihood
+    over the free elements, which needs the condition that names them."""
+    if likelihood not in (None, "free"):
+        raise ValueError(f"{where}: likelihood = {likelihood!r} is neither None nor 'free'")
+    if likelihood is not None and condition is None:
+        raise ValueError(f"{where}: likelihood = 'free' needs the condition that names the free elements (condition=None)")
+    return likelihood is not None
 
 
 def apply(cb, level, seed, atom_types, frac_coords, lattices):

@@ -51,4 +51,34 @@ __device__ __forceinline__ float log_prob_wn_dmu(float x, float mu, float sigma_
     return logf(p);
 }
 
+// sum over a 256-thread block in a fixed tree: the wave sums, then ((w0 + w1) + (w2 + w3)) from `red` (4 floats of LDS) -- the same bits every call
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
+    v = wave_sum(v);
+    int wave = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[wave] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// ---- predictor (diffusion.py:337-382): the arguments of sampler.hip's predictor_kernel and of its masked form in condition.hip ----
+struct PredictorArgs {
+    const float *x_mid, *pred_x, *pred_l, *pred_t;
+    const float *noise_x, *noise_l, *noise_t;  // slices for step t, or NULL (Philox)
+    const float* coef;
+    const int* node_off;
+    const float* lp_corr;
+    float *frac, *lattices, *atom_types;  // state, updated in place
+    float *rec_types, *rec_frac, *rec_lat, *rec_lpl, *rec_lpt, *rec_lpx;  // slices (t-1 for state, t for log-probs)
+    uint64_t seed;
+    int64_t node_offset, graph_offset;
+    int t;
+    int keep_lattice, keep_coords;  // CSP mode (diffusion.py:283-287, 308-312, 348-349): that part of the state is never moved
+};
+
+// the likelihood mask of a conditioned chain (include/matinvent_hip_lik.h): 0 / 1 per atom (types, coordinates) and per crystal (lattice)
+struct LikMask {
+    const int *known_types, *known_coords, *known_lattice;   // [N], [N], [B]
+};
+
 }  // namespace mi

@@ -218,6 +218,11 @@ struct mi_batch {
     int cond_table_cap = 0;
     int *cond_kt = nullptr, *cond_kx = nullptr, *cond_kl = nullptr, *cond_types0 = nullptr;   // [N], [N], [B], [N] (allocated on first use)
     float *cond_frac0 = nullptr, *cond_lat0 = nullptr, *cond_table = nullptr;                  // [N][3], [B][9], [cond_levels][3]
+    // likelihood mask (condition.hip, mi_batch_set_likelihood_mask): the elements whose predictor terms leave the trajectory
+    // likelihood -- state of its own, apart from the condition above (a policy-gradient handle carries the masks alone)
+    bool lik_on = false;
+    int *lik_kt = nullptr, *lik_kx = nullptr, *lik_kl = nullptr;      // [N], [N], [B] 0 / 1 (allocated on first use)
+    std::vector<int> lik_h;                                           // host copy [N | N | B]: comparison between the handles of a call
     // preference pairs (dpo.hip, mi_batch_set_pairs): (winner, loser) crystal indices, and per crystal the list of its pair slots in
     // ascending pair index -- entry 2 p: crystal is pair p's winner, 2 p + 1: its loser
     int n_pairs = 0, pairs_cap = 0;
@@ -295,6 +300,11 @@ int time_map_same(const mi_batch* p, const mi_batch* q, const char* what);
 int condition_check(const mi_batch* b, int T, const char* what);
 int condition_impose(const mi_batch* b, int level, uint64_t seed, float* atom_types, float* frac, float* lattices, float* rec_types, float* rec_frac,
                      float* rec_lat, hipStream_t s);
+// ... and the entries' host-side check that two handles of one call carry the same likelihood mask, or none (MI_EINVAL with the message set)
+int likelihood_mask_same(const mi_batch* p, const mi_batch* q, const char* what);
+// ... and the masked form of the sampler's predictor launch (logprob.h: PredictorArgs), for a recording chain on a handle with a condition and a mask
+struct PredictorArgs;
+int predictor_masked_launch(const mi_batch* b, const PredictorArgs& a, hipStream_t s);
 extern int g_knn_nosync;
 int knn_build(mi_batch* b, const float* frac, const float* lattices, hipStream_t s, bool nosync = false);
 }  // namespace mi

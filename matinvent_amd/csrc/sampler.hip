@@ -44,15 +44,6 @@ __global__ void philox_fill_kernel(uint64_t seed, uint32_t step, uint32_t draw, 
     out[i] = uniform ? philox_uniform1(seed, step, draw, e) : philox_normal1(seed, step, draw, e);
 }
 
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-    v = wave_sum(v);
-    int wave = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[wave] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // ---- corrector (diffusion.py:320-334): x_{t-1/2} = x_t - eps * s + sqrt(2 eps) z ---------------
 // one 64-lane block per crystal; also the corrector half of log_prob_x (:363-368)
 __global__ __launch_bounds__(64) void corrector_kernel(const float* __restrict__ x_t, const float* __restrict__ pred_x,
@@ -82,20 +73,6 @@ __global__ __launch_bounds__(64) void corrector_kernel(const float* __restrict__
 }
 
 // ---- predictor (diffusion.py:337-382) -------------------------------------------------------
-struct PredictorArgs {
-    const float *x_mid, *pred_x, *pred_l, *pred_t;
-    const float *noise_x, *noise_l, *noise_t;  // slices for step t, or NULL (Philox)
-    const float* coef;
-    const int* node_off;
-    const float* lp_corr;
-    float *frac, *lattices, *atom_types;  // state, updated in place
-    float *rec_types, *rec_frac, *rec_lat, *rec_lpl, *rec_lpt, *rec_lpx;  // slices (t-1 for state, t for log-probs)
-    uint64_t seed;
-    int64_t node_offset, graph_offset;
-    int t;
-    int keep_lattice, keep_coords;  // CSP mode (diffusion.py:283-287, 308-312, 348-349): that part of the state is never moved
-};
-
 __global__ __launch_bounds__(256) void predictor_kernel(PredictorArgs a) {
     __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -313,8 +290,12 @@ int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int 
         a.t = t;
         a.keep_lattice = b->keep_lattice;
         a.keep_coords = b->keep_coords;
-        hipLaunchKernelGGL(predictor_kernel, dim3(B), dim3(256), 0, s, a);
-        MI_KERNEL_CHECK();
+        if (b->cond_on && b->lik_on && rec) {   // the record of a conditioned chain's likelihood (condition.hip)
+            MI_TRY(predictor_masked_launch(b, a, s));
+        } else {
+            hipLaunchKernelGGL(predictor_kernel, dim3(B), dim3(256), 0, s, a);
+            MI_KERNEL_CHECK();
+        }
         // ... and at the level the step arrived at: the known elements of the state and of its record are overwritten (the corrector is left alone)
         if (b->cond_on) MI_TRY(condition_impose(b, t - 1, seed, atom_types, frac, lattices, a.rec_types, a.rec_frac, a.rec_lat, s));
     }

@@ -12,6 +12,7 @@
 #include "../../include/matinvent_hip_traj.h"
 #include "../../include/matinvent_hip_pg.h"
 #include "../../include/matinvent_hip_pg_kl.h"
+#include "../../include/matinvent_hip_lik.h"
 #include "net.h"
 #include "logprob.h"
 
@@ -27,15 +28,6 @@ struct TrajArgs {
     float *dx_corr, *dx_pred, *dl, *dt;                            // local derivatives (taped call) or NULL
     int B;
 };
-
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-    v = wave_sum(v);
-    int wave = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[wave] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // one 256-thread block per crystal; every sum runs over a fixed thread-to-element map and a fixed tree: no atomics, same bits every call
 __global__ __launch_bounds__(256) void traj_logprob_kernel(TrajArgs a) {
@@ -113,6 +105,97 @@ __global__ __launch_bounds__(256) void traj_logprob_kernel(TrajArgs a) {
     }
 }
 
+// traj_logprob_kernel under a likelihood mask: the predictor terms of the known elements leave the sums and their local derivatives are
+// 0.f; the divisors, the corrector term, the thread-to-element maps, the reduction trees and every free element's arithmetic are
+// traj_logprob_kernel's, line for line -- a kernel of its own, so that traj_logprob_kernel's device code stays what it was.
+__global__ __launch_bounds__(256) void traj_logprob_masked_kernel(TrajArgs a, LikMask m) {
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const StepCoef c = load_coef(a.coef, a.t[b]);
+    const int n0 = a.node_off[b], n1 = a.node_off[b + 1], n = n1 - n0;
+    const float cnt = (float)(n > 0 ? n : 1);
+    const bool tape = a.dx_corr != nullptr;
+
+    // corrector (diffusion.py:175-192): mu = (x - step_corr * sqrt(sn) * pred_x_corr) % 1, log_prob_wn(x_mid, mu, std_corr)
+    // predictor (:194-213):            mu = (x_mid - step_pred * sqrt(sn) * pred_x_pred) % 1, log_prob_wn(x_next, mu, std_pred)
+    // d mu / d pred = -step * sqrt(sn) (the `% 1` passes the gradient through unchanged, as in torch); each coordinate enters its crystal's mean
+    // with weight 1 / (3 n)
+    const float kc = -(c.step_corr * c.sqrt_sn) / 3.0f / cnt, kp = -(c.step_pred * c.sqrt_sn) / 3.0f / cnt;
+    float lpc = 0.f, lpp = 0.f;
+    for (int idx = n0 * 3 + tid; idx < n1 * 3; idx += 256) {
+        float px = a.px_corr[idx] * c.sqrt_sn;
+        float mu = pymod1(a.x[idx] - c.step_corr * px);
+        float xm = a.x_mid[idx];
+        if (tape) {
+            float dmu;
+            lpc += log_prob_wn_dmu(xm, mu, c.std_corr_sq, &dmu);
+            a.dx_corr[idx] = dmu * kc;
+        } else {
+            lpc += log_prob_wn(xm, mu, c.std_corr_sq);
+        }
+        if (m.known_coords[idx / 3]) {   // the imposition replaced this coordinate: its predictor term is a constant of theta
+            if (tape) a.dx_pred[idx] = 0.f;
+        } else {
+            px = a.px_pred[idx] * c.sqrt_sn;
+            mu = pymod1(xm - c.step_pred * px);
+            if (tape) {
+                float dmu;
+                lpp += log_prob_wn_dmu(a.x_next[idx], mu, c.std_pred_sq, &dmu);
+                a.dx_pred[idx] = dmu * kp;
+            } else {
+                lpp += log_prob_wn(a.x_next[idx], mu, c.std_pred_sq);
+            }
+        }
+    }
+    lpc = block_sum_256(lpc, red);
+    lpp = block_sum_256(lpp, red);
+
+    // lattice (:215-218): Normal(c0 (l - c1 pred_l), sigma).log_prob(l_next), mean over the 9 entries; d/d pred_l = (l_next - m) / sigma^2 * (-c0 c1) / 9
+    float lpl = 0.f;
+    if (tid < 9) {
+        const int idx = b * 9 + tid;
+        if (m.known_lattice[b]) {
+            if (tape) a.dl[idx] = 0.f;
+        } else {
+            const float mean = c.c0 * (a.l[idx] - c.c1 * a.pl[idx]);
+            const float v = a.l_next[idx];
+            lpl = normal_log_prob(v, mean, c.sigma_sq, c.log_sigma);
+            if (tape) a.dl[idx] = (v - mean) / c.sigma_sq * (-(c.c0 * c.c1)) / 9.0f;
+        }
+    }
+    lpl = block_sum_256(lpl, red);
+
+    // atom-type logits (:216-221): the same Normal, mean over the 100 logits, then over the atoms; one wave per atom
+    const int lane = tid & 63, wave = tid >> 6;
+    const float kt = -(c.c0 * c.c1) / (float)MI_NUM_TYPES / cnt;
+    float lpt = 0.f;
+    for (int i = n0 + wave; i < n1; i += 4) {
+        if (m.known_types[i]) {   // (the same for every lane of the wave: the atom's row leaves the sum whole)
+            if (tape)
+                for (int k = lane; k < MI_NUM_TYPES; k += 64) a.dt[(size_t)i * MI_NUM_TYPES + k] = 0.f;
+            continue;
+        }
+        float s = 0.f;
+        for (int k = lane; k < MI_NUM_TYPES; k += 64) {
+            const size_t idx = (size_t)i * MI_NUM_TYPES + k;
+            const float mean = c.c0 * (a.a[idx] - c.c1 * a.pt[idx]);
+            const float v = a.a_next[idx];
+            s += normal_log_prob(v, mean, c.sigma_sq, c.log_sigma);
+            if (tape) a.dt[idx] = (v - mean) / c.sigma_sq * kt;
+        }
+        s = wave_sum(s);
+        lpt += s / (float)MI_NUM_TYPES;
+    }
+    __syncthreads();
+    if (lane == 0) red[wave] = lpt;
+    __syncthreads();
+    if (tid == 0) {
+        a.lp[b] = (lpl / 3.0f) / 3.0f;                                      // .mean(-1).mean(-1)
+        a.lp[a.B + b] = ((red[0] + red[1]) + (red[2] + red[3])) / cnt;      // scatter mean over the atoms
+        a.lp[2 * a.B + b] = (lpc / 3.0f) / cnt + (lpp / 3.0f) / cnt;  // corrector + predictor, each a mean over coordinates and atoms
+    }
+}
+
 struct SeedArgs {
     const float* g;      // [3][B] upstream gradients of (log_prob_l, log_prob_t, log_prob_x)
     const int* n2g;      // [N]
@@ -163,6 +246,8 @@ static int traj_buffers(mi_batch* b) {
     return alloc_set(b, {{&b->tr_dl, nl}, {&b->tr_dt, nt}, {&b->tr_sl, nl}, {&b->tr_sx, nx}, {&b->tr_st, nt}, {&b->tr_dx, nx}});
 }
 
+static LikMask lik_mask(const mi_batch* b) { return LikMask{b->lik_kt, b->lik_kx, b->lik_kl}; }
+
 static bool same_counts(const mi_batch* p, const mi_batch* q) {
     return p->B == q->B && p->N == q->N && p->num_atoms_h == q->num_atoms_h;
 }
@@ -207,7 +292,11 @@ static int traj_logprob_enqueue(mi_net* net, mi_batch* bc, mi_batch* bp, const i
     a.dl = train ? bp->tr_dl : nullptr;
     a.dt = train ? bp->tr_dt : nullptr;
     a.B = B;
-    hipLaunchKernelGGL(traj_logprob_kernel, dim3(B), dim3(256), 0, s, a);
+    if (bp->lik_on) {   // a conditioned chain's likelihood; the entries have checked that bc carries the same mask
+        hipLaunchKernelGGL(traj_logprob_masked_kernel, dim3(B), dim3(256), 0, s, a, lik_mask(bp));
+    } else {
+        hipLaunchKernelGGL(traj_logprob_kernel, dim3(B), dim3(256), 0, s, a);
+    }
     MI_KERNEL_CHECK();
     if (train && N > 0) {
         bc->tr_partner = bp;
@@ -221,8 +310,10 @@ static bool traj_handles_ok(mi_net* net, mi_batch* bc, mi_batch* bp) {
     return bc->H == net->H && bc->L == net->L && bp->H == net->H && bp->L == net->L;
 }
 
-// strided chains: the pair shares one time map (or has none), and a map has the call's T + 1 entries
+// strided chains: the pair shares one time map (or has none), and a map has the call's T + 1 entries; conditioned chains: the pair shares
+// one likelihood mask (or has none)
 static int traj_time_map_ok(const mi_batch* bc, const mi_batch* bp, int T) {
+    MI_TRY(likelihood_mask_same(bc, bp, "the two batch handles carry different likelihood masks (mi_batch_set_likelihood_mask: both, and the same, or neither)"));
     MI_TRY(time_map_same(bc, bp, "the two batch handles carry different time maps"));
     return time_map_check(bc, T, "the batch handle");
 }
@@ -383,7 +474,10 @@ struct KlArgs {
 
 // one 256-thread block per crystal, the thread-to-element maps and reduction trees of traj_logprob_kernel: no atomics, same bits every call.
 // Every difference is taken between the two predictions, never between the two rounded means.
-__global__ __launch_bounds__(256) void traj_pg_kl_kernel(KlArgs a) {
+// MASK: as traj_logprob_masked_kernel's -- the predictor's lattice, type and coordinate terms of the known elements leave the sums, their
+// derivatives are 0.f; the corrector coordinate term and the divisors stay.  traj_pg_kl_kernel is this body with MASK = false.
+template <bool MASK>
+__device__ __forceinline__ void traj_pg_kl_body(KlArgs a, LikMask m) {
     __shared__ float red[4];
     const int b = blockIdx.x, tid = threadIdx.x;
     const StepCoef c = load_coef(a.coef, a.t[b]);
@@ -400,6 +494,10 @@ __global__ __launch_bounds__(256) void traj_pg_kl_kernel(KlArgs a) {
         d = d - rintf(d);
         klc += (d * d) / (2.0f * c.std_corr_sq);
         a.dxc[idx] = d * kc;
+        if (MASK && m.known_coords[idx / 3]) {
+            a.dxp[idx] = 0.f;
+            continue;
+        }
         d = sp * (a.pxp_a[idx] - a.pxp_p[idx]);
         d = d - rintf(d);
         klp += (d * d) / (2.0f * c.std_pred_sq);
@@ -413,9 +511,13 @@ __global__ __launch_bounds__(256) void traj_pg_kl_kernel(KlArgs a) {
     float kll = 0.f;
     if (tid < 9) {
         const int idx = b * 9 + tid;
-        const float d = cc * (a.pl_a[idx] - a.pl_p[idx]);
-        kll = (d * d) / (2.0f * c.sigma_sq);
-        a.dl[idx] = d * cc / c.sigma_sq / 9.0f;
+        if (MASK && m.known_lattice[b]) {
+            a.dl[idx] = 0.f;
+        } else {
+            const float d = cc * (a.pl_a[idx] - a.pl_p[idx]);
+            kll = (d * d) / (2.0f * c.sigma_sq);
+            a.dl[idx] = d * cc / c.sigma_sq / 9.0f;
+        }
     }
     kll = block_sum_256(kll, red);
 
@@ -424,6 +526,10 @@ __global__ __launch_bounds__(256) void traj_pg_kl_kernel(KlArgs a) {
     const float kt = cc / c.sigma_sq / (float)MI_NUM_TYPES / cnt;
     float klt = 0.f;
     for (int i = n0 + wave; i < n1; i += 4) {
+        if (MASK && m.known_types[i]) {
+            for (int k = lane; k < MI_NUM_TYPES; k += 64) a.dt[(size_t)i * MI_NUM_TYPES + k] = 0.f;
+            continue;
+        }
         float s = 0.f;
         for (int k = lane; k < MI_NUM_TYPES; k += 64) {
             const size_t idx = (size_t)i * MI_NUM_TYPES + k;
@@ -448,6 +554,14 @@ __global__ __launch_bounds__(256) void traj_pg_kl_kernel(KlArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256) void traj_pg_kl_kernel(KlArgs a) {
+    traj_pg_kl_body<false>(a, LikMask{nullptr, nullptr, nullptr});
+}
+
+__global__ __launch_bounds__(256) void traj_pg_kl_masked_kernel(KlArgs a, LikMask m) {
+    traj_pg_kl_body<true>(a, m);
+}
+
 static int kl_buffers(mi_batch* bc, mi_batch* pb) {
     const size_t nt = (size_t)bc->N * MI_NUM_TYPES, nx = (size_t)bc->N * 3, nl = (size_t)bc->B * 9;
     MI_TRY(alloc_set(pb, {{&pb->kl_pxc, (size_t)pb->N * 3}}));
@@ -465,7 +579,11 @@ static int kl_launch(mi_batch* bc, mi_batch* bp, mi_batch* pb, const float* coef
     k.stats = stats + 4 * (size_t)bc->B;
     k.w0 = w_host[0], k.w1 = w_host[1], k.w2 = w_host[2];
     k.B = bc->B;
-    hipLaunchKernelGGL(traj_pg_kl_kernel, dim3(bc->B), dim3(256), 0, s, k);
+    if (bp->lik_on) {
+        hipLaunchKernelGGL(traj_pg_kl_masked_kernel, dim3(bc->B), dim3(256), 0, s, k, lik_mask(bp));
+    } else {
+        hipLaunchKernelGGL(traj_pg_kl_kernel, dim3(bc->B), dim3(256), 0, s, k);
+    }
     MI_KERNEL_CHECK();
     return MI_OK;
 }
@@ -589,6 +707,16 @@ int mi_traj_logprob_backward(mi_net* net, mi_batch* bc, mi_batch* bp, const floa
     return traj_seed_backward(net, bc, bp, g_logp, d_corr_l, d_corr_x, d_corr_t, nullptr, grad_theta, (hipStream_t)stream);
 }
 
+int mi_traj_read_derivatives(const mi_batch* b, float* dl, float* dx, float* dt, void* stream) {
+    MI_CHECK(b, MI_EINVAL, "null handle");
+    MI_CHECK(b->tr_dl && b->tr_dx && b->tr_dt, MI_ESTATE, "mi_traj_read_derivatives: no taped call has used this handle");
+    hipStream_t s = (hipStream_t)stream;
+    if (dl && b->B) MI_HIP(hipMemcpyAsync(dl, b->tr_dl, (size_t)b->B * 9 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (dx && b->N) MI_HIP(hipMemcpyAsync(dx, b->tr_dx, (size_t)b->N * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (dt && b->N) MI_HIP(hipMemcpyAsync(dt, b->tr_dt, (size_t)b->N * MI_NUM_TYPES * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return MI_OK;
+}
+
 int mi_traj_pg_step(mi_net* net, mi_batch* bc, mi_batch* bp, const float* coef_dev, int T, const float* time_freqs,
                     const float* traj_atom_types, const float* traj_frac, const float* traj_frac_mid, const float* traj_lattices,
                     const float* traj_lp_old, const int* t_host, const int* t_dev, const float* adv_dev, float clip_range,
@@ -611,6 +739,7 @@ int mi_traj_pg_kl_step(mi_net* net, mi_batch* bc, mi_batch* bp, mi_net* prior, m
     MI_CHECK(pb->H == prior->H && pb->L == prior->L, MI_EINVAL, "prior batch was created for a different network");
     MI_CHECK(same_counts(bc, pb), MI_EINVAL, "the prior's batch handle holds different atom counts");
     MI_TRY(time_map_same(bc, pb, "the prior's batch handle carries another time map than the agent's (a strided chain: both, and the same)"));
+    MI_TRY(likelihood_mask_same(bc, pb, "the prior's batch handle carries another likelihood mask than the agent's (a conditioned rollout: all three handles, and the same)"));
     MI_CHECK(prior->TD == net->TD, MI_EINVAL, "the prior's time embedding has %d dimensions, the agent's %d (one frequency table serves both)", prior->TD, net->TD);
     MI_CHECK(kl_coef >= 0.f, MI_EINVAL, "kl_coef = %g: must be >= 0", (double)kl_coef);
     MI_CHECK(prior->theta != nullptr, MI_ESTATE, "mi_net_set_params must run on the prior before it is evaluated");

@@ -279,7 +279,7 @@ class DiffCSPModule(nn.Module):
         pair.calls += 1   # every call overwrites what the pair holds: a pending backward of an earlier call must refuse (TrajLogProbFunction)
         return pair
 
-    def forward_logprb(self, state, step_lr=1e-5, condition=None):
+    def forward_logprb(self, state, step_lr=1e-5, condition=None, likelihood=None):
         """DiffCSPModule.forward_logprb (diffusion.py:158-227): re-evaluate one recorded step -- the corrector's network evaluation on
         (atom_types, frac_coords, lattices), the predictor's on frac_coords_mid -- under the current weights.  Returns
         (log_prob_l, log_prob_t, log_prob_x, (pred_l_corr, pred_x_corr, pred_t_corr)) like the reference, differentiable with respect
@@ -289,13 +289,17 @@ class DiffCSPModule(nn.Module):
         for every crystal.  The two agree whenever the timesteps are equal -- the only case sample_mdp produces.  t must lie in 2..T
         (ValueError otherwise; the reference's formulas give inf / NaN at t = 1).  One pending backward per atom-count vector: a later
         call with the same atom counts overwrites the tapes, and the earlier call's backward then raises instead of returning wrong
-        gradients.  A `condition` is refused (ValueError): the log-probability of a conditioned transition is not modelled."""
-        if condition is not None:
+        gradients.  A `condition` alone is refused (ValueError): the unmasked sums are not a conditioned chain's likelihood.
+        condition=c, likelihood="free" (DESIGN 36): `state` is a step of a chain sampled under `c` (for the crystals of `state`), and the
+        predictor terms of c's known elements leave the three log-probabilities and their gradients -- the trajectory likelihood of the
+        conditioned chain up to a constant of theta.  The handle pair carries c's masks for the call alone (one device synchronisation)."""
+        from .conditioning import check_likelihood
+        masked = check_likelihood("forward_logprb", likelihood, condition)
+        if condition is not None and not masked:
             raise ValueError("forward_logprb: a condition is not supported -- the recorded log-probabilities of a conditioned chain are those "
                              "of the unconditioned proposal, not a trajectory likelihood")
         for k, v in state.items():   # (the reference moves the caller's tensors to the device in place, :159-160)
             state[k] = v.to(self.device)
-        dev = self.device
         T = self.beta_scheduler.timesteps
         times = state["timesteps"].to(torch.int32)
         th = times.cpu()
@@ -303,7 +307,16 @@ class DiffCSPModule(nn.Module):
             raise ValueError(f"forward_logprb: timesteps must lie in 2..{T} (got {int(th.min())}..{int(th.max())}); the reference's "
                              "formulas give inf / NaN at t = 1")
         num_atoms = state["num_atoms"]
+        if masked and [int(v) for v in condition.num_atoms.tolist()] != [int(v) for v in num_atoms.tolist()]:
+            raise ValueError("forward_logprb: the condition's atom counts are not the state's")
         pair = self._traj_batches(num_atoms)
+        batches = pair.handles
+        with self._conditioned([(cb, condition) for cb in batches] if masked else [], condition=False, likelihood=masked):
+            return self._forward_logprb(state, step_lr, pair, times, T)
+
+    def _forward_logprb(self, state, step_lr, pair, times, T):
+        """forward_logprb after its checks, on the handle pair `pair` (which carries a likelihood mask or none)."""
+        dev = self.device
         batches = pair.handles
         B, N = batches[0].num_graphs, batches[0].num_nodes
         f = lambda k: state[k].detach().to(dev, torch.float32).contiguous()
@@ -354,7 +367,7 @@ class DiffCSPModule(nn.Module):
 
     @torch.no_grad()
     def sample(self, batch, diff_ratio=1.0, step_lr=1e-5, seed=0, noise=None, init=None, record=False, t_start=None,
-               t_stop=0, node_offset=0, graph_offset=0, streams=None, rec_sink=None, condition=None):
+               t_stop=0, node_offset=0, graph_offset=0, streams=None, rec_sink=None, condition=None, likelihood=None):
         """DiffCSPModule.sample (diffusion.py:273-399).
 
         `rec_sink` (a list; with record=True): receives one (first crystal, first atom, buffers) per chain, in crystal order -- the
@@ -376,14 +389,21 @@ class DiffCSPModule(nn.Module):
         call's first launch, none inside the chain).  With record=True the CONDITIONED states are recorded; the recorded log-probabilities
         are then those of the unconditioned proposal of each step -- not a trajectory likelihood, which is why sample_mdp, sample_rollout
         and forward_logprb refuse a condition.  CSP mode together with a condition is refused by the library (MI_EINVAL).
+
+        `likelihood` = "free" (with a condition): the chain's handles also carry the condition's masks as their likelihood
+        mask for this call, and a recording chain records the log-probabilities with the predictor terms of the known elements left
+        out -- the conditioned chain's trajectory likelihood up to a constant of the weights.  The states are those of the same call
+        without the keyword, bit for bit.  None (the default): the record of the unconditioned proposal, as above.
         """
+        from .conditioning import check_likelihood
+        lik = check_likelihood("sample", likelihood, condition)
         if condition is not None and [int(v) for v in condition.num_atoms.tolist()] != [int(v) for v in batch.num_atoms.tolist()]:
             raise ValueError("sample: the condition's atom counts are not the batch's")
         if self.__dict__.get("_knn_pending"):
             self.check_graph()   # (the verdict of the previous call's chains: by now they have long finished)
         if isinstance(batch, CrystalBatch):
             return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink,
-                                    condition=condition)
+                                    condition=condition, likelihood=lik)
         if (self.keep_lattice or self.keep_coords) and init is None and condition is None:
             # CSP mode (diffusion.py:283-287): the known part of the structure replaces the drawn initial state and is never moved
             cb0 = self.crystal_batch(batch, node_offset, graph_offset)
@@ -406,7 +426,7 @@ class DiffCSPModule(nn.Module):
         streams = max(1, min(int(streams), len(na)))
         if streams == 1:
             return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink,
-                                    condition=condition)
+                                    condition=condition, likelihood=lik)
         key = ("split", streams, tuple(na))
         parts = getattr(batch, "_mi_split", {}).get(key)
         if parts is None:  # contiguous crystal groups, cached on the batch object like its CrystalBatch
@@ -454,7 +474,7 @@ class DiffCSPModule(nn.Module):
         # the chains), and cleared when all of them are: each group gets its crystals' slice
         conds = [] if condition is None else [(self.crystal_batch(parts[k], node_offset + n0[k], graph_offset + g0[k]), condition.slice(g0[k], g0[k + 1]))
                                               for k in range(streams)]
-        with self._conditioned(conds):
+        with self._conditioned(conds, likelihood=lik):
             out = workers.run(run, streams)
         if rec_sink is not None:
             for k, sk in enumerate(sinks):
@@ -498,10 +518,11 @@ class DiffCSPModule(nn.Module):
             _lib.check(lib.mi_knn_graph_status(cb._h, C.c_void_p(stream.cuda_stream)), "mi_knn_graph_status")
 
     @contextlib.contextmanager
-    def _conditioned(self, pairs):
+    def _conditioned(self, pairs, condition=True, likelihood=False):
         """Attach each (batch handle, Condition) of `pairs` for the duration of the block and clear the handles afterwards, whatever happens
         inside: the cached handles of `crystal_batch` must not carry a condition into a later call.  The device is drained once first --
-        an earlier chain of a cached handle may still be reading the arrays the attach overwrites."""
+        an earlier chain of a cached handle may still be reading the arrays the attach overwrites.  `condition`: the condition itself
+        (values and level table); `likelihood`: its masks as the handle's likelihood mask; either or both."""
         if not pairs:
             yield
             return
@@ -509,14 +530,20 @@ class DiffCSPModule(nn.Module):
         torch.cuda.synchronize(self.device)
         try:
             for cb, c in pairs:
-                c.attach(self, cb)
+                if condition:
+                    c.attach(self, cb)
+                if likelihood:
+                    c.attach_likelihood(self, cb)
             yield
         finally:
             for cb, _ in pairs:
-                Condition.clear(cb)
+                if condition:
+                    Condition.clear(cb)
+                if likelihood:
+                    Condition.clear_likelihood(cb)
 
     def _sample_one(self, batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, inplace=None, drawn=False,
-                    rec_sink=None, condition=None):
+                    rec_sink=None, condition=None, likelihood=False):
         """One chain over one CrystalBatch on the current stream.
 
         Returns (traj[t_stop], traj) like the reference.  `traj` holds every step only when
@@ -559,7 +586,7 @@ class DiffCSPModule(nn.Module):
                          frac_coords_mid=z(T + 1, N, 3), log_prob_l=z(T + 1, B), log_prob_t=z(T + 1, B), log_prob_x=z(T + 1, B))
             rec = _lib.SamplerRecord(*(rec_t[k].data_ptr() for k in ("atom_types", "frac_coords", "lattices", "frac_coords_mid",
                                                                      "log_prob_l", "log_prob_t", "log_prob_x")))
-        with self._conditioned([] if condition is None else [(cb, condition)]):
+        with self._conditioned([] if condition is None else [(cb, condition)], likelihood=likelihood):
             _lib.check(lib.mi_sampler_run(self.decoder._h, cb._h, coef.numpy().ctypes.data_as(C.POINTER(C.c_float)), T, t_start, t_stop,
                                           _ptr(self.time_embedding.freqs), seed, C.byref(nz) if nz is not None else None,
                                           C.byref(rec) if rec is not None else None, _ptr(a), _ptr(x), _ptr(l), _stream()),

@@ -207,7 +207,11 @@ class MatInventPG(MatInvent):
     so replay=True is refused.  Single GPU, DiffCSP only (MatterGen has no log-probability path), one sampling batch per loop.
     finetune_cfg.kl_coef > 0 anchors the agent's transitions to the frozen prior's (policy.pg_step) and logs prior_kl.
     sample_cfg.sample_steps = S: rollout and training run through strided views of agent and prior and `rollout steps` is logged.
-    sample_cfg.target_compositions_dict / condition (conditioned sampling) are refused: MatInvent has them."""
+    sample_cfg.target_compositions_dict / condition (conditioned sampling) are refused by default: the record of a conditioned
+    chain is not its likelihood.  sample_cfg.condition_likelihood: free lifts the refusal: the condition is built as
+    DiffCSPSampler.generate builds it (target_compositions_dict: batch_size crystals cycling through the list, every atom type fixed; or an
+    explicit conditioning.Condition for batch_size crystals), the rollout records -- and pg_step re-evaluates -- the likelihood over the
+    free elements, and the condition follows the kept crystals through the filters and max_num."""
 
     def __init__(self, rl_epoch, model_suite, reward, sample_cfg, finetune_cfg, save_dir, save_freq=50, device=None, logger=None,
                  replay=False, replay_args=None, topk_ratio=1.0, **kwargs):
@@ -220,8 +224,13 @@ class MatInventPG(MatInvent):
         if rank_world()[1] > 1:
             raise ValueError("MatInventPG runs on one GPU: world_size > 1 is not supported")
         merged = C.merge(model_suite.sample_cfg, sample_cfg)
+        lik = merged.get("condition_likelihood")
+        if lik not in (None, "free"):
+            raise ValueError(f"MatInventPG: sample_cfg.condition_likelihood = {lik!r} is neither null nor 'free'")
+        if lik is not None and merged.get("target_compositions_dict") is not None and merged.get("condition") is not None:
+            raise ValueError("MatInventPG: give sample_cfg.target_compositions_dict or sample_cfg.condition, not both")
         for k in ("target_compositions_dict", "condition"):
-            if merged.get(k) is not None:
+            if merged.get(k) is not None and lik is None:
                 raise ValueError(f"MatInventPG: sample_cfg.{k} is not supported -- a conditioned chain's recorded log-probabilities are those "
                                  "of the unconditioned proposal, not a trajectory likelihood (use pipeline=mat_invent)")
         if kwargs.get("div_filter"):
@@ -234,13 +243,27 @@ class MatInventPG(MatInvent):
                          topk_ratio=topk_ratio, save_dir=save_dir, save_freq=save_freq, device=device, logger=logger, replay=False,
                          replay_args=None, **kwargs)
 
+    def _condition_kwargs(self):
+        """sample_rollout's condition / likelihood keywords from sample_cfg (condition_likelihood: free), or none."""
+        lik = self.sample_cfg.get("condition_likelihood")
+        targets, cond = self.sample_cfg.get("target_compositions_dict"), self.sample_cfg.get("condition")
+        if targets is not None and len(targets) == 0:
+            targets = None
+        if lik is None or (targets is None and cond is None):
+            return {}
+        if targets is not None:   # as DiffCSPSampler.generate: the crystals cycle through the list, every atom type fixed
+            from .conditioning import Condition
+            cond = Condition.composition([dict(t) for t in targets], int(self.sample_cfg.batch_size))
+        return dict(condition=cond, likelihood=lik)
+
     def sample_step(self):
         """Rollout + the MatInvent sample step's filtering.  Returns (data, strucs, rollout restricted to data, metrics)."""
         from .data import data2struc
         from .sampling import sample_rollout
         self.sampler.seed += 1
         data, rollout = sample_rollout(int(self.sample_cfg.batch_size), self.agent, seed=self.sampler.seed,
-                                       geometric_filter=bool(self.sample_cfg.get("geometric_filter", True)), sample_steps=self.sample_steps)
+                                       geometric_filter=bool(self.sample_cfg.get("geometric_filter", True)), sample_steps=self.sample_steps,
+                                       **self._condition_kwargs())
         strucs = [data2struc(d) for d in data]
         logging.info(f"rollout kept {len(data)} samples" + (f" over {rollout.T} steps" if self.sample_steps is not None else ""))
         if getattr(self, "sample_dir", None):

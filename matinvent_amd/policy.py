@@ -68,7 +68,10 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
     read in the same transfer as the rest.
     A strided chain: `agent` a view made by DiffCSPModule.respaced and `rollout` recorded through it -- T is then the view's S,
     the draws come from 2..S and every time is a step index; with kl_coef > 0 `prior` must be a view on the same grid.  The optimiser
-    steps land in the view's base module: they share theta."""
+    steps land in the view's base module: they share theta.
+    A conditioned rollout: when rollout.condition is set (sample_rollout(..., condition=c, likelihood="free")) the call's
+    handles -- the agent pair and, with kl_coef > 0, the prior's -- carry its masks as their likelihood mask from before the first
+    micro-step until the return: log-probabilities, KL terms and gradients leave out the predictor terms of the known elements."""
     opt = clip_options(cfg)
     lr, epochs = float(cfg_get(cfg, "lr")), int(cfg_get(cfg, "epochs"))
     timesteps, accum_steps = int(cfg_get(cfg, "timesteps")), int(cfg_get(cfg, "accum_steps"))
@@ -117,6 +120,10 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
         theta.grad = torch.zeros_like(theta)
     stats = torch.zeros(5 if use_kl else 4, B, device=dev)
     handles = (b_corr, b_pred)
+    cond = getattr(rollout, "condition", None)
+    if cond is not None:                                                           # fresh handles, nothing in flight on them: blocking copies, once per call
+        for cb in handles + ((b_prior,) if use_kl else ()):
+            cond.attach_likelihood(agent, cb)
     if use_kl:                                                                     # the micro-step of this call, chosen once
         micro_step = lambda th, td: pg_kl_micro_step(agent, handles, prior, b_prior, rollout, th, td, adv, clip_range, w_host, kl_coef, 1.0 / M,
                                                      theta.grad, stats, aux_stream=aux)

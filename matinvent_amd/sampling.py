@@ -210,7 +210,9 @@ class Rollout:
     """The kept crystals' reverse-diffusion chains on the device, stacked over t = 0..T (index t = the state at diffusion time t):
     atom_types [T+1, N, 100], frac_coords / frac_coords_mid [T+1, N, 3], lattices [T+1, B, 9], lp_old [T+1, B, 3] = the sampler's own
     recorded (log_prob_l, log_prob_t, log_prob_x) of the step t -> t-1 (defined for t = 2..T).  num_atoms: host long [B]; node_offsets:
-    host long [B+1]; step_lr: the step size the chain ran with (mi_traj_pg_step re-evaluates with the same one)."""
+    host long [B+1]; step_lr: the step size the chain ran with (mi_traj_pg_step re-evaluates with the same one).  condition: None, or
+    the conditioning.Condition of the kept crystals when the chain was sampled with likelihood="free" -- lp_old is then the masked record
+    and policy.pg_step re-evaluates under the same masks."""
     atom_types: torch.Tensor
     frac_coords: torch.Tensor
     frac_coords_mid: torch.Tensor
@@ -220,6 +222,7 @@ class Rollout:
     node_offsets: torch.Tensor
     T: int
     step_lr: float
+    condition: Optional[object] = None
 
     @property
     def num_graphs(self):
@@ -237,26 +240,36 @@ class Rollout:
         na = self.num_atoms[gi]
         return Rollout(self.atom_types.index_select(1, ad), self.frac_coords.index_select(1, ad), self.frac_coords_mid.index_select(1, ad),
                        self.lattices.index_select(1, gd), self.lp_old.index_select(1, gd), na,
-                       torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(na, 0)]), self.T, self.step_lr)
+                       torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(na, 0)]), self.T, self.step_lr,
+                       None if self.condition is None else self.condition.select(idx))
 
 
-def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=True, sample_steps=None, condition=None):
+def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=True, sample_steps=None, condition=None, likelihood=None):
     """Sample like sample_mdp (same atom-count draw, seed handling and invalid_filter; geometric_filter=False keeps every crystal) and
     keep the kept crystals' whole trajectories on the device as a Rollout -- compacted once per chain straight from the sampler's stacked
     record buffers, without the per-step dict or a host copy.  Returns (sample_list, rollout).  The policy gradient (policy.pg_step)
     consumes it.  CSP mode (keep_lattice / keep_coords) is refused: forward_logprb does not model it.
     A strided view (DiffCSPModule.respaced), or sample_steps = S which builds it: rollout.T = S, the arrays are [S + 1, ...] and index k is
-    the state at step index k (trained time tau_k); pg_step then takes the same view as its agent.  A `condition` is refused (ValueError),
-    like CSP mode."""
+    the state at step index k (trained time tau_k); pg_step then takes the same view as its agent.  A `condition` alone is refused
+    (ValueError), like CSP mode.
+    condition=c (for `sample_size` crystals), likelihood="free" (DESIGN 36): the chains are conditioned on c, whose atom counts replace the
+    draw; rollout.lp_old is the masked record (the predictor terms of the known elements left out) and rollout.condition the kept
+    crystals' part of c, which pg_step re-evaluates under.  CSP mode stays refused."""
+    from .conditioning import check_likelihood
     from .filters import invalid_filter
-    _refuse_condition("sample_rollout", condition)
+    if not check_likelihood("sample_rollout", likelihood, condition):
+        _refuse_condition("sample_rollout", condition)
+    elif len(condition) != int(sample_size):
+        raise ValueError(f"sample_rollout: the condition covers {len(condition)} crystals, sample_size is {sample_size}")
     model = _strided(model, sample_steps)
     if getattr(model, "keep_lattice", False) or getattr(model, "keep_coords", False):
         raise ValueError("sample_rollout: CSP mode (keep_lattice / keep_coords) is not supported -- forward_logprb does not model a given "
                          "lattice or given coordinates")
     counts, step_lr = _prelude(sample_size, model, step_lr)
+    if condition is not None:   # (the atom counts are the condition's; the draw above is made all the same, so the global generator moves as without one)
+        counts = _AtomCounts(condition.num_atoms)
     sink = []
-    outputs, _ = model.sample(counts, step_lr=step_lr, seed=_draw_seed(seed), record=True, rec_sink=sink)
+    outputs, _ = model.sample(counts, step_lr=step_lr, seed=_draw_seed(seed), record=True, rec_sink=sink, condition=condition, likelihood=likelihood)
     data_list = _unpack(model, counts, outputs)
     valid = invalid_filter(data_list, return_mask=True) if geometric_filter else np.ones(len(data_list), dtype=bool)
     sample_list = [d for d, ok in zip(data_list, valid) if ok]
@@ -280,5 +293,6 @@ def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=T
     st = {k: (v[0] if len(v) == 1 else torch.cat(v, dim=1)) for k, v in parts.items()}
     kept = na[valid]
     rollout = Rollout(st["atom_types"], st["frac_coords"], st["frac_coords_mid"], st["lattices"], st["lp_old"], kept,
-                      torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(kept, 0)]), T, float(step_lr))
+                      torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(kept, 0)]), T, float(step_lr),
+                      None if condition is None else condition.select(torch.nonzero(valid).flatten().tolist()))
     return sample_list, rollout

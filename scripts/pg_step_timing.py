@@ -2,12 +2,15 @@
 C entry (policy.pg_micro_step = mi_traj_pg_step: gather, two taped evaluations, surrogate and seeds, backward) against the unfused
 composition on the same draws (torch indexing of the rollout, forward_logprb, the surrogate in torch, autograd).
 
-    python scripts/pg_step_timing.py [--crystals 64,256] [--iters 10] [--logratio] [--sample-steps S] [--json OUT]
+    python scripts/pg_step_timing.py [--crystals 64,256] [--iters 10] [--logratio] [--sample-steps S] [--conditioned] [--json OUT]
 
 Prints one JSON line per batch size: ms per micro-step and crystal-timesteps/s for both paths, next to DESIGN 21's forward_logprb + backward
 (9.2 ms at 64 crystals, 20.7 ms at 256).  --logratio also re-evaluates EVERY step t = 2..T of the rollout at unchanged weights and reports the
 largest |log rho| (the sampler's recorded log-probabilities against the re-evaluation: pure rounding), per term and for w = (1, 1, 1).
 --sample-steps S runs all of it on the strided chain of S of the T steps (DiffCSPModule.respaced): rollout, draws and re-evaluation.
+--conditioned also times the same micro-step on a handle pair that carries a likelihood mask (every atom type known, every
+second atom's coordinates, every second crystal's lattice) and prints ms_masked beside ms_fused of the same build -- the masked kernels
+do the unmasked kernels' work less the skipped terms, on the same rollout (its record is not the masked one: this is a timing, not a ratio).
 Under `rocprofv3 --kernel-trace --stats -- python scripts/pg_step_timing.py ...` the stats file gives the gather and surrogate kernels' share
 (traj_pg_gather_kernel, traj_pg_surrogate_kernel)."""
 import argparse
@@ -62,6 +65,7 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--logratio", action="store_true")
     ap.add_argument("--sample-steps", type=int, default=None, help="run on the strided chain of this many of the T = 1000 steps")
+    ap.add_argument("--conditioned", action="store_true", help="also time the micro-step under a likelihood mask")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     H, L, F, T = 512, 6, 128, 1000
@@ -89,6 +93,23 @@ def main():
             policy.pg_micro_step(m, handles, ro, draws[i], draws_dev[i], A, eps, w, 1.0 / M, grad, stats)
 
         ms_fused = timed(fused, a.iters)
+        ms_masked = None
+        if a.conditioned:
+            from matinvent_amd.conditioning import Condition
+            N = sum(na)
+            cond = Condition(na, atom_types=torch.ones(N, dtype=torch.long), known_types=torch.ones(N, dtype=torch.bool),
+                             frac_coords=torch.zeros(N, 3), known_coords=torch.arange(N) % 2 == 0, lattices=torch.zeros(B, 3, 3),
+                             known_lattice=torch.arange(B) % 2 == 0)
+            masked = (m.make_batch(na), m.make_batch(na))
+            for h in masked:
+                cond.attach_likelihood(m, h)
+
+            def fused_masked(i=0):
+                policy.pg_micro_step(m, masked, ro, draws[i], draws_dev[i], A, eps, w, 1.0 / M, grad, stats)
+
+            ms_masked = timed(fused_masked, a.iters)
+            ms_fused = min(ms_fused, timed(fused, a.iters))   # (the unmasked step once more, after the masked one: same build, same box, interleaved)
+            del masked
         ar_n, ar_b = torch.arange(sum(na), device="cuda"), torch.arange(B, device="cuda")
         nat = ro.num_atoms.cuda()
 
@@ -110,6 +131,8 @@ def main():
         row = dict(crystals=B, atoms=a.atoms, chain_steps=T, ms_fused=round(ms_fused, 3), ms_unfused=round(ms_unfused, 3),
                    fused_over_unfused=round(ms_fused / ms_unfused, 4), crystal_timesteps_per_s_fused=round(B / ms_fused * 1e3, 1),
                    crystal_timesteps_per_s_unfused=round(B / ms_unfused * 1e3, 1), design21_forward_logprb_backward_ms=DESIGN21_MS.get(B))
+        if ms_masked is not None:
+            row.update(ms_masked=round(ms_masked, 3), masked_over_unmasked=round(ms_masked / ms_fused, 4))
         if a.logratio:
             # every step of the chain at unchanged weights: the largest |lp_new - lp_old| per term and for w = 1
             lp = torch.empty(3, B, device="cuda")
