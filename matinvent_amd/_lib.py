@@ -240,9 +240,17 @@ MATCH_SIGNATURES = {
     "mi_fp_match": (_I, [C.POINTER(FpMatchArgs), _P]),
 }
 
+# the resampling extension, include/matinvent_hip_resample.h (RePaint's jumps for the conditioned chain: a batch handle's (r, j) and jump table)
+RESAMPLE_SIGNATURES = {
+    "mi_batch_set_resampling": (_I, [_P, C.POINTER(C.c_float), _I, _I, _I]),
+    "mi_resample_jump": (_I, [_P, _I, _U64, _P, _P, _P, _P]),
+    "mi_resample_schedule": (_L, [_I, _I, _I, C.POINTER(_I), _L]),
+    "mi_resample_visit_seed": (_U64, [_U64, _U32]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
-                        DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES)
+                        DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES)
 
 _lib = None
 

@@ -184,6 +184,8 @@ enum : uint32_t {
     DRAW_FT_L = 7, DRAW_FT_X = 8, DRAW_FT_T = 9,
     // (10 .. 20: the MatterGen-shaped path, gemnet.hip)
     DRAW_COND_L = 21, DRAW_COND_X = 22, DRAW_COND_T = 23,   // replacement conditioning (condition.hip); step field = the noise level
+    DRAW_JUMP_L = 24, DRAW_JUMP_X = 25, DRAW_JUMP_T = 26,   // resampling jumps (resample.hip); step field = the level jumped TO
+    DRAW_VISIT = 27,                                        // ... and the per-visit seed: counter (0, 0, 27, v) under the chain's seed
 };
 
 }  // namespace mi

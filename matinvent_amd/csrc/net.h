@@ -223,6 +223,13 @@ struct mi_batch {
     bool lik_on = false;
     int *lik_kt = nullptr, *lik_kx = nullptr, *lik_kl = nullptr;      // [N], [N], [B] 0 / 1 (allocated on first use)
     std::vector<int> lik_h;                                           // host copy [N | N | B]: comparison between the handles of a call
+    // resampling jumps of a conditioned chain (resample.hip, mi_batch_set_resampling): r visits per jump-off level, jumps of j
+    // levels, and the jump table on the device
+    bool rs_on = false;
+    int rs_r = 1, rs_j = 0;
+    int rs_levels = 0;             // rows of rs_table (= T + 1 of the chains it is for)
+    int rs_table_cap = 0;
+    float* rs_table = nullptr;     // [rs_levels][3] = (c0, c1, s) of the jump a -> a + j; rows with a + j > T are zero
     // preference pairs (dpo.hip, mi_batch_set_pairs): (winner, loser) crystal indices, and per crystal the list of its pair slots in
     // ascending pair index -- entry 2 p: crystal is pair p's winner, 2 p + 1: its loser
     int n_pairs = 0, pairs_cap = 0;
@@ -305,6 +312,13 @@ int likelihood_mask_same(const mi_batch* p, const mi_batch* q, const char* what)
 // ... and the masked form of the sampler's predictor launch (logprob.h: PredictorArgs), for a recording chain on a handle with a condition and a mask
 struct PredictorArgs;
 int predictor_masked_launch(const mi_batch* b, const PredictorArgs& a, hipStream_t s);
+// resample.hip: mi_sampler_run's host-side check of a handle with resampling (MI_EINVAL with the message set), the visited levels of a
+// resampled chain (the one definition: mi_resample_schedule and the chain's driver read it), the per-visit seed and the forward jump
+// from `from_level` to from_level + j (one launch)
+int resample_check(const mi_batch* b, int T, int t_start, int t_stop, bool has_noise, bool has_rec, const char* what);
+int resample_levels(int t_start, int r, int j, std::vector<int>* levels);
+uint64_t resample_visit_seed(uint64_t seed, uint32_t v);
+int resample_jump(const mi_batch* b, int from_level, uint64_t seed, float* atom_types, float* frac, float* lattices, hipStream_t s);
 extern int g_knn_nosync;
 int knn_build(mi_batch* b, const float* frac, const float* lattices, hipStream_t s, bool nosync = false);
 }  // namespace mi

@@ -8,6 +8,8 @@
 
 #include <string.h>
 
+#include <vector>
+
 #include "net.h"
 #include "logprob.h"
 
@@ -175,6 +177,66 @@ __global__ void wrap_inplace_kernel(float* x, int64_t n) {
 
 using namespace mi;
 
+// One reverse step t -> t - 1 of the chain under `seed`: corrector, predictor and, on a handle with a condition, the imposition at t - 1
+// (the body of mi_sampler_run's loop; a resampled chain calls it in schedule order with the visit seeds)
+static int sampler_step(mi_net* net, mi_batch* b, int t, uint64_t seed, const float* time_freqs, const mi_sampler_noise* noise,
+                        const mi_sampler_record* rec, float* atom_types, float* frac, float* lattices, hipStream_t s) {
+    const int N = b->N, B = b->B;
+    const size_t n3 = (size_t)N * 3, nA = (size_t)N * MI_NUM_TYPES, b9 = (size_t)B * 9;
+    TraceRange range("mi_sampler_step");
+    if (b->time_map) {   // a strided chain: t is the step index, the network sees the trained time map[t]
+        MI_TRY(time_embedding_mapped(b, nullptr, t, time_freqs, B, net->TD, b->temb, s));
+    } else {
+        hipLaunchKernelGGL(time_embedding_kernel, dim3(cdiv((int64_t)B * net->TD, 256)), dim3(256), 0, s, (const int*)nullptr, time_freqs, b->temb, B,
+                           net->TD, t);
+    }
+    // corrector
+    // (the Langevin corrector reads the coordinate score alone, diffusion.py:310-322: the type columns of the heads and the lattice head are not evaluated)
+    MI_TRY(net_forward(net, b, b->temb, atom_types, frac, lattices, b->pred_l, b->pred_x, b->pred_t, s, false, false, true));
+    hipLaunchKernelGGL(corrector_kernel, dim3(B), dim3(64), 0, s, frac, b->pred_x, noise ? noise->corr_x + t * n3 : nullptr,
+                       b->coef, t, seed, b->node_offset, b->node_off, b->x_mid, (rec && rec->log_prob_x) ? b->lp_corr : nullptr,
+                       (rec && rec->frac_coords_mid) ? rec->frac_coords_mid + t * n3 : nullptr, b->keep_coords);
+    MI_KERNEL_CHECK();
+    // predictor
+    // the corrector moved the coordinates only (diffusion.py:320-322): layer-0 node features are those of the evaluation above
+    MI_TRY(net_forward(net, b, b->temb, atom_types, b->x_mid, lattices, b->pred_l, b->pred_x, b->pred_t, s, false, true));
+    PredictorArgs a;
+    a.x_mid = b->x_mid;
+    a.pred_x = b->pred_x;
+    a.pred_l = b->pred_l;
+    a.pred_t = b->pred_t;
+    a.noise_x = noise ? noise->pred_x + t * n3 : nullptr;
+    a.noise_l = noise ? noise->pred_l + t * b9 : nullptr;
+    a.noise_t = noise ? noise->pred_t + t * nA : nullptr;
+    a.coef = b->coef;
+    a.node_off = b->node_off;
+    a.lp_corr = b->lp_corr;
+    a.frac = frac;
+    a.lattices = lattices;
+    a.atom_types = atom_types;
+    a.rec_types = (rec && rec->atom_types) ? rec->atom_types + (t - 1) * nA : nullptr;
+    a.rec_frac = (rec && rec->frac_coords) ? rec->frac_coords + (t - 1) * n3 : nullptr;
+    a.rec_lat = (rec && rec->lattices) ? rec->lattices + (t - 1) * b9 : nullptr;
+    a.rec_lpl = (rec && rec->log_prob_l) ? rec->log_prob_l + (size_t)t * B : nullptr;
+    a.rec_lpt = (rec && rec->log_prob_t) ? rec->log_prob_t + (size_t)t * B : nullptr;
+    a.rec_lpx = (rec && rec->log_prob_x) ? rec->log_prob_x + (size_t)t * B : nullptr;
+    a.seed = seed;
+    a.node_offset = b->node_offset;
+    a.graph_offset = b->graph_offset;
+    a.t = t;
+    a.keep_lattice = b->keep_lattice;
+    a.keep_coords = b->keep_coords;
+    if (b->cond_on && b->lik_on && rec) {   // the record of a conditioned chain's likelihood (condition.hip)
+        MI_TRY(predictor_masked_launch(b, a, s));
+    } else {
+        hipLaunchKernelGGL(predictor_kernel, dim3(B), dim3(256), 0, s, a);
+        MI_KERNEL_CHECK();
+    }
+    // ... and at the level the step arrived at: the known elements of the state and of its record are overwritten (the corrector is left alone)
+    if (b->cond_on) MI_TRY(condition_impose(b, t - 1, seed, atom_types, frac, lattices, a.rec_types, a.rec_frac, a.rec_lat, s));
+    return MI_OK;
+}
+
 extern "C" {
 
 int mi_time_embedding(const int* times, const float* freqs, int B, int time_dim, float* out, void* stream) {
@@ -214,6 +276,7 @@ int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int 
              t_start, t_stop);
     MI_TRY(time_map_check(b, T, "the batch handle"));
     MI_TRY(condition_check(b, T, "the batch handle"));
+    MI_TRY(resample_check(b, T, t_start, t_stop, noise != nullptr, rec != nullptr, "the batch handle"));
     hipStream_t s = (hipStream_t)stream;
     const int N = b->N, B = b->B;
     if (N == 0 || B == 0) return MI_OK;
@@ -246,59 +309,23 @@ int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int 
         explicit NoSyncScope(mi_batch* b_) : b(b_) { b->knn_nosync = true; }
         ~NoSyncScope() { b->knn_nosync = false; }
     } nosync_scope(b);
-    for (int t = t_start; t > t_stop; --t) {
-        TraceRange range("mi_sampler_step");
-        if (b->time_map) {   // a strided chain: t is the step index, the network sees the trained time map[t]
-            MI_TRY(time_embedding_mapped(b, nullptr, t, time_freqs, B, net->TD, b->temb, s));
-        } else {
-            hipLaunchKernelGGL(time_embedding_kernel, dim3(cdiv((int64_t)B * net->TD, 256)), dim3(256), 0, s, (const int*)nullptr, time_freqs, b->temb, B,
-                               net->TD, t);
+    if (b->rs_on && b->rs_r > 1) {
+        // resampling jumps (resample.hip): the visited levels in schedule order -- a level below the last is a reverse step, a level
+        // above it a forward jump -- each repetition of a transition, and each jump off a level, under its own visit seed
+        std::vector<int> levels;
+        MI_TRY(resample_levels(t_start, b->rs_r, b->rs_j, &levels));
+        std::vector<uint32_t> steps_done((size_t)t_start + 1, 0), jumps_done((size_t)t_start + 1, 0);
+        for (size_t k = 1; k < levels.size(); ++k) {
+            const int from = levels[k - 1], to = levels[k];
+            if (to == from - 1) {
+                MI_TRY(sampler_step(net, b, from, resample_visit_seed(seed, steps_done[(size_t)from]++), time_freqs, noise, rec, atom_types, frac, lattices, s));
+            } else {
+                MI_TRY(resample_jump(b, from, resample_visit_seed(seed, ++jumps_done[(size_t)from]), atom_types, frac, lattices, s));
+            }
         }
-        // corrector
-        // (the Langevin corrector reads the coordinate score alone, diffusion.py:310-322: the type columns of the heads and the lattice head are not evaluated)
-        MI_TRY(net_forward(net, b, b->temb, atom_types, frac, lattices, b->pred_l, b->pred_x, b->pred_t, s, false, false, true));
-        hipLaunchKernelGGL(corrector_kernel, dim3(B), dim3(64), 0, s, frac, b->pred_x, noise ? noise->corr_x + t * n3 : nullptr,
-                           b->coef, t, seed, b->node_offset, b->node_off, b->x_mid, (rec && rec->log_prob_x) ? b->lp_corr : nullptr,
-                           (rec && rec->frac_coords_mid) ? rec->frac_coords_mid + t * n3 : nullptr, b->keep_coords);
-        MI_KERNEL_CHECK();
-        // predictor
-        // the corrector moved the coordinates only (diffusion.py:320-322): layer-0 node features are those of the evaluation above
-        MI_TRY(net_forward(net, b, b->temb, atom_types, b->x_mid, lattices, b->pred_l, b->pred_x, b->pred_t, s, false, true));
-        PredictorArgs a;
-        a.x_mid = b->x_mid;
-        a.pred_x = b->pred_x;
-        a.pred_l = b->pred_l;
-        a.pred_t = b->pred_t;
-        a.noise_x = noise ? noise->pred_x + t * n3 : nullptr;
-        a.noise_l = noise ? noise->pred_l + t * b9 : nullptr;
-        a.noise_t = noise ? noise->pred_t + t * nA : nullptr;
-        a.coef = b->coef;
-        a.node_off = b->node_off;
-        a.lp_corr = b->lp_corr;
-        a.frac = frac;
-        a.lattices = lattices;
-        a.atom_types = atom_types;
-        a.rec_types = (rec && rec->atom_types) ? rec->atom_types + (t - 1) * nA : nullptr;
-        a.rec_frac = (rec && rec->frac_coords) ? rec->frac_coords + (t - 1) * n3 : nullptr;
-        a.rec_lat = (rec && rec->lattices) ? rec->lattices + (t - 1) * b9 : nullptr;
-        a.rec_lpl = (rec && rec->log_prob_l) ? rec->log_prob_l + (size_t)t * B : nullptr;
-        a.rec_lpt = (rec && rec->log_prob_t) ? rec->log_prob_t + (size_t)t * B : nullptr;
-        a.rec_lpx = (rec && rec->log_prob_x) ? rec->log_prob_x + (size_t)t * B : nullptr;
-        a.seed = seed;
-        a.node_offset = b->node_offset;
-        a.graph_offset = b->graph_offset;
-        a.t = t;
-        a.keep_lattice = b->keep_lattice;
-        a.keep_coords = b->keep_coords;
-        if (b->cond_on && b->lik_on && rec) {   // the record of a conditioned chain's likelihood (condition.hip)
-            MI_TRY(predictor_masked_launch(b, a, s));
-        } else {
-            hipLaunchKernelGGL(predictor_kernel, dim3(B), dim3(256), 0, s, a);
-            MI_KERNEL_CHECK();
-        }
-        // ... and at the level the step arrived at: the known elements of the state and of its record are overwritten (the corrector is left alone)
-        if (b->cond_on) MI_TRY(condition_impose(b, t - 1, seed, atom_types, frac, lattices, a.rec_types, a.rec_frac, a.rec_lat, s));
+        return MI_OK;
     }
+    for (int t = t_start; t > t_stop; --t) MI_TRY(sampler_step(net, b, t, seed, time_freqs, noise, rec, atom_types, frac, lattices, s));
     return MI_OK;
 }
 

@@ -367,7 +367,7 @@ class DiffCSPModule(nn.Module):
 
     @torch.no_grad()
     def sample(self, batch, diff_ratio=1.0, step_lr=1e-5, seed=0, noise=None, init=None, record=False, t_start=None,
-               t_stop=0, node_offset=0, graph_offset=0, streams=None, rec_sink=None, condition=None, likelihood=None):
+               t_stop=0, node_offset=0, graph_offset=0, streams=None, rec_sink=None, condition=None, likelihood=None, resample=None):
         """DiffCSPModule.sample (diffusion.py:273-399).
 
         `rec_sink` (a list; with record=True): receives one (first crystal, first atom, buffers) per chain, in crystal order -- the
@@ -394,8 +394,17 @@ class DiffCSPModule(nn.Module):
         mask for this call, and a recording chain records the log-probabilities with the predictor terms of the known elements left
         out -- the conditioned chain's trajectory likelihood up to a constant of the weights.  The states are those of the same call
         without the keyword, bit for bit.  None (the default): the record of the unconditioned proposal, as above.
+
+        `resample` = (r, j) (with a condition): RePaint's resampling jumps.  At every jump-off level 1, 1 + j, 1 + 2 j, ... the
+        whole state is re-noised j levels forward and denoised again, r visits in all, every repetition under a seed of its own
+        (resampling.visit_seed); (1, j) is the plain conditioned chain, bit for bit.  The chain's handles carry (r, j) and the jump table
+        for this call, like the condition.  ValueError before any device work: no condition, record=True, `noise`, `likelihood`,
+        t_stop != 0, r < 1, j < 1, or no jump-off level (1 + j > t_start).
         """
         from .conditioning import check_likelihood
+        from .resampling import check_chain
+        rj = None if resample is None else check_chain("sample", resample, self.beta_scheduler.timesteps, t_start, t_stop, condition, record,
+                                                       noise, likelihood)
         lik = check_likelihood("sample", likelihood, condition)
         if condition is not None and [int(v) for v in condition.num_atoms.tolist()] != [int(v) for v in batch.num_atoms.tolist()]:
             raise ValueError("sample: the condition's atom counts are not the batch's")
@@ -403,7 +412,7 @@ class DiffCSPModule(nn.Module):
             self.check_graph()   # (the verdict of the previous call's chains: by now they have long finished)
         if isinstance(batch, CrystalBatch):
             return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink,
-                                    condition=condition, likelihood=lik)
+                                    condition=condition, likelihood=lik, resample=rj)
         if (self.keep_lattice or self.keep_coords) and init is None and condition is None:
             # CSP mode (diffusion.py:283-287): the known part of the structure replaces the drawn initial state and is never moved
             cb0 = self.crystal_batch(batch, node_offset, graph_offset)
@@ -426,7 +435,7 @@ class DiffCSPModule(nn.Module):
         streams = max(1, min(int(streams), len(na)))
         if streams == 1:
             return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink,
-                                    condition=condition, likelihood=lik)
+                                    condition=condition, likelihood=lik, resample=rj)
         key = ("split", streams, tuple(na))
         parts = getattr(batch, "_mi_split", {}).get(key)
         if parts is None:  # contiguous crystal groups, cached on the batch object like its CrystalBatch
@@ -474,7 +483,7 @@ class DiffCSPModule(nn.Module):
         # the chains), and cleared when all of them are: each group gets its crystals' slice
         conds = [] if condition is None else [(self.crystal_batch(parts[k], node_offset + n0[k], graph_offset + g0[k]), condition.slice(g0[k], g0[k + 1]))
                                               for k in range(streams)]
-        with self._conditioned(conds, likelihood=lik):
+        with self._conditioned(conds, likelihood=lik, resample=rj):
             out = workers.run(run, streams)
         if rec_sink is not None:
             for k, sk in enumerate(sinks):
@@ -518,22 +527,27 @@ class DiffCSPModule(nn.Module):
             _lib.check(lib.mi_knn_graph_status(cb._h, C.c_void_p(stream.cuda_stream)), "mi_knn_graph_status")
 
     @contextlib.contextmanager
-    def _conditioned(self, pairs, condition=True, likelihood=False):
+    def _conditioned(self, pairs, condition=True, likelihood=False, resample=None):
         """Attach each (batch handle, Condition) of `pairs` for the duration of the block and clear the handles afterwards, whatever happens
         inside: the cached handles of `crystal_batch` must not carry a condition into a later call.  The device is drained once first --
         an earlier chain of a cached handle may still be reading the arrays the attach overwrites.  `condition`: the condition itself
-        (values and level table); `likelihood`: its masks as the handle's likelihood mask; either or both."""
+        (values and level table); `likelihood`: its masks as the handle's likelihood mask; either or both.  `resample`: (r, j), attached
+        with this module's jump table alongside the condition."""
         if not pairs:
             yield
             return
+        from . import resampling
         from .conditioning import Condition
         torch.cuda.synchronize(self.device)
         try:
+            jumps = None if resample is None else resampling.jump_table(self, resample[1])
             for cb, c in pairs:
                 if condition:
                     c.attach(self, cb)
                 if likelihood:
                     c.attach_likelihood(self, cb)
+                if resample is not None:
+                    resampling.attach(self, cb, resample[0], resample[1], table=jumps)
             yield
         finally:
             for cb, _ in pairs:
@@ -541,9 +555,11 @@ class DiffCSPModule(nn.Module):
                     Condition.clear(cb)
                 if likelihood:
                     Condition.clear_likelihood(cb)
+                if resample is not None:
+                    resampling.clear(cb)
 
     def _sample_one(self, batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, inplace=None, drawn=False,
-                    rec_sink=None, condition=None, likelihood=False):
+                    rec_sink=None, condition=None, likelihood=False, resample=None):
         """One chain over one CrystalBatch on the current stream.
 
         Returns (traj[t_stop], traj) like the reference.  `traj` holds every step only when
@@ -586,7 +602,7 @@ class DiffCSPModule(nn.Module):
                          frac_coords_mid=z(T + 1, N, 3), log_prob_l=z(T + 1, B), log_prob_t=z(T + 1, B), log_prob_x=z(T + 1, B))
             rec = _lib.SamplerRecord(*(rec_t[k].data_ptr() for k in ("atom_types", "frac_coords", "lattices", "frac_coords_mid",
                                                                      "log_prob_l", "log_prob_t", "log_prob_x")))
-        with self._conditioned([] if condition is None else [(cb, condition)], likelihood=likelihood):
+        with self._conditioned([] if condition is None else [(cb, condition)], likelihood=likelihood, resample=resample):
             _lib.check(lib.mi_sampler_run(self.decoder._h, cb._h, coef.numpy().ctypes.data_as(C.POINTER(C.c_float)), T, t_start, t_stop,
                                           _ptr(self.time_embedding.freqs), seed, C.byref(nz) if nz is not None else None,
                                           C.byref(rec) if rec is not None else None, _ptr(a), _ptr(x), _ptr(l), _stream()),

@@ -84,7 +84,8 @@ class MatInvent(ReinL):
         """mat_invent.py:74-123: sample, geometric validity pre-filter (device-side quantities), save the valid set as
         extxyz, optional filter callable, max_num.  MLIP relaxation / SUN metrics are out of scope.
         sample_cfg.target_compositions_dict (a list of {symbol: count}) reaches the sampler with the other keys: the loop then samples
-        crystals of those formulas only (replacement conditioning) and fine-tunes on them -- a fixed-formula RL loop."""
+        crystals of those formulas only (replacement conditioning) and fine-tunes on them -- a fixed-formula RL loop.
+        sample_cfg.resample_times / sample_cfg.jump_length reach it the same way: the conditioned chains make RePaint's jumps."""
         rank, world = rank_world()
         kw = {k: v for k, v in self.sample_cfg.items() if k not in ("filter", "mlip_opt", "geometric_filter")}
         if self.sample_steps is not None:   # (the sampler builds the agent's strided view; ft_step stays on the agent and its trained grid)
@@ -211,7 +212,8 @@ class MatInventPG(MatInvent):
     chain is not its likelihood.  sample_cfg.condition_likelihood: free lifts the refusal: the condition is built as
     DiffCSPSampler.generate builds it (target_compositions_dict: batch_size crystals cycling through the list, every atom type fixed; or an
     explicit conditioning.Condition for batch_size crystals), the rollout records -- and pg_step re-evaluates -- the likelihood over the
-    free elements, and the condition follows the kept crystals through the filters and max_num."""
+    free elements, and the condition follows the kept crystals through the filters and max_num.
+    sample_cfg.resample_times / jump_length (resampling jumps) are refused: a rollout holds one visit per level."""
 
     def __init__(self, rl_epoch, model_suite, reward, sample_cfg, finetune_cfg, save_dir, save_freq=50, device=None, logger=None,
                  replay=False, replay_args=None, topk_ratio=1.0, **kwargs):
@@ -233,6 +235,8 @@ class MatInventPG(MatInvent):
             if merged.get(k) is not None and lik is None:
                 raise ValueError(f"MatInventPG: sample_cfg.{k} is not supported -- a conditioned chain's recorded log-probabilities are those "
                                  "of the unconditioned proposal, not a trajectory likelihood (use pipeline=mat_invent)")
+        from .resampling import refuse
+        refuse("MatInventPG", **{f"sample_cfg.{k}": merged.get(k) for k in ("resample_times", "jump_length")})
         if kwargs.get("div_filter"):
             raise ValueError("MatInventPG: div_filter=True is not built -- the diversity filter penalises the rewards that rank a top-k, and the "
                              "policy gradient has no top-k (use pipeline=mat_invent)")

@@ -42,7 +42,7 @@ class DiffCSPSampler:
     seed: int = 0
 
     def generate(self, model, batch_size=None, num_batches=None, sample_steps=None, condition=None, target_compositions_dict=None,
-                 **kwargs) -> Tuple[List[CrystalData], list]:
+                 resample_times=None, jump_length=None, **kwargs) -> Tuple[List[CrystalData], list]:
         """sample.py:148-201.  Extra kwargs (`max_num`, `filter`, ...) are tolerated like the reference.
         `sample_steps` = S: the chains run on S of the model's T trained steps (model.respaced(S)); None: all of them.
         As in the reference, every batch is sampled but only the LAST batch's outputs are unpacked
@@ -52,7 +52,9 @@ class DiffCSPSampler:
         Conditioned generation (DiffCSPModule.sample's `condition`): `target_compositions_dict` -- this keyword, else the
         field -- is a list of {symbol: count} mappings; the batch_size x num_batches crystals cycle through it, every atom type is
         fixed (Condition.composition) and the atom counts come from the compositions instead of the mp_20 draw.  `condition`: an explicit
-        conditioning.Condition for all batch_size x num_batches crystals, or for batch_size of them (then used for every batch)."""
+        conditioning.Condition for all batch_size x num_batches crystals, or for batch_size of them (then used for every batch).
+        `resample_times` = r with `jump_length` = j (DiffCSPModule.sample's `resample`): the conditioned chains make RePaint's
+        resampling jumps; both or neither, and only with a condition (ValueError).  Levels are step indices under `sample_steps`."""
         batch_size = batch_size or self.batch_size
         num_batches = num_batches or self.num_batches
         assert batch_size is not None and num_batches is not None
@@ -67,6 +69,11 @@ class DiffCSPSampler:
         elif condition is not None and len(condition) not in (batch_size, batch_size * num_batches):
             raise ValueError(f"DiffCSPSampler.generate: the condition covers {len(condition)} crystals, not batch_size = {batch_size} or "
                              f"batch_size x num_batches = {batch_size * num_batches}")
+        if (resample_times is None) != (jump_length is None):
+            raise ValueError("DiffCSPSampler.generate: give resample_times and jump_length together, or neither")
+        resample = None if resample_times is None else (resample_times, jump_length)
+        if resample is not None and condition is None:
+            raise ValueError("DiffCSPSampler.generate: resample_times / jump_length need a condition (target_compositions_dict or condition)")
         rank, world = int(kwargs.get("rank", 0)), int(kwargs.get("world_size", 1))
         model = _strided(model, sample_steps)
         model.eval()
@@ -94,7 +101,8 @@ class DiffCSPSampler:
             if condition is not None:
                 c0 = bi * batch_size % len(condition)
                 cond = condition.slice(c0 + lo, c0 + hi)
-            outputs, _ = model.sample(counts, step_lr=step_lr, seed=self.seed, node_offset=node_off, graph_offset=lo, condition=cond)
+            outputs, _ = model.sample(counts, step_lr=step_lr, seed=self.seed, node_offset=node_off, graph_offset=lo, condition=cond,
+                                      **({} if resample is None else {"resample": resample}))
         data_list = _unpack(model, counts, outputs, node_off, lo, where="DiffCSPSampler.generate")
         struc_list = [data2struc(d) for d in data_list]
         if world > 1 or collectives_on():
@@ -164,15 +172,17 @@ def _refuse_condition(where, condition):
                          "unconditioned proposal, not a trajectory likelihood (DESIGN 31)")
 
 
-def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_steps=None, condition=None):
+def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_steps=None, condition=None, resample=None):
     """sample.py:249-309: sample with the trajectory recorded and return (sample_list, sample_traj), restricted to the crystals that
     pass invalid_filter.  sample_traj[k] is the step t = T - k (t = T .. 2) with the reference's keys (atom_types, lattices, frac_coords,
     frac_coords_mid, num_atoms, timesteps, log_prob_{t,x,l}; host tensors) plus next_frac_coords / next_lattices / next_atom_types --
     the state at t - 1 -- so that any element can go straight to DiffCSPModule.forward_logprb.  (The reference's own sample_mdp unpacks
     invalid_filter into the wrong values and never builds the next_* keys that forward_logprb reads.)
     A strided view (DiffCSPModule.respaced), or sample_steps = S which builds it: T is the view's S and `timesteps` are step indices --
-    what the VIEW's forward_logprb takes.  A `condition` is refused (ValueError)."""
+    what the VIEW's forward_logprb takes.  A `condition` is refused (ValueError), and so is `resample`."""
     from .filters import invalid_filter
+    from .resampling import refuse
+    refuse("sample_mdp", resample=resample)
     _refuse_condition("sample_mdp", condition)
     model = _strided(model, sample_steps)
     counts, step_lr = _prelude(sample_size, model, step_lr)
@@ -244,7 +254,8 @@ class Rollout:
                        None if self.condition is None else self.condition.select(idx))
 
 
-def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=True, sample_steps=None, condition=None, likelihood=None):
+def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=True, sample_steps=None, condition=None, likelihood=None,
+                   resample=None):
     """Sample like sample_mdp (same atom-count draw, seed handling and invalid_filter; geometric_filter=False keeps every crystal) and
     keep the kept crystals' whole trajectories on the device as a Rollout -- compacted once per chain straight from the sampler's stacked
     record buffers, without the per-step dict or a host copy.  Returns (sample_list, rollout).  The policy gradient (policy.pg_step)
@@ -254,9 +265,12 @@ def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=T
     (ValueError), like CSP mode.
     condition=c (for `sample_size` crystals), likelihood="free" (DESIGN 36): the chains are conditioned on c, whose atom counts replace the
     draw; rollout.lp_old is the masked record (the predictor terms of the known elements left out) and rollout.condition the kept
-    crystals' part of c, which pg_step re-evaluates under.  CSP mode stays refused."""
+    crystals' part of c, which pg_step re-evaluates under.  CSP mode stays refused.  `resample` is refused (ValueError): a resampled chain
+    visits levels more than once and a rollout holds one visit."""
     from .conditioning import check_likelihood
     from .filters import invalid_filter
+    from .resampling import refuse
+    refuse("sample_rollout", resample=resample)
     if not check_likelihood("sample_rollout", likelihood, condition):
         _refuse_condition("sample_rollout", condition)
     elif len(condition) != int(sample_size):
