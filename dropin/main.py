@@ -1,4 +1,7 @@
-"""Entry point with the semantics of the reference's main.py:8-21 (hydra compose + instantiate + run_rl)."""
+"""Entry point with the semantics of the reference's main.py:8-21 (hydra compose + instantiate + run_rl).
+
+pipeline = mat_invent | mat_invent_pg | mat_invent_dpo | baseline | pretrain (configs/pipeline/*.yaml); `pretrain` trains a prior on
+pipeline.train_path (an extxyz file) and its run_rl is the training run."""
 import logging
 import os
 import sys

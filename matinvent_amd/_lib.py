@@ -248,9 +248,15 @@ RESAMPLE_SIGNATURES = {
     "mi_resample_visit_seed": (_U64, [_U64, _U32]),
 }
 
+# the supervised-training extension, include/matinvent_hip_pretrain.h (one denoising-training micro-step of one network)
+PRETRAIN_SIGNATURES = {
+    "mi_pretrain_micro_step": (_I, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(_I), _P, _P, _I, _U64, _U32, _P, _P, _P, C.c_float, C.c_float, C.c_float,
+                                    _I, _I, _I, _P, _P, _P, _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
-                        DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES)
+                        DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, PRETRAIN_SIGNATURES)
 
 _lib = None
 

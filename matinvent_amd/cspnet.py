@@ -112,10 +112,14 @@ class CrystalBatch:
     def num_pairs(self) -> int:
         return int(self._lib.mi_batch_num_pairs(self._h))
 
-    def __del__(self):
+    def release(self):
+        """Destroy the handle now and free its device memory (the runtime waits for the work enqueued on it); the object is dead afterwards."""
         h, self._h = getattr(self, "_h", None), None
         if h is not None and getattr(self, "_lib", None) is not None:
             self._lib.mi_batch_destroy(h)
+
+    def __del__(self):
+        self.release()
 
 
 class CSPNet(nn.Module):

@@ -238,6 +238,10 @@ struct mi_batch {
     float* dpo_delta = nullptr;                      // [B]: d_b
     float *dpo_m = nullptr, *dpo_g = nullptr;        // [n_pairs]: m_p, g_p
     std::vector<int> dpo_w_h, dpo_l_h;
+    // supervised training micro-step (pretrain.hip, mi_pretrain_micro_step; allocated on first use): the crystals' schedule rows, their
+    // sums of squares, and -- forward-only form, which prepares no tape -- the noised inputs and targets
+    float *pt_sched = nullptr, *pt_parts = nullptr;   // [B][4], [B][3]
+    float* pt_noised = nullptr;                       // in_lat | in_frac | in_types | tar_x | rnd_l | rnd_t
     std::vector<void*> allocs;
 };
 

@@ -184,19 +184,28 @@ class DiffCSPModule(nn.Module):
         return cb
 
     # ---- fine-tune surface (pipeline/mat_invent.py:152-161) ------------------------------------
-    def add_noise(self, batch, time=None, noise=None, seed=None):
+    def add_noise(self, batch, time=None, noise=None, seed=None, times=None):
         """DiffCSPModule.add_noise (diffusion.py:81-119) for an explicit timestep index
         (`time` in 0..T-1 -> diffusion time T - time, :86-87).  Returns the reference's triple
         (noised_input, noises, batch.batch).  Fresh Gaussian noise per call from the Philox
-        stream (seed, running call counter) unless `noise` = (rand_l, rand_x, rand_t)."""
+        stream (seed, running call counter) unless `noise` = (rand_l, rand_x, rand_t).
+        `times` (with time=None): the per-crystal diffusion times, [B] ints in 1..T, in place of the numpy draw."""
         lib = _lib.load()
         dev = self.device
         T = self.beta_scheduler.timesteps
         cb = self._batch_for(batch.num_atoms)
         B, N = cb.num_graphs, cb.num_nodes
         sched = None
+        if time is not None and times is not None:
+            raise ValueError("add_noise: give `time` (one index for every crystal) or `times` (one time per crystal), not both")
         if time is None:   # :83-84: one uniformly drawn time per crystal (numpy's global generator, like the reference)
-            times = self.beta_scheduler.uniform_sample_t(B, dev)
+            if times is None:
+                times = self.beta_scheduler.uniform_sample_t(B, dev)
+            else:
+                times = torch.as_tensor(times).long().reshape(-1)
+                if times.numel() != B or (B and (int(times.min()) < 1 or int(times.max()) > T)):
+                    raise ValueError(f"add_noise: `times` must hold {B} values in 1..{T}")
+                times = times.to(dev)
             ac = self.beta_scheduler.alphas_cumprod[times]
             sched = torch.stack([torch.sqrt(ac), torch.sqrt(1.0 - ac), self.sigma_scheduler.sigmas[times],
                                  self.sigma_scheduler.sigmas_norm[times]], dim=1).to(torch.float32).contiguous()
@@ -259,6 +268,21 @@ class DiffCSPModule(nn.Module):
         k1 = _scatter_mean(torch.pow(px - pxp, 2).mean(dim=1), node2graph, B)
         k2 = _scatter_mean(torch.pow(pt - ptp, 2).mean(dim=1), node2graph, B)
         return k0 + k1 + k2
+
+    def training_step(self, batch, times=None, noise=None):
+        """DiffCSPModule.training_step (diffusion.py:457-486) on the module surface: add_noise with one time per crystal (`times`: [B]
+        ints in 1..T in place of the numpy draw), the network, three F.mse_loss over all elements of the batch, the cost-weighted sum.
+        Returns (loss, dict(loss, loss_lattice, loss_coord, loss_type)); differentiable through the decoder's autograd function.  The
+        unfused yardstick of pretrain.train_step, as ft_step(fused=False) is of the fused fine-tune step."""
+        if self.base is not None:
+            raise ValueError("training_step: a respaced view is for sampling; train its .base, the module of the trained grid")
+        input_all = self.add_noise(batch, None, noise=noise, times=times)
+        _, (rand_l, tar_x, rand_t), _ = input_all
+        pred_l, pred_x, pred_t = self.predict(input_all)
+        mse = nn.functional.mse_loss
+        loss_lattice, loss_coord, loss_type = mse(pred_l, rand_l), mse(pred_x, tar_x), mse(pred_t, rand_t)
+        loss = self.cost_lattice * loss_lattice + self.cost_coord * loss_coord + self.cost_type * loss_type
+        return loss, dict(loss=loss, loss_lattice=loss_lattice, loss_coord=loss_coord, loss_type=loss_type)
 
     def forward(self, noised_input):
         time_emb, atom_types, frac, lattices, num_atoms, node2graph = noised_input

@@ -388,3 +388,70 @@ class MatInventDPO(MatInvent):
         if self.logger is not None:
             self.logger.log(log, step=self.step)
         logging.info(f"*****   LOOP {self.step} FINISH   *****  {(time.time() - t0) / 60:.2f} min")
+
+
+class Pretrain:
+    """Supervised denoising training of a DiffCSP prior on a crystal dataset (pretrain.fit): the pipeline that produces the
+    model the RL pipelines start from.  train_path / val_path: extxyz files (structure.read_extxyz); train_cfg: pretrain.fit's config
+    (lr, epochs, batch_size, accum_steps, max_grad_norm, skip_nonfinite_steps, lr_plateau), merged over the suite's finetune_cfg (the
+    pipeline wins).  DiffCSPSuite.save_model writes <save_dir>/models/epoch_NNNN every save_freq epochs and <save_dir>/models/final at the
+    end: directories that load_model(model_path=...) of this build loads.  `run_rl` is the entry the drop-in's main calls; `reward`,
+    `logger` rows and sampling play no part (the logger, when given, receives every epoch's dict).  The MatterGen suite is refused."""
+
+    def __init__(self, model_suite, train_path, save_dir, train_cfg=None, val_path=None, save_freq=10, seed=0, device=None, logger=None,
+                 reward=None, **kwargs):
+        from .suite import MatterGenSuite
+        if isinstance(model_suite, MatterGenSuite):
+            raise ValueError("Pretrain needs the DiffCSP suite: the MatterGen-shaped module has no supervised training here")
+        if not train_path:
+            raise ValueError("Pretrain: train_path (an extxyz file) is required")
+        self.model_suite, self.logger = model_suite, logger
+        self.train_path, self.val_path = train_path, val_path
+        self.save_dir, self.save_freq, self.seed = save_dir, max(1, int(save_freq)), int(seed)
+        self.device = get_device(device)
+        self.cfg = C.create(kwargs)
+        self.train_cfg = C.merge(model_suite.finetune_cfg, train_cfg)
+        self.models_dir = os.path.join(save_dir, "models")
+        os.makedirs(self.models_dir, exist_ok=True)
+        self.model, self.history = None, []
+
+    @staticmethod
+    def read_dataset(path):
+        """An extxyz file -> the CrystalData records pretrain.fit trains on (fractional coordinates wrapped into [0, 1))."""
+        from .data import CrystalData
+        from .structure import read_extxyz
+        out = []
+        for s in read_extxyz(path):
+            frac = torch.as_tensor(np.asarray(s.frac_coords), dtype=torch.float64) % 1.0
+            out.append(CrystalData(frac.float(), torch.tensor(s.species, dtype=torch.long), torch.tensor([s.lengths], dtype=torch.float32),
+                                   torch.tensor([s.angles], dtype=torch.float32)))
+        return out
+
+    def load_model(self):
+        self.model = self.model_suite.load_model()
+        for p in self.model.parameters():
+            p.requires_grad = True
+        self.model.to(self.device)
+        return self.model
+
+    def run_rl(self):
+        from .pretrain import fit
+        rank, _ = rank_world()
+        train = self.read_dataset(self.train_path)
+        val = self.read_dataset(self.val_path) if self.val_path else None
+        if self.model is None:
+            self.load_model()
+        logging.info(f"training on {len(train)} crystals" + (f", validating on {len(val)}" if val is not None else ""))
+
+        def on_epoch_end(epoch, d):
+            if rank != 0:
+                return
+            if self.logger is not None:
+                self.logger.log(dict(d), step=epoch)
+            if (epoch + 1) % self.save_freq == 0:
+                self.model_suite.save_model(self.model, os.path.join(self.models_dir, f"epoch_{epoch:0>4d}"))
+
+        self.history = fit(self.model, train, self.train_cfg, val_list=val, seed=self.seed, on_epoch_end=on_epoch_end)
+        if rank == 0:
+            self.model_suite.save_model(self.model, os.path.join(self.models_dir, "final"))
+        return self.history
