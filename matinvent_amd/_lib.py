@@ -254,9 +254,21 @@ PRETRAIN_SIGNATURES = {
                                     _I, _I, _I, _P, _P, _P, _P]),
 }
 
+# the handle-pool extension, include/matinvent_hip_pool.h (a device-memory pool for batch handles and the pooled handle)
+POOL_SIGNATURES = {
+    "mi_pool_create": (_I, [_P, _L, C.POINTER(_P)]),
+    "mi_pool_destroy": (_I, [_P]),
+    "mi_pool_trim": (_I, [_P]),
+    "mi_pool_stats": (_I, [_P, C.POINTER(_L)]),
+    "mi_pool_block_bytes": (_L, [_L]),
+    "mi_pool_set_poison": (_I, [_P, _I]),
+    "mi_batch_create_pooled": (_I, [_P, _P, C.POINTER(_I), _I, _L, _L, C.POINTER(_P)]),
+    "mi_batch_index_table": (_L, [_P, _I, C.POINTER(_I), _L]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
-                        DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, PRETRAIN_SIGNATURES)
+                        DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, PRETRAIN_SIGNATURES)
 
 _lib = None
 

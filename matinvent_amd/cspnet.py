@@ -46,7 +46,7 @@ class CrystalBatch:
     bookkeeping (`num_atoms`, `batch`) and the per-call edge enumeration of gen_edges."""
 
     def __init__(self, net: "CSPNet", num_atoms, node_offset: int = 0, graph_offset: int = 0, edge_style: str = "fc",
-                 max_neighbors: int = 20, edge_cap_per_node: int = 48):
+                 max_neighbors: int = 20, edge_cap_per_node: int = 48, pool=None):
         lib = _lib.load()
         na = [int(x) for x in (num_atoms.tolist() if torch.is_tensor(num_atoms) else num_atoms)]
         self.num_atoms_list = na
@@ -55,6 +55,16 @@ class CrystalBatch:
         arr = (C.c_int * max(len(na), 1))(*na)
         h = C.c_void_p()
         self.edge_style = edge_style
+        self._pool = pool   # (a pool.HandlePool, kept alive as long as this handle: its blocks are the pool's)
+        if pool is not None:
+            # a pooled handle (mi_batch_create_pooled): its set-up is enqueued on the pool's stream and nothing here waits --
+            # the `num_atoms` / `batch` tensors, whose construction synchronises, are built on first access (__getattr__ below)
+            if edge_style == "knn":
+                raise _lib.MIError(_lib.MI_EINVAL, "CrystalBatch: a pooled batch handle has the fully connected edge style only (edge_style='knn' takes no pool)")
+            _lib.check(lib.mi_batch_create_pooled(net._h, pool._handle(), arr, len(na), node_offset, graph_offset, C.byref(h)), "mi_batch_create_pooled")
+            self._h, self._dev, self._lib = h, net.theta.device, lib
+            self.num_edges = int(lib.mi_batch_num_edges(h))
+            return
         if edge_style == "knn":
             _lib.check(lib.mi_batch_create_knn(net._h, arr, len(na), node_offset, graph_offset, max_neighbors, edge_cap_per_node, C.byref(h)),
                        "mi_batch_create_knn")
@@ -67,6 +77,15 @@ class CrystalBatch:
         self.num_atoms = torch.tensor(na, dtype=torch.long, device=dev)
         self.batch = torch.repeat_interleave(torch.arange(len(na), device=dev), self.num_atoms)
         self.num_edges = int(lib.mi_batch_num_edges(h))
+
+    def __getattr__(self, name):
+        # (only reached for an attribute that is not set: the two index tensors of a pooled handle, built on first use)
+        if name in ("num_atoms", "batch") and self.__dict__.get("_pool") is not None:
+            na = torch.tensor(self.num_atoms_list, dtype=torch.long, device=self._dev)
+            self.num_atoms = na
+            self.batch = torch.repeat_interleave(torch.arange(len(self.num_atoms_list), device=self._dev), na)
+            return self.__dict__[name]
+        raise AttributeError(name)
 
     # ---- knn edge style (gen_edges knn branch, cspnet.py:243-257) ----
     def build_graph(self, frac_coords, lattices) -> int:
@@ -113,7 +132,8 @@ class CrystalBatch:
         return int(self._lib.mi_batch_num_pairs(self._h))
 
     def release(self):
-        """Destroy the handle now and free its device memory (the runtime waits for the work enqueued on it); the object is dead afterwards."""
+        """Destroy the handle now and free its device memory (the runtime waits for the work enqueued on it); the object is dead afterwards.
+        A pooled handle hands its blocks back to its pool instead: nothing is freed and nothing waits."""
         h, self._h = getattr(self, "_h", None), None
         if h is not None and getattr(self, "_lib", None) is not None:
             self._lib.mi_batch_destroy(h)
@@ -227,9 +247,9 @@ class CSPNet(nn.Module):
         self.edge_mode = mode
 
     # ---- forward ------------------------------------------------------------------------------
-    def make_batch(self, num_atoms, node_offset=0, graph_offset=0) -> CrystalBatch:
+    def make_batch(self, num_atoms, node_offset=0, graph_offset=0, pool=None) -> CrystalBatch:
         return CrystalBatch(self, num_atoms, node_offset, graph_offset, edge_style=self.edge_style, max_neighbors=self.max_neighbors,
-                            edge_cap_per_node=self.edge_cap_per_node)
+                            edge_cap_per_node=self.edge_cap_per_node, pool=pool)
 
     def forward(self, t, atom_types, frac_coords, lattices, num_atoms, node2graph=None, batch: CrystalBatch = None):
         """Same positional signature as the reference CSPNet.forward (cspnet.py:260); `batch`

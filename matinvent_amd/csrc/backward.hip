@@ -791,13 +791,13 @@ static int alloc_tape(mi_net* net, mi_batch* b) {
     if (MI_PLANES_FP16 && g_bwd_wgrad_planes && H % 256 == 0 && b->M1pl && E >= 8192) {   // every layer's M1 plane set (see Tape::M1pl_l); row padding zero
         t.m1pl_stride = planes_elems(E, H);
         T_(M1pl_l, L * t.m1pl_stride);
-        if (rc == MI_OK && hipMemset(t.M1pl_l, 0, L * t.m1pl_stride * sizeof(unsigned short)) != hipSuccess) rc = MI_EHIP;
+        if (rc == MI_OK && batch_memset(b, t.M1pl_l, 0, L * t.m1pl_stride * sizeof(unsigned short)) != hipSuccess) rc = MI_EHIP;   // (pooled handle: on the pool's stream)
     }
     if (t.M1pl_l && b->Np >= 4096 && H % 256 == 0) {   // the pair differences / sums of dZ1 as plane sets (see Tape::DmPl)
         const size_t ne = planes_elems(b->Np, H);
         T_(DmPl, ne);
         T_(DpPl, ne);
-        if (rc == MI_OK && (hipMemset(t.DmPl, 0, ne * sizeof(unsigned short)) != hipSuccess || hipMemset(t.DpPl, 0, ne * sizeof(unsigned short)) != hipSuccess)) rc = MI_EHIP;
+        if (rc == MI_OK && (batch_memset(b, t.DmPl, 0, ne * sizeof(unsigned short)) != hipSuccess || batch_memset(b, t.DpPl, 0, ne * sizeof(unsigned short)) != hipSuccess)) rc = MI_EHIP;
     }
     T_(dM1, E * H);
     T_(FF, E * 6 * F);
@@ -835,8 +835,7 @@ int net_wgrad_window(mi_net* net, mi_batch* b, int slots) {
         for (float** q : {&t.w_dY, &t.w_Xa, &t.w_dXa, &t.w_cat, &t.w_dPQ, &t.w_dlo, &t.w_gf, &t.w_dtype, &t.w_dcoord, &t.w_hf, &t.w_dh, &t.w_x1, &t.w_dtproj, &t.w_temb,
                           &t.w_eXa, &t.w_types})
             if (*q) {
-                b->allocs.erase(std::remove(b->allocs.begin(), b->allocs.end(), (void*)*q), b->allocs.end());
-                (void)hipFree(*q);
+                dev_release(b, *q);   // (hipFree, or back to the handle's pool)
                 *q = nullptr;
             }
         t.wcap = 0;
@@ -1445,6 +1444,7 @@ extern "C" {
 
 int mi_cspnet_forward_train(mi_net* net, mi_batch* b, const float* t_emb, const float* atom_types, const float* frac,
                             const float* lattices, float* lattice_out, float* coord_out, float* type_out, void* stream) {
+    MI_POOL_STREAM(b, stream, "mi_cspnet_forward_train");
     MI_CHECK(net && b, MI_EINVAL, "null handle");
     MI_CHECK(b->H == net->H && b->L == net->L, MI_EINVAL, "batch was created for a different network");
     MI_TRY(net_tape_prepare(net, b));
@@ -1453,6 +1453,7 @@ int mi_cspnet_forward_train(mi_net* net, mi_batch* b, const float* t_emb, const 
 
 int mi_cspnet_backward(mi_net* net, mi_batch* b, const float* d_lattice_out, const float* d_coord_out, const float* d_type_out,
                        float* grad_theta, void* stream) {
+    MI_POOL_STREAM(b, stream, "mi_cspnet_backward");
     MI_CHECK(net && b && d_lattice_out && d_coord_out && d_type_out && grad_theta, MI_EINVAL, "null argument");
     MI_CHECK(net->W2T != nullptr, MI_ESTATE, "mi_net_set_params must run before backward");
     return net_backward(net, b, d_lattice_out, d_coord_out, d_type_out, grad_theta, (hipStream_t)stream);
@@ -1465,6 +1466,7 @@ int mi_batch_set_wgrad_window(mi_net* net, mi_batch* b, int micro_steps) {
 }
 
 int mi_cspnet_wgrad_flush(mi_net* net, mi_batch* b, float* grad_theta, void* stream) {
+    MI_POOL_STREAM(b, stream, "mi_cspnet_wgrad_flush");
     MI_CHECK(net && b && grad_theta, MI_EINVAL, "null argument");
     return net_wgrad_flush(net, b, grad_theta, (hipStream_t)stream);
 }
@@ -1485,6 +1487,7 @@ int mi_adam_step(float* theta, const float* grad, float* exp_avg, float* exp_avg
 int mi_add_noise(mi_batch* b, const float* lengths, const float* angles, const float* frac0, const int* atom_types, float c0, float c1,
                  float sigma, float sigma_norm, uint64_t seed, uint32_t step, const float* rand_l, const float* rand_x, const float* rand_t,
                  float* in_lattice, float* in_frac, float* in_types, float* tar_x, float* out_rand_l, float* out_rand_t, void* stream) {
+    MI_NO_POOLED(b, "mi_add_noise");
     MI_CHECK(b && lengths && angles && frac0 && atom_types && in_lattice && in_frac && in_types && tar_x && out_rand_l && out_rand_t,
              MI_EINVAL, "null argument");
     if (b->B == 0) return MI_OK;
@@ -1636,6 +1639,8 @@ int mi_ft_micro_step(mi_net* agent, mi_batch* ab, mi_net* prior, mi_batch* pb, c
                      float sigma_t, float sigma_norm, uint64_t seed, uint32_t noise_step, const float* rand_l, const float* rand_x,
                      const float* rand_t, float cost_lattice, float cost_coord, float cost_type, float kl_sigma, int b_global, int accum_steps,
                      float* grad_theta, float* stats, float* out_sample_loss, float* out_kl, void* stream, void* aux_stream) {
+    MI_NO_POOLED(ab, "mi_ft_micro_step");
+    MI_NO_POOLED(pb, "mi_ft_micro_step");
     return ft_micro_impl(agent, ab, prior, pb, lengths, angles, frac0, atom_types, reward, time_freqs, t, c0, c1, sigma_t, sigma_norm, 0, nullptr,
                          nullptr, nullptr, nullptr, nullptr, seed, noise_step, rand_l, rand_x, rand_t, cost_lattice, cost_coord, cost_type,
                          kl_sigma, b_global, accum_steps, grad_theta, stats, out_sample_loss, out_kl, stream, aux_stream);
@@ -1647,6 +1652,8 @@ int mi_ft_micro_steps_stacked(mi_net* agent, mi_batch* ab, mi_net* prior, mi_bat
                               const float* sigma_norm_host, uint64_t seed, uint32_t noise_step, const float* rand_l, const float* rand_x,
                               const float* rand_t, float cost_lattice, float cost_coord, float cost_type, float kl_sigma, int b_global,
                               int accum_steps, float* grad_theta, float* stats, void* stream, void* aux_stream) {
+    MI_NO_POOLED(ab, "mi_ft_micro_steps_stacked");
+    MI_NO_POOLED(pb, "mi_ft_micro_steps_stacked");
     MI_CHECK(copies >= 1, MI_EINVAL, "copies must be positive");
     return ft_micro_impl(agent, ab, prior, pb, lengths, angles, frac0, atom_types, reward, time_freqs, 0, 0.f, 0.f, 0.f, 0.f, copies, t_host,
                          c0_host, c1_host, sigma_t_host, sigma_norm_host, seed, noise_step, rand_l, rand_x, rand_t, cost_lattice, cost_coord,

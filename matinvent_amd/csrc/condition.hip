@@ -251,6 +251,7 @@ int upload(mi_batch* b, T** dev, const T* host, size_t n) {
 extern "C" {
 
 int mi_batch_set_condition(mi_batch* b, const mi_condition* cond, const float* level_table_host, int n) {
+    MI_NO_POOLED(b, "mi_batch_set_condition");
     MI_CHECK(b, MI_EINVAL, "null handle");
     if (!cond) {
         b->cond_on = b->cond_any = false;
@@ -309,6 +310,7 @@ int mi_batch_set_condition(mi_batch* b, const mi_condition* cond, const float* l
 }
 
 int mi_batch_set_likelihood_mask(mi_batch* b, const int* known_types, const int* known_coords, const int* known_lattice) {
+    MI_NO_POOLED(b, "mi_batch_set_likelihood_mask");
     MI_CHECK(b, MI_EINVAL, "null handle");
     if (!known_types && !known_coords && !known_lattice) {
         b->lik_on = false;
@@ -342,6 +344,7 @@ int mi_batch_has_likelihood_mask(const mi_batch* b) {
 }
 
 int mi_condition_apply(mi_batch* b, int level, uint64_t seed, float* atom_types, float* frac, float* lattices, void* stream) {
+    MI_NO_POOLED(b, "mi_condition_apply");
     MI_CHECK(b && atom_types && frac && lattices, MI_EINVAL, "null argument");
     return condition_impose(b, level, seed, atom_types, frac, lattices, nullptr, nullptr, nullptr, (hipStream_t)stream);
 }

@@ -4,12 +4,15 @@
 #include <stdarg.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <atomic>
 
 #define MI_GEMM_OWNER   // this unit defines the GEMM launchers of gemm.h / gemm_split.h (and therefore carries their kernels); the others see prototypes
 #include "edge_mlp.h"
 #include "gemm_split.h"
 #include "net.h"
+#include "pool_tables.h"
+#include "../../include/matinvent_hip_pool.h"
 
 namespace mi {
 
@@ -834,6 +837,13 @@ __global__ __launch_bounds__(256) void lattice_head_kernel(const float* __restri
 template <typename T>
 int dev_alloc(mi_batch* b, T** p, size_t n) {
     void* q = nullptr;
+    if (b->pool) {   // pooled handle: the same exact-size request, served by the pool (int / unsigned blocks arrive zero-filled)
+        const int kind = std::is_same<T, float>::value ? POOL_F32 : std::is_same<T, unsigned short>::value ? POOL_F16 : POOL_INT;
+        MI_TRY(pool_alloc(b->pool, std::max<size_t>(n, 1) * sizeof(T), kind, &q));
+        b->allocs.push_back(q);
+        *p = (T*)q;
+        return MI_OK;
+    }
     hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
     if (e != hipSuccess) {
         set_error("hipMalloc(%zu bytes) failed: %s", n * sizeof(T), hipGetErrorString(e));
@@ -842,6 +852,11 @@ int dev_alloc(mi_batch* b, T** p, size_t n) {
     b->allocs.push_back(q);
     *p = (T*)q;
     return MI_OK;
+}
+void dev_release(mi_batch* b, void* p) {
+    b->allocs.erase(std::remove(b->allocs.begin(), b->allocs.end(), p), b->allocs.end());
+    if (b->pool) pool_release(b->pool, p);
+    else (void)hipFree(p);
 }
 template int dev_alloc<float>(mi_batch*, float**, size_t);
 template int dev_alloc<int>(mi_batch*, int**, size_t);
@@ -1533,8 +1548,9 @@ int mi_net_set_params(mi_net* n, const float* theta, const float* freqs_host, vo
 }
 
 static int batch_create_impl(const mi_net* net, const int* num_atoms_host, int B, int64_t node_offset, int64_t graph_offset, bool knn,
-                             int max_neighbors, int cap_per_node, mi_batch** out) {
+                             int max_neighbors, int cap_per_node, mi_batch** out, mi_pool* pool = nullptr) {
     MI_CHECK(net && out && (num_atoms_host || B == 0) && B >= 0, MI_EINVAL, "bad argument");
+    MI_CHECK(!pool || !knn, MI_EINVAL, "a pooled batch handle has the fully connected edge style only");
     mi_batch* b = new mi_batch();
     b->B = B;
     b->H = net->H;
@@ -1571,11 +1587,27 @@ static int batch_create_impl(const mi_net* net, const int* num_atoms_host, int B
         return MI_EINVAL;
     }
     // fully connected edges, row-major incl. self loops (cspnet.py:239-241)
-    const size_t Efc = knn ? 0 : (size_t)E;
-    std::vector<int> n2g(N), src(Efc), dst(Efc), rowptr(N + 1, 0), egraph(Efc), pr_i, pr_j, pr_e1, pr_e2, pr_g, ediag(knn ? 0 : N), pr_off(B + 1, 0);
+    const size_t Efc = knn || pool ? 0 : (size_t)E;
+    std::vector<int> n2g(pool ? 0 : N), src(Efc), dst(Efc), rowptr(pool ? 0 : N + 1, 0), egraph(Efc), pr_i, pr_j, pr_e1, pr_e2, pr_g, ediag(knn || pool ? 0 : N), pr_off(B + 1, 0);
     size_t e = 0;
     int nslots = knn ? b->deg_cap / 32 + 2 : 1;
-    for (int g = 0; g < B; ++g) {
+    if (pool) {
+        // pooled handle: the host computes the three prefix sums, nslots and nmax_fc; pool.hip's kernels write the tables
+        // that the loops of the other branch build, value for value (csrc/pool_tables.h)
+        b->edge_off_h.assign(B + 1, 0);
+        b->pair_off_h.assign(B + 1, 0);
+        for (int g = 0; g < B; ++g) {
+            const int n = num_atoms_host[g];
+            b->edge_off_h[g + 1] = b->edge_off_h[g] + n * n;
+            b->pair_off_h[g + 1] = b->pair_off_h[g] + n * (n - 1) / 2;
+            b->nmax_fc = std::max(b->nmax_fc, n);
+            for (int i = 0; i < n; ++i) nslots = std::max(nslots, pt_node_slots(b->edge_off_h[g] + i * n, n));
+        }
+        b->Np = b->pair_off_h[B];
+        b->pool = pool;   // (from here on every dev_alloc is a block of the pool, and mi_batch_destroy gives them back)
+        pool_handle_count(pool, +1);
+    }
+    for (int g = 0; g < B && !pool; ++g) {
         int n = num_atoms_host[g], o = b->node_off_h[g];
         for (int i = 0; i < n; ++i) {
             n2g[o + i] = g;
@@ -1603,15 +1635,18 @@ static int batch_create_impl(const mi_net* net, const int* num_atoms_host, int B
             }
         }
     }
-    b->Np = (int64_t)pr_i.size();
-    pr_off[B] = (int)pr_i.size();
-    rowptr[N] = (int)e;
+    if (!pool) {
+        b->Np = (int64_t)pr_i.size();
+        pr_off[B] = (int)pr_i.size();
+        rowptr[N] = (int)e;
+    }
     b->nslots = nslots;
     const int H = net->H, L = net->L;
     const size_t NH = (size_t)N * H;
     int rc = MI_OK;
 #define A_(p, n)                                   \
     if (rc == MI_OK) rc = dev_alloc(b, &b->p, (n))
+    if (pool) A_(edge_off, B + 1);
     A_(num_atoms, B);
     A_(node_off, B + 1);
     A_(node2graph, N);
@@ -1667,6 +1702,33 @@ static int batch_create_impl(const mi_net* net, const int* num_atoms_host, int B
         mi_batch_destroy(b);
         return rc;
     }
+    if (pool) {
+        // everything on the pool's stream, nothing waits: the handle's side streams (hi_stream, the fork / join events of the fused
+        // micro-steps) are entered through an event recorded on the call's stream -- the pool's -- so this set-up is ordered before
+        // their work.  The three prefix arrays are read from vectors the handle owns.
+        hipStream_t ps = pool_stream(pool);
+        auto upa = [&](int* d, const std::vector<int>& h) { return hipMemcpyAsync(d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, ps); };
+        hipError_t he = hipMemsetAsync(b->M1pl, 0, planes_elems(E, H) * sizeof(unsigned short), ps);
+        if (he == hipSuccess) he = hipMemsetAsync(b->lnpl, 0, planes_elems(N, H) * sizeof(unsigned short), ps);
+        if (he == hipSuccess) he = hipMemsetAsync(b->aggpl, 0, planes_elems(N, H) * sizeof(unsigned short), ps);
+        if (he == hipSuccess) he = hipMemsetAsync(b->Xpl, 0, planes_elems(N, H) * sizeof(unsigned short), ps);
+        if (he == hipSuccess) he = hipMemsetAsync(b->absmax, 0, (4 * L + 2) * sizeof(unsigned), ps);
+        if (he == hipSuccess) he = upa(b->node_off, b->node_off_h);
+        if (he == hipSuccess) he = upa(b->edge_off, b->edge_off_h);
+        if (he == hipSuccess) he = upa(b->pair_off, b->pair_off_h);
+        int rcp = MI_OK;
+        if (he != hipSuccess) {
+            set_error("pooled handle set-up failed: %s", hipGetErrorString(he));
+            rcp = MI_EHIP;
+        }
+        if (rcp == MI_OK) rcp = pool_build_tables(b, ps);
+        if (rcp != MI_OK) {
+            mi_batch_destroy(b);
+            return rcp;
+        }
+        *out = b;
+        return MI_OK;
+    }
     // M1 planes: the GEMM epilogue only writes rows < E; the row padding of the last tile must be finite
     if (hipMemset(b->M1pl, 0, planes_elems(E, H) * sizeof(unsigned short)) != hipSuccess ||
         hipMemset(b->lnpl, 0, planes_elems(N, H) * sizeof(unsigned short)) != hipSuccess ||
@@ -1711,7 +1773,12 @@ void mi_batch_destroy(mi_batch* b) {
     if (b->hi_stream) (void)hipStreamDestroy(b->hi_stream);
     for (hipEvent_t e : b->hi_ev)
         if (e) (void)hipEventDestroy(e);
-    for (void* p : b->allocs) (void)hipFree(p);
+    if (b->pool) {   // a pooled handle frees nothing: its blocks go back to the pool, in stream order
+        for (void* p : b->allocs) pool_release(b->pool, p);
+        pool_handle_count(b->pool, -1);
+    } else {
+        for (void* p : b->allocs) (void)hipFree(p);
+    }
     delete b;
 }
 
@@ -1724,6 +1791,26 @@ int mi_batch_create_knn(const mi_net* net, const int* num_atoms_host, int B, int
     return batch_create_impl(net, num_atoms_host, B, node_offset, graph_offset, true, max_neighbors, edge_cap_per_node, out);
 }
 
+int mi_batch_create_pooled(const mi_net* net, mi_pool* pool, const int* num_atoms_host, int B, int64_t node_offset, int64_t graph_offset,
+                           mi_batch** out) {
+    MI_CHECK(pool, MI_EINVAL, "mi_batch_create_pooled: null pool");
+    return batch_create_impl(net, num_atoms_host, B, node_offset, graph_offset, false, 0, 0, out, pool);
+}
+
+int64_t mi_batch_index_table(const mi_batch* b, int which, int* host_out, int64_t cap) {
+    MI_CHECK(b, MI_EINVAL, "null handle");
+    const int64_t N = b->N, B = b->B, E = b->E, Np = b->Np;
+    const int* const tab[14] = {b->num_atoms, b->node2graph, b->rowptr, b->e_diag, b->src, b->dst, b->edge_graph, b->pair_i, b->pair_j, b->pair_e1,
+                                b->pair_e2, b->pair_graph, b->node_off, b->pair_off};
+    const int64_t len[14] = {B, N, N + 1, b->knn ? 0 : N, E, E, E, Np, Np, Np, Np, Np, B + 1, B + 1};
+    MI_CHECK(which >= 0 && which < 14, MI_EINVAL, "mi_batch_index_table: table %d is not one of 0 .. 13", which);
+    if (!host_out) return len[which];
+    MI_CHECK(cap >= len[which], MI_EINVAL, "mi_batch_index_table: room for %lld of %lld entries", (long long)cap, (long long)len[which]);
+    if (b->pool) MI_HIP(hipStreamSynchronize(pool_stream(b->pool)));   // (a pooled handle's tables are written on its pool's stream)
+    if (len[which] > 0) MI_HIP(hipMemcpy(host_out, tab[which], (size_t)len[which] * sizeof(int), hipMemcpyDeviceToHost));
+    return len[which];
+}
+
 int mi_batch_num_nodes(const mi_batch* b) { return b ? b->N : 0; }
 int64_t mi_batch_num_edges(const mi_batch* b) { return b ? b->E : 0; }
 const int* mi_batch_node2graph(const mi_batch* b) { return b ? b->node2graph : nullptr; }
@@ -1732,12 +1819,14 @@ int mi_cspnet_forward(mi_net* net, mi_batch* b, const float* t_emb, const float*
                       const float* lattices, float* lattice_out, float* coord_out, float* type_out, void* stream) {
     MI_CHECK(net && b, MI_EINVAL, "null handle");
     MI_CHECK(b->H == net->H && b->L == net->L, MI_EINVAL, "batch was created for a different network");
+    MI_POOL_STREAM(b, stream, "mi_cspnet_forward");
     return net_forward(net, b, t_emb, atom_types, frac, lattices, lattice_out, coord_out, type_out, (hipStream_t)stream);
 }
 
 int mi_cspnet_tap(mi_net* net, mi_batch* b, int layer, float* out, void* stream) {
     MI_CHECK(net && b && out, MI_EINVAL, "null argument");
     MI_CHECK(layer >= 0 && layer <= net->L + 1, MI_EINVAL, "layer %d out of range", layer);
+    MI_NO_POOLED(b, "mi_cspnet_tap");
     const size_t NH = (size_t)b->N * net->H;
     const float* src = layer <= net->L ? b->h + (size_t)layer * NH : b->hf;
     MI_HIP(hipMemcpyAsync(out, src, NH * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));

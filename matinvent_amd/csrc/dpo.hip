@@ -155,6 +155,7 @@ using namespace mi;
 extern "C" {
 
 int mi_batch_set_pairs(mi_batch* b, const int* winners_host, const int* losers_host, int n_pairs) {
+    MI_NO_POOLED(b, "mi_batch_set_pairs");
     MI_CHECK(b, MI_EINVAL, "null handle");
     MI_CHECK(n_pairs >= 0, MI_EINVAL, "n_pairs = %d: must be >= 0", n_pairs);
     if (n_pairs == 0) {
@@ -215,6 +216,8 @@ int mi_dpo_micro_step(mi_net* agent, mi_batch* ab, mi_net* prior, mi_batch* pb, 
                       float sigma_norm, uint64_t seed, uint32_t noise_step, const float* rand_l, const float* rand_x, const float* rand_t,
                       float cost_lattice, float cost_coord, float cost_type, float beta, int p_global, int accum_steps, float* grad_theta,
                       float* stats, float* out_delta, float* out_margin, void* stream, void* aux_stream) {
+    MI_NO_POOLED(ab, "mi_dpo_micro_step");
+    MI_NO_POOLED(pb, "mi_dpo_micro_step");
     MI_CHECK(ab, MI_EINVAL, "null argument");
     MI_CHECK(ab->n_pairs >= 1, MI_ESTATE, "the agent's batch handle carries no pairs (mi_batch_set_pairs)");
     MI_CHECK(p_global >= ab->n_pairs, MI_EINVAL, "p_global = %d is below the handle's %d pairs", p_global, ab->n_pairs);

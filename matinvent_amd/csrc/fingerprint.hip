@@ -59,6 +59,7 @@ int mi_structure_fingerprint_offsets(const int* node_off, int B, const int* atom
 
 int mi_structure_fingerprint(const mi_batch* b, const int* atom_types, const float* frac, const float* lattices, const mi_fp_params* params,
                              float* out_fp, float* out_info, void* stream) {
+    MI_NO_POOLED(b, "mi_structure_fingerprint");
     MI_CHECK(b, MI_EINVAL, "structure fingerprint: null handle");
     return fingerprint_launch(b->node_off, b->B, atom_types, frac, lattices, params, out_fp, out_info, (hipStream_t)stream);
 }

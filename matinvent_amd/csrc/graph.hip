@@ -449,6 +449,7 @@ int mi_structure_check_offsets(const int* node_off, int B, const float* frac, co
 }
 
 int mi_structure_check(const mi_batch* b, const float* frac, const float* lattices, float* out, void* stream) {
+    MI_POOL_STREAM(b, stream, "mi_structure_check");
     MI_CHECK(b && frac && lattices && out, MI_EINVAL, "null argument");
     if (b->B == 0) return MI_OK;
     hipLaunchKernelGGL(structure_check_kernel, dim3(b->B), dim3(256), 0, (hipStream_t)stream, frac, lattices, b->node_off, out);

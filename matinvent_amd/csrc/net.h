@@ -5,6 +5,8 @@
 #include "common.h"
 #include "gemm.h"
 
+struct mi_pool;   // pool.hip (include/matinvent_hip_pool.h): the memory behind a pooled batch handle
+
 struct ParamInfo {
     std::string name;
     int64_t off, numel;
@@ -242,6 +244,11 @@ struct mi_batch {
     // sums of squares, and -- forward-only form, which prepares no tape -- the noised inputs and targets
     float *pt_sched = nullptr, *pt_parts = nullptr;   // [B][4], [B][3]
     float* pt_noised = nullptr;                       // in_lat | in_frac | in_types | tar_x | rnd_l | rnd_t
+    // pooled handle (pool.hip, mi_batch_create_pooled): the pool every buffer above was lent by (NULL: the handle owns them),
+    // the two prefix arrays next to node_off_h that the index-table kernels read, and the device copy of the edge prefix
+    mi_pool* pool = nullptr;
+    std::vector<int> edge_off_h, pair_off_h;
+    int* edge_off = nullptr;   // [B + 1] first edge of each crystal (pooled handles only)
     std::vector<void*> allocs;
 };
 
@@ -279,7 +286,24 @@ int ft_micro_run(const char* what, mi_net* agent, mi_batch* ab, mi_net* prior, m
 int net_wgrad_window(mi_net* net, mi_batch* b, int slots);                   // 0: every backward contracts its own rows (default)
 int net_wgrad_flush(mi_net* net, mi_batch* b, float* grad, hipStream_t s);   // grad += the pending micro-steps' node-level weight gradients
 template <typename T>
-int dev_alloc(mi_batch* b, T** p, size_t n);
+int dev_alloc(mi_batch* b, T** p, size_t n);   // hipMalloc, or (pooled handle) a block of the pool: int / unsigned zero-filled, see pool.hip
+void dev_release(mi_batch* b, void* p);        // one buffer of the handle, ahead of its destruction: hipFree, or back to the pool
+// pool.hip: what a pooled handle asks of its pool.  kind = element type of the block: the typed hand-out of include/matinvent_hip_pool.h
+enum PoolKind { POOL_INT = 0, POOL_F32 = 1, POOL_F16 = 2 };
+hipStream_t pool_stream(const mi_pool* pool);
+int pool_alloc(mi_pool* pool, size_t bytes, int kind, void** out);
+void pool_release(mi_pool* pool, void* p);
+void pool_handle_count(mi_pool* pool, int delta);
+int pool_build_tables(mi_batch* b, hipStream_t s);   // the index tables of a pooled handle from node_off / edge_off / pair_off (device)
+// a buffer's clear at set-up: the blocking hipMemset of a handle that owns its memory, or enqueued on the pool's stream
+inline hipError_t batch_memset(const mi_batch* b, void* p, int v, size_t bytes) {
+    return b->pool ? hipMemsetAsync(p, v, bytes, pool_stream(b->pool)) : hipMemset(p, v, bytes);
+}
+// the one-line checks of the entries: a pooled handle where none is taken; a pooled handle used on another stream than its pool's
+#define MI_NO_POOLED(b, what) \
+    MI_CHECK(!(b) || !(b)->pool, MI_EINVAL, what ": a pooled batch handle is not taken here (include/matinvent_hip_pool.h lists the entries that take one)")
+#define MI_POOL_STREAM(b, stream, what) \
+    MI_CHECK(!(b) || !(b)->pool || mi::pool_stream((b)->pool) == (hipStream_t)(stream), MI_EINVAL, what ": a pooled batch handle is used on its pool's stream only")
 int knn_alloc(mi_batch* b, int max_neighbors, int cap_per_node);
 // node_bwd.hip: the node-level BACKWARD chain between two edge stages of the backward pass as one launch per layer boundary
 extern int g_node_bwd, g_node_bwd_min_blocks;

@@ -127,6 +127,7 @@ int mi_pretrain_micro_step(mi_net* net, mi_batch* b, const float* lengths, const
                            uint32_t noise_step, const float* rand_l, const float* rand_x, const float* rand_t, float cost_lattice,
                            float cost_coord, float cost_type, int b_global, int n_global, int accum_steps, float* grad_theta, float* stats,
                            float* out_parts, void* stream) {
+    MI_POOL_STREAM(b, stream, "mi_pretrain_micro_step");
     MI_CHECK(net && b, MI_EINVAL, "null handle");
     MI_CHECK(b->H == net->H && b->L == net->L, MI_EINVAL, "batch was created for a different network");
     MI_CHECK(!b->time_map, MI_EINVAL, "mi_pretrain_micro_step: the handle carries a time map (training runs on the trained grid)");

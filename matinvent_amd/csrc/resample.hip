@@ -124,6 +124,7 @@ using namespace mi;
 extern "C" {
 
 int mi_batch_set_resampling(mi_batch* b, const float* jump_table_host, int n, int r, int j) {
+    MI_NO_POOLED(b, "mi_batch_set_resampling");
     if (!jump_table_host) {
         MI_CHECK(b, MI_EINVAL, "null handle");
         b->rs_on = false;
@@ -153,6 +154,7 @@ int mi_batch_set_resampling(mi_batch* b, const float* jump_table_host, int n, in
 }
 
 int mi_resample_jump(mi_batch* b, int from_level, uint64_t seed, float* atom_types, float* frac, float* lattices, void* stream) {
+    MI_NO_POOLED(b, "mi_resample_jump");
     MI_CHECK(b && atom_types && frac && lattices, MI_EINVAL, "null argument");
     return resample_jump(b, from_level, seed, atom_types, frac, lattices, (hipStream_t)stream);
 }

@@ -259,6 +259,7 @@ int mi_philox_fill(uint64_t seed, uint32_t step, uint32_t draw_id, int64_t elem_
 }
 
 int mi_sampler_init_state(mi_batch* b, uint64_t seed, int T, float* atom_types, float* frac, float* lattices, void* stream) {
+    MI_NO_POOLED(b, "mi_sampler_init_state");
     MI_CHECK(b && atom_types && frac && lattices, MI_EINVAL, "null argument");
     // diffusion.py:277-279; step field of the counter = T + 1
     MI_TRY(mi_philox_fill(seed, (uint32_t)(T + 1), DRAW_X_T, b->node_offset * 3, (int64_t)b->N * 3, 1, frac, stream));
@@ -271,6 +272,7 @@ int mi_sampler_init_state(mi_batch* b, uint64_t seed, int T, float* atom_types, 
 int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int t_start, int t_stop, const float* time_freqs,
                    uint64_t seed, const mi_sampler_noise* noise, const mi_sampler_record* rec, float* atom_types, float* frac,
                    float* lattices, void* stream) {
+    MI_NO_POOLED(b, "mi_sampler_run");
     MI_CHECK(net && b && coef_host && time_freqs && atom_types && frac && lattices, MI_EINVAL, "null argument");
     MI_CHECK(T >= 1 && t_start <= T && t_stop >= 0 && t_stop <= t_start, MI_EINVAL, "bad step range T=%d start=%d stop=%d", T,
              t_start, t_stop);
@@ -330,6 +332,7 @@ int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int 
 }
 
 int mi_sampler_set_keep(mi_batch* b, int keep_lattice, int keep_coords) {
+    MI_NO_POOLED(b, "mi_sampler_set_keep");
     MI_CHECK(b, MI_EINVAL, "null handle");
     b->keep_lattice = keep_lattice != 0;
     b->keep_coords = keep_coords != 0;

@@ -49,6 +49,7 @@ using namespace mi;
 extern "C" {
 
 int mi_batch_set_time_map(mi_batch* b, const int* map_host, int n) {
+    MI_NO_POOLED(b, "mi_batch_set_time_map");
     MI_CHECK(b, MI_EINVAL, "null handle");
     MI_CHECK(n >= 0, MI_EINVAL, "n = %d: must be >= 0", n);
     if (n == 0) {

@@ -676,6 +676,8 @@ int mi_traj_logprob(mi_net* net, mi_batch* bc, mi_batch* bp, const int* t_dev, c
                     const float* atom_types, const float* frac, const float* frac_mid, const float* lattices, const float* next_atom_types,
                     const float* next_frac, const float* next_lattices, float* log_prob, float* pred_corr_l, float* pred_corr_x,
                     float* pred_corr_t, int keep_tape, void* stream) {
+    MI_NO_POOLED(bc, "mi_traj_logprob");
+    MI_NO_POOLED(bp, "mi_traj_logprob");
     MI_CHECK(net && bc && bp, MI_EINVAL, "null handle");
     MI_CHECK(bc != bp, MI_EINVAL, "the corrector and the predictor evaluation need two distinct batch handles");
     MI_CHECK(traj_handles_ok(net, bc, bp), MI_EINVAL, "batch was created for a different network");
@@ -699,6 +701,8 @@ int mi_traj_logprob(mi_net* net, mi_batch* bc, mi_batch* bp, const int* t_dev, c
 
 int mi_traj_logprob_backward(mi_net* net, mi_batch* bc, mi_batch* bp, const float* g_logp, const float* d_corr_l, const float* d_corr_x,
                              const float* d_corr_t, float* grad_theta, void* stream) {
+    MI_NO_POOLED(bc, "mi_traj_logprob_backward");
+    MI_NO_POOLED(bp, "mi_traj_logprob_backward");
     MI_CHECK(net && bc && bp && g_logp && grad_theta, MI_EINVAL, "null argument");
     MI_CHECK(net->W2T != nullptr, MI_ESTATE, "mi_net_set_params must run before backward");
     if (bc->B == 0 || bc->N == 0) return MI_OK;
@@ -708,6 +712,7 @@ int mi_traj_logprob_backward(mi_net* net, mi_batch* bc, mi_batch* bp, const floa
 }
 
 int mi_traj_read_derivatives(const mi_batch* b, float* dl, float* dx, float* dt, void* stream) {
+    MI_NO_POOLED(b, "mi_traj_read_derivatives");
     MI_CHECK(b, MI_EINVAL, "null handle");
     MI_CHECK(b->tr_dl && b->tr_dx && b->tr_dt, MI_ESTATE, "mi_traj_read_derivatives: no taped call has used this handle");
     hipStream_t s = (hipStream_t)stream;
@@ -721,6 +726,8 @@ int mi_traj_pg_step(mi_net* net, mi_batch* bc, mi_batch* bp, const float* coef_d
                     const float* traj_atom_types, const float* traj_frac, const float* traj_frac_mid, const float* traj_lattices,
                     const float* traj_lp_old, const int* t_host, const int* t_dev, const float* adv_dev, float clip_range,
                     const float* w_host, float loss_scale, float* log_prob, float* grad_theta, float* stats, void* stream) {
+    MI_NO_POOLED(bc, "mi_traj_pg_step");
+    MI_NO_POOLED(bp, "mi_traj_pg_step");
     MI_TRY(pg_check(net, bc, bp, coef_dev, T, time_freqs, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, traj_lp_old, t_host, t_dev,
                     adv_dev, clip_range, w_host, grad_theta, stats));
     return pg_enqueue(net, bc, bp, nullptr, nullptr, coef_dev, T, time_freqs, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, traj_lp_old,
@@ -732,6 +739,9 @@ int mi_traj_pg_kl_step(mi_net* net, mi_batch* bc, mi_batch* bp, mi_net* prior, m
                        const float* traj_lattices, const float* traj_lp_old, const int* t_host, const int* t_dev, const float* adv_dev,
                        float clip_range, const float* w_host, float loss_scale, float kl_coef, float* log_prob, float* kl_out,
                        float* grad_theta, float* stats, void* stream, void* aux_stream) {
+    MI_NO_POOLED(bc, "mi_traj_pg_kl_step");
+    MI_NO_POOLED(bp, "mi_traj_pg_kl_step");
+    MI_NO_POOLED(pb, "mi_traj_pg_kl_step");
     MI_TRY(pg_check(net, bc, bp, coef_dev, T, time_freqs, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, traj_lp_old, t_host, t_dev,
                     adv_dev, clip_range, w_host, grad_theta, stats));
     MI_CHECK(prior && pb, MI_EINVAL, "null prior handle");

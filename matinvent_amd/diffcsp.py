@@ -146,9 +146,10 @@ class DiffCSPModule(nn.Module):
             cache[key] = view
         return view
 
-    def make_batch(self, num_atoms, node_offset=0, graph_offset=0) -> CrystalBatch:
-        """A batch handle of the decoder for THIS module's chain: a strided view's handles carry its time map (set here, once, at creation)."""
-        cb = self.decoder.make_batch(num_atoms, node_offset, graph_offset)
+    def make_batch(self, num_atoms, node_offset=0, graph_offset=0, pool=None) -> CrystalBatch:
+        """A batch handle of the decoder for THIS module's chain: a strided view's handles carry its time map (set here, once, at creation).
+        pool: a pool.HandlePool the handle's memory is taken from (training handles of the trained grid)."""
+        cb = self.decoder.make_batch(num_atoms, node_offset, graph_offset, pool=pool)
         if self.time_map is not None:
             tm = self.time_map.numpy()
             _lib.check(_lib.load().mi_batch_set_time_map(cb._h, tm.ctypes.data_as(C.POINTER(C.c_int)), len(tm)), "mi_batch_set_time_map")

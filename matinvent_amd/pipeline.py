@@ -393,7 +393,7 @@ class MatInventDPO(MatInvent):
 class Pretrain:
     """Supervised denoising training of a DiffCSP prior on a crystal dataset (pretrain.fit): the pipeline that produces the
     model the RL pipelines start from.  train_path / val_path: extxyz files (structure.read_extxyz); train_cfg: pretrain.fit's config
-    (lr, epochs, batch_size, accum_steps, max_grad_norm, skip_nonfinite_steps, lr_plateau), merged over the suite's finetune_cfg (the
+    (lr, epochs, batch_size, accum_steps, max_grad_norm, skip_nonfinite_steps, lr_plateau, handle_pool), merged over the suite's finetune_cfg (the
     pipeline wins).  DiffCSPSuite.save_model writes <save_dir>/models/epoch_NNNN every save_freq epochs and <save_dir>/models/final at the
     end: directories that load_model(model_path=...) of this build loads.  `run_rl` is the entry the drop-in's main calls; `reward`,
     `logger` rows and sampling play no part (the logger, when given, receives every epoch's dict).  The MatterGen suite is refused."""

@@ -23,6 +23,7 @@ from .cspnet import _ptr, _stream
 from .data import CrystalBatchData
 from .dist import allreduce_flat_, rank_world, shard_range
 from .optim import FusedAdam, cfg_get, clip_options, epoch_grad_stats, window_closes
+from .pool import HandlePool, parse_handle_pool
 
 STATS = ("loss", "loss_lattice", "loss_coord", "loss_type")   # mi_pretrain_micro_step's stats[0..3]
 _PLAN_TAG, _TIME_TAG = 0x706C616E, 0x74696D65                 # (the two generators never share a key)
@@ -72,13 +73,15 @@ def _counts(batch):
 
 
 def train_step(model, batch, times, noise=None, grad=None, stats=None, b_global=None, n_global=None, accum_steps=1, seed=0, call_id=None,
-               offsets=(0, 0), forward_only=False, out_parts=None):
+               offsets=(0, 0), forward_only=False, out_parts=None, pool=None):
     """One fused micro-step on the current stream: `batch` (num_atoms, lengths, angles, frac_coords, atom_types; a CrystalBatchData) at
     the per-crystal `times` ([B] ints in 1..T).  Accumulates (+=) into `grad` (default: theta.grad, allocated when absent) and `stats`
     (4 device floats in STATS order; returned).  noise = (rand_l, rand_x, rand_t) injects the draws; otherwise Philox draws 7-9 at
     `call_id` (default: the module's running counter, advanced) with the handle's `offsets` = (first atom, first crystal) of this shard
     in the mini-batch.  b_global / n_global: the crystal / atom counts the loss is normalised by (default: the batch's own).
-    forward_only=True: no tape, no backward, `grad` untouched (the validation loss).  The batch handle lives for this call only."""
+    forward_only=True: no tape, no backward, `grad` untouched (the validation loss).  The batch handle lives for this call only.
+    pool: a pool.HandlePool of the current stream -- the handle's memory comes from it and goes back to it, and this call waits for
+    nothing; None: the handle allocates and frees its own memory, which waits for the micro-step."""
     _refuse(model, "train_step")
     lib = _lib.load()
     dev = model.device
@@ -105,10 +108,11 @@ def train_step(model, batch, times, noise=None, grad=None, stats=None, b_global=
     f = lambda x: x.to(dev, torch.float32).contiguous()
     lengths, angles, frac0 = f(batch.lengths), f(batch.angles), f(batch.frac_coords)
     at = batch.atom_types.to(dev, torch.int32).contiguous()
-    t_dev = torch.from_numpy(th).to(dev)
+    # (with a pool nothing below waits for the device: the times go up from pinned memory, behind the stream's work)
+    t_dev = torch.from_numpy(th).to(dev) if pool is None else torch.from_numpy(th).pin_memory().to(dev, non_blocking=True)
     nz = (None, None, None) if noise is None else tuple(f(x) for x in noise)
     model.decoder.sync()
-    cb = model.make_batch(na, int(offsets[0]), int(offsets[1]))   # (its own handle: never the module's cache)
+    cb = model.make_batch(na, int(offsets[0]), int(offsets[1]), pool=pool)   # (its own handle: never the module's cache)
     try:
         _lib.check(lib.mi_pretrain_micro_step(
             model.decoder._h, cb._h, _ptr(lengths), _ptr(angles), _ptr(frac0), _ptr(at), _ptr(model.time_embedding.freqs),
@@ -119,7 +123,9 @@ def train_step(model, batch, times, noise=None, grad=None, stats=None, b_global=
     finally:
         # the handle's memory is freed here, which makes the host wait for the micro-step (hipFree waits for the device in any case; the
         # explicit wait on this stream keeps that from resting on the runtime's behaviour)
-        torch.cuda.current_stream().synchronize()
+        # -- a pooled handle frees nothing: its blocks go back to the pool in stream order, and no wait is made
+        if pool is None:
+            torch.cuda.current_stream().synchronize()
         cb.release()
     return stats
 
@@ -143,7 +149,7 @@ def _slice_noise(noise, rows, na_all):
     return noise[0][lo:hi], noise[1][n0:n1], noise[2][n0:n1]
 
 
-def _eval_enqueue(model, data_list, batch_size, seed, times, acc):
+def _eval_enqueue(model, data_list, batch_size, seed, times, acc, pool=None):
     """`evaluate` without the read-back: every mini-batch of the set in order, forward-only, normalised by the counts of the WHOLE set (so
     the four sums are the set's losses whatever batch_size is), into the 4 device floats `acc`."""
     n = len(data_list)
@@ -166,23 +172,23 @@ def _eval_enqueue(model, data_list, batch_size, seed, times, acc):
                 continue
             # (the noise is indexed by the crystal's and the atom's position in the SET: the draws do not depend on batch_size either)
             train_step(model, _as_batch([data_list[i] for i in own], model.device), tt[own], stats=acc, b_global=n, n_global=sum(na), seed=seed,
-                       call_id=EVAL_CALL, offsets=(sum(na[:own[0]]), own[0]), forward_only=True)
+                       call_id=EVAL_CALL, offsets=(sum(na[:own[0]]), own[0]), forward_only=True, pool=pool)
     finally:
         model.train(was_training)
     return acc
 
 
-def evaluate(model, data_list, batch_size, seed=0, times=None):
+def evaluate(model, data_list, batch_size, seed=0, times=None, pool=None):
     """The four losses of `data_list` under the current weights, forward-only: dict(loss, loss_lattice, loss_coord, loss_type), each the
     mean over ALL elements of the set (mini-batches weighted by their element counts: the result does not depend on batch_size beyond
     fp32 summation order).  times=None: one time per crystal from draw_times(len, T, 0, 0, seed); times=k: every crystal at time k
-    (the per-time loss curve).  Noise: Philox at call id 0 under `seed`.  One host read."""
+    (the per-time loss curve).  Noise: Philox at call id 0 under `seed`.  One host read.  pool: train_step's."""
     _refuse(model, "evaluate")
     if int(batch_size) < 1:
         raise ValueError(f"evaluate: batch_size = {batch_size}: must be >= 1")
     if len(data_list) == 0:
         raise ValueError("evaluate: an empty set")
-    acc = _eval_enqueue(model, data_list, batch_size, seed, times, torch.zeros(4, device=model.device))
+    acc = _eval_enqueue(model, data_list, batch_size, seed, times, torch.zeros(4, device=model.device), pool=pool)
     allreduce_flat_(acc)
     return dict(zip(STATS, acc.tolist()))
 
@@ -206,7 +212,9 @@ def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging
     """Train `model` (a DiffCSPModule of the trained grid) on `data_list` (CrystalData records).  cfg (key or attribute access): lr,
     epochs, batch_size; accum_steps (default 1: mini-batches per optimizer step, each normalised by its own counts and 1 / accum_steps);
     shuffle (default true); max_grad_norm / skip_nonfinite_steps (optim.clip_options); lr_plateau = {factor, patience, min_lr}
-    (ReduceLROnPlateau on the validation loss, or on the training loss without a validation set).
+    (ReduceLROnPlateau on the validation loss, or on the training loss without a validation set); handle_pool = false (default), true or
+    {max_bytes: ...}: one pool.HandlePool for the run, behind every mini-batch's handle, closed at the end (pool.parse_handle_pool; its last
+    stats() are left in model.handle_pool_stats).
     One FusedAdam for the whole run; an optimizer step wherever optim.window_closes says so; one host read per epoch (the validation
     pass of `val_list` -- pretrain.evaluate's, same times and noise every epoch -- rides in it).  noise_fn(epoch, step) -> (rand_l,
     rand_x, rand_t) of the whole mini-batch injects the noise and times_fn(epoch, step, B) -> [B] ints in 1..T replaces draw_times (parity
@@ -234,6 +242,7 @@ def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging
         raise ValueError(f"fit: accum_steps = {accum}: must be >= 1")
     shuffle = bool(cfg_get(cfg, "shuffle", True))
     opt = clip_options(cfg)
+    pool_kw = parse_handle_pool(cfg_get(cfg, "handle_pool"))
     rank, world = rank_world()
     dev = model.device
     theta = model.decoder.theta
@@ -244,6 +253,24 @@ def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging
         theta.grad = torch.zeros_like(theta)
     n = len(data_list)
     out = []
+    pool = None if pool_kw is None else HandlePool(**pool_kw)
+    try:
+        return _fit_epochs(model, data_list, val_list, seed, noise_fn, log, on_epoch_end, times_fn, epochs, batch_size, accum, shuffle, optimizer,
+                           plateau, pool, out)
+    finally:
+        if pool is not None:
+            model.__dict__["handle_pool_stats"] = pool.stats()   # (the run's pool just before it is closed: HandlePool.stats())
+            pool.close()
+
+
+def _fit_epochs(model, data_list, val_list, seed, noise_fn, log, on_epoch_end, times_fn, epochs, batch_size, accum, shuffle, optimizer, plateau, pool, out):
+    """fit's epoch loop (its docstring); `pool`: the run's HandlePool or None."""
+    from .finetune import _epoch_reduce
+    rank, world = rank_world()
+    dev = model.device
+    theta = model.decoder.theta
+    T = model.beta_scheduler.timesteps
+    n = len(data_list)
     for epoch in range(epochs):
         model.train()
         optimizer.zero_grad(set_to_none=False)
@@ -257,13 +284,14 @@ def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging
                 noise = None if noise_fn is None else _slice_noise(noise_fn(epoch, step), rows, [int(d.num_atoms) for d in items])
                 times = draw_times(len(idx), T, epoch, step, seed) if times_fn is None else np.asarray(times_fn(epoch, step, len(idx)))
                 train_step(model, _as_batch(own, dev), times[rows[0]:rows[1]], noise=noise, grad=theta.grad,
-                           stats=acc, b_global=b_glob, n_global=n_glob, accum_steps=accum, seed=seed, call_id=model._noise_calls, offsets=offsets)
+                           stats=acc, b_global=b_glob, n_global=n_glob, accum_steps=accum, seed=seed, call_id=model._noise_calls, offsets=offsets,
+                           pool=pool)
             if window_closes(step + 1, accum, len(plan)):
                 allreduce_flat_(theta.grad)
                 optimizer.step()
                 optimizer.zero_grad(set_to_none=False)
         if val_list is not None:
-            acc = torch.cat([acc, _eval_enqueue(model, val_list, batch_size, seed, None, torch.zeros(4, device=dev))])
+            acc = torch.cat([acc, _eval_enqueue(model, val_list, batch_size, seed, None, torch.zeros(4, device=dev), pool=pool)])
         a = _epoch_reduce(acc, "fit", optimizer)   # the epoch's only host read
         d = dict(train_loss=a[0] / len(plan), lattice_loss=a[1] / len(plan), coord_loss=a[2] / len(plan), type_loss=a[3] / len(plan))
         k = 4

@@ -2,13 +2,16 @@
 mi_ft_micro_step on the same set in the same process, alternating, and the cost of creating plus releasing a mini-batch's batch handle
 (what pretrain.train_step pays per micro-step for not keeping handles) as a share of the step.
 
-    python scripts/pretrain_step_timing.py [--iters 20] [--json OUT]
+    python scripts/pretrain_step_timing.py [--iters 20] [--pool] [--json OUT]
 
 Two sets: 256 crystals x 20 atoms, and the reference's default-size fine-tune set (18 crystals, SampleDataset atom counts).  Prints one
 JSON line per set: ms per micro-step of both entries on kept handles (device noise; the fine-tune entry with its frozen prior's forward
 forked onto a second stream, as ft_step runs it), the forward-only form, ms per handle create + release (host wall clock, the device idle),
 ms per pretrain.train_step (which does both, and allocates the tape inside the fresh handle), and the ratios:
-handle_share = create + release / train_step, overhead_share = (train_step - the entry on a kept handle) / train_step.  The script asserts nothing about the outcome."""
+handle_share = create + release / train_step, overhead_share = (train_step - the entry on a kept handle) / train_step.  The script asserts nothing about the outcome.
+--pool adds, per set: ms per pretrain.train_step on a POOLED handle in steady state (pool.HandlePool, warmed up; host wall
+clock like the unpooled one, measured alternating with it -- unpooled, pooled, unpooled, pooled -- in this process), ms per pooled handle
+create + release alone, their ratios to the unpooled figures, and the pool's statistics."""
 import argparse
 import ctypes as C
 import json
@@ -50,7 +53,7 @@ def wall(fn, iters):
     return (time.perf_counter() - t0) * 1e3 / iters
 
 
-def measure(agent, prior, na, iters, g):
+def measure(agent, prior, na, iters, g, with_pool=False):
     from matinvent_amd import _lib, finetune, pretrain, streams
     from matinvent_amd.cspnet import _ptr, _stream
     from matinvent_amd.data import CrystalBatchData, CrystalData
@@ -101,17 +104,41 @@ def measure(agent, prior, na, iters, g):
     ms_whole = wall(whole, iters)
     pre, ftm = 0.5 * (ms_pre + ms_pre2), 0.5 * (ms_ft + ms_ft2)
     cb.release()
+    extra = {}
+    if with_pool:
+        from matinvent_amd.pool import HandlePool
+        pool = HandlePool()
+
+        def whole_pooled():
+            step[0] += 1
+            pretrain.train_step(agent, batch, pretrain.draw_times(B, T, 0, step[0], 0), grad=grad, stats=st4, pool=pool)
+
+        def handle_pooled():
+            agent.make_batch(na, pool=pool).release()
+
+        cl, po = [], []
+        for _ in range(2):
+            cl.append(wall(whole, iters))
+            po.append(wall(whole_pooled, iters))
+        ms_hp = wall(handle_pooled, iters)
+        ps = pool.stats()
+        pool.close()
+        extra = dict(ms_train_step_wall_alternating=[round(v, 3) for v in cl], ms_train_step_pooled_wall=[round(v, 3) for v in po],
+                     pooled_over_unpooled_train_step=round(sum(po) / sum(cl), 4), ms_pooled_handle_create_release=round(ms_hp, 3),
+                     pooled_over_kept_handle_entry=round(0.5 * sum(po) / pre, 4), pool_stats=ps)
     return dict(crystals=B, atoms=N, edges=sum(n * n for n in na), iters=iters, ms_ft_micro_step=[round(ms_ft, 3), round(ms_ft2, 3)],
                 ms_pretrain_micro_step=[round(ms_pre, 3), round(ms_pre2, 3)], pretrain_over_ft=round(pre / ftm, 4),
                 ms_pretrain_forward_only=round(ms_fwd, 3), ms_handle_create_release=round(ms_handle, 3), ms_train_step_wall=round(ms_whole, 3),
                 handle_share_of_train_step=round(ms_handle / ms_whole, 4),
-                overhead_share_of_train_step=round((ms_whole - pre) / ms_whole, 4), finite=bool(torch.isfinite(grad).all() and torch.isfinite(st4).all()))
+                overhead_share_of_train_step=round((ms_whole - pre) / ms_whole, 4), finite=bool(torch.isfinite(grad).all() and torch.isfinite(st4).all()),
+                **extra)
 
 
 def main():
     from matinvent_amd.sampling import SampleDataset
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--pool", action="store_true", help="also time train_step on pooled handles (DESIGN 39)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     H, L, F, T = 512, 6, 128, 1000
@@ -124,7 +151,7 @@ def main():
     np.random.seed(0)
     rows = []
     for name, na in (("256x20", [20] * 256), ("reference-default-18", [int(n) for n in SampleDataset(18).num_atoms])):
-        row = dict(set=name, **measure(agent, prior, na, a.iters, g))
+        row = dict(set=name, **measure(agent, prior, na, a.iters, g, with_pool=a.pool))
         print(json.dumps(row), flush=True)
         rows.append(row)
     if a.json:
