@@ -266,9 +266,14 @@ POOL_SIGNATURES = {
     "mi_batch_index_table": (_L, [_P, _I, C.POINTER(_I), _L]),
 }
 
+# the weight-average extension, include/matinvent_hip_ema.h (the fused Adam step with an exponential moving average of the weights)
+EMA_SIGNATURES = {
+    "mi_adam_step_ema": (_I, [_P, _P, _P, _P, _P, _L, _I, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P, _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
-                        DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, PRETRAIN_SIGNATURES)
+                        DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, PRETRAIN_SIGNATURES)
 
 _lib = None
 

@@ -11,21 +11,10 @@
 
 #include "../../include/matinvent_hip_optim.h"
 #include "common.h"
+#include "optim_state.h"
 
 namespace mi {
 
-// the state block, word by word as include/matinvent_hip_optim.h lists it
-struct OptimState {
-    float coef, lr_over_bc1, inv_sqrt_bc2;
-    unsigned apply, adam_steps, applied, skipped, clipped, nonfinite;
-    float last_norm, norm_max;
-    unsigned reserved0;
-    double norm_sum;
-    unsigned reserved1, reserved2;
-};
-static_assert(sizeof(OptimState) == 64 && offsetof(OptimState, norm_sum) == 48 && offsetof(OptimState, last_norm) == 36, "state block layout");
-
-constexpr int OPT_BLOCK = 256;        // threads per block
 constexpr int OPT_UNROLL = 4;         // 16-byte loads in flight per thread and sweep
 constexpr int OPT_MAX_BLOCKS = 2048;  // 8 blocks on each of 256 CUs: fills the chip, the rest is grid-stride
 constexpr int64_t OPT_BLOCK_ELEMS = (int64_t)OPT_BLOCK * OPT_UNROLL * 4;   // elements of one block in one sweep
@@ -131,16 +120,6 @@ __global__ __launch_bounds__(OPT_BLOCK) void grad_finish_kernel(const double* __
 }
 
 // Item i < units: elements 4 i .. 4 i + 3 (VEC) or element i; with VEC, item `units` is the n % 4 elements behind the last whole float4.
-__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float gscale, float coef, float lr_over_bc1, float inv_sqrt_bc2,
-                                         float b1, float b2, float eps) {
-    const float gi = g * gscale * coef;   // (coef == 1: adam_kernel's g * gscale, bit for bit)
-    const float mi_ = b1 * m + (1.0f - b1) * gi;
-    const float vi = b2 * v + (1.0f - b2) * gi * gi;
-    m = mi_;
-    v = vi;
-    p -= lr_over_bc1 * (mi_ / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(OPT_BLOCK) void adam_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                                  float* __restrict__ v, int64_t n, const OptimState* __restrict__ st, float b1, float b2,
@@ -170,8 +149,6 @@ __global__ __launch_bounds__(OPT_BLOCK) void adam_guarded_kernel(float* __restri
         for (int64_t k = units * 4; k < n; ++k) adam_one(p[k], g[k], m[k], v[k], gscale, coef, lr_over_bc1, inv_sqrt_bc2, b1, b2, eps);
     }
 }
-
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace mi
 

@@ -393,13 +393,19 @@ class MatInventDPO(MatInvent):
 class Pretrain:
     """Supervised denoising training of a DiffCSP prior on a crystal dataset (pretrain.fit): the pipeline that produces the
     model the RL pipelines start from.  train_path / val_path: extxyz files (structure.read_extxyz); train_cfg: pretrain.fit's config
-    (lr, epochs, batch_size, accum_steps, max_grad_norm, skip_nonfinite_steps, lr_plateau, handle_pool), merged over the suite's finetune_cfg (the
+    (lr, epochs, batch_size, accum_steps, max_grad_norm, skip_nonfinite_steps, lr_plateau, handle_pool, ema), merged over the suite's finetune_cfg (the
     pipeline wins).  DiffCSPSuite.save_model writes <save_dir>/models/epoch_NNNN every save_freq epochs and <save_dir>/models/final at the
     end: directories that load_model(model_path=...) of this build loads.  `run_rl` is the entry the drop-in's main calls; `reward`,
-    `logger` rows and sampling play no part (the logger, when given, receives every epoch's dict).  The MatterGen suite is refused."""
+    `logger` rows and sampling play no part (the logger, when given, receives every epoch's dict).  The MatterGen suite is refused.
+    Every models/epoch_NNNN also gets train_state.ckpt (pretrain.save_training_state: raw weights, optimizer, scheduler, counters), written by
+    rank 0; resume_from=<such a directory> continues that run, on every rank, as the same run.  With train_cfg.ema set, last.ckpt
+    in those directories and in models/final holds the AVERAGED weights -- what the RL pipelines load as their prior -- marked
+    "weights": "ema"; the raw weights live in train_state.ckpt."""
+
+    TRAIN_STATE = "train_state.ckpt"
 
     def __init__(self, model_suite, train_path, save_dir, train_cfg=None, val_path=None, save_freq=10, seed=0, device=None, logger=None,
-                 reward=None, **kwargs):
+                 reward=None, resume_from=None, **kwargs):
         from .suite import MatterGenSuite
         if isinstance(model_suite, MatterGenSuite):
             raise ValueError("Pretrain needs the DiffCSP suite: the MatterGen-shaped module has no supervised training here")
@@ -408,6 +414,7 @@ class Pretrain:
         self.model_suite, self.logger = model_suite, logger
         self.train_path, self.val_path = train_path, val_path
         self.save_dir, self.save_freq, self.seed = save_dir, max(1, int(save_freq)), int(seed)
+        self.resume_from = resume_from
         self.device = get_device(device)
         self.cfg = C.create(kwargs)
         self.train_cfg = C.merge(model_suite.finetune_cfg, train_cfg)
@@ -434,8 +441,19 @@ class Pretrain:
         self.model.to(self.device)
         return self.model
 
+    def _save(self, name):
+        """models/<name>: the average inside FusedAdam.ema_weights when the run keeps one, the weights themselves otherwise."""
+        path = os.path.join(self.models_dir, name)
+        opt = self.model.__dict__.get("fit_optimizer")
+        if opt is not None and opt.ema_decay is not None:
+            with opt.ema_weights(self.model.decoder):
+                self.model_suite.save_model(self.model, path, extra={"weights": "ema"})
+        else:
+            self.model_suite.save_model(self.model, path)
+        return path
+
     def run_rl(self):
-        from .pretrain import fit
+        from .pretrain import fit, load_training_state, save_training_state
         rank, _ = rank_world()
         train = self.read_dataset(self.train_path)
         val = self.read_dataset(self.val_path) if self.val_path else None
@@ -449,9 +467,15 @@ class Pretrain:
             if self.logger is not None:
                 self.logger.log(dict(d), step=epoch)
             if (epoch + 1) % self.save_freq == 0:
-                self.model_suite.save_model(self.model, os.path.join(self.models_dir, f"epoch_{epoch:0>4d}"))
+                self._save(f"epoch_{epoch:0>4d}")
 
-        self.history = fit(self.model, train, self.train_cfg, val_list=val, seed=self.seed, on_epoch_end=on_epoch_end)
+        def checkpoint(epoch, state):   # (behind on_epoch_end: the epoch's directory exists)
+            save_training_state(os.path.join(self.models_dir, f"epoch_{epoch:0>4d}", self.TRAIN_STATE), state)
+        checkpoint.due = lambda epoch: rank == 0 and (epoch + 1) % self.save_freq == 0
+
+        resume = load_training_state(os.path.join(self.resume_from, self.TRAIN_STATE)) if self.resume_from else None
+        self.history = fit(self.model, train, self.train_cfg, val_list=val, seed=self.seed, on_epoch_end=on_epoch_end, checkpoint=checkpoint,
+                           resume=resume)
         if rank == 0:
-            self.model_suite.save_model(self.model, os.path.join(self.models_dir, "final"))
+            self._save("final")
         return self.history

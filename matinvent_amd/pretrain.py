@@ -12,8 +12,11 @@ call id per micro-step, indexed by the crystal's and the atom's position in the 
 mini-batch draws).  A mini-batch's batch handle is created for its atom counts and released after its micro-step: device memory does
 not grow with the number of distinct mini-batches, and the module's handle cache (sampling, ft_step) is left alone.
 """
+import contextlib
 import ctypes as C
 import logging
+import os
+import tempfile
 
 import numpy as np
 import torch
@@ -22,7 +25,7 @@ from . import _lib
 from .cspnet import _ptr, _stream
 from .data import CrystalBatchData
 from .dist import allreduce_flat_, rank_world, shard_range
-from .optim import FusedAdam, cfg_get, clip_options, epoch_grad_stats, window_closes
+from .optim import FusedAdam, cfg_get, clip_options, ema_decay_at, epoch_grad_stats, parse_ema, window_closes
 from .pool import HandlePool, parse_handle_pool
 
 STATS = ("loss", "loss_lattice", "loss_coord", "loss_type")   # mi_pretrain_micro_step's stats[0..3]
@@ -208,13 +211,100 @@ def plateau_scheduler(optimizer, spec):
     return torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="min", **kw)
 
 
-def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging.info, on_epoch_end=None, times_fn=None):
+META_KEYS = ("seed", "batch_size", "accum_steps", "shuffle", "n_train", "n_val", "world_size", "T", "numel", "max_grad_norm", "skip_nonfinite",
+             "ema_decay", "ema_warmup", "ema_validate", "lr_plateau")
+
+
+def run_meta(model, optimizer, plateau, seed, batch_size, accum_steps, shuffle, n_train, n_val, ema):
+    """What decides a run's batch plan, noise and arithmetic besides its weights (META_KEYS): a checkpoint is continued only under the
+    same values (check_meta)."""
+    o = optimizer.options()
+    return dict(seed=int(seed), batch_size=int(batch_size), accum_steps=int(accum_steps), shuffle=bool(shuffle), n_train=int(n_train),
+                n_val=int(n_val), world_size=int(rank_world()[1]), T=int(model.beta_scheduler.timesteps), numel=int(model.decoder.theta.numel()),
+                max_grad_norm=o["max_grad_norm"], skip_nonfinite=o["skip_nonfinite"], ema_decay=o["ema_decay"], ema_warmup=o["ema_warmup"],
+                ema_validate=None if ema is None else bool(ema["validate"]), lr_plateau=plateau is not None)
+
+
+def check_meta(saved, now):
+    """ValueError naming the first key under which the saved run and this one differ: a different batch plan, world size or option would
+    silently be a different run."""
+    for k in META_KEYS:
+        if k not in saved:
+            raise ValueError(f"resume: the saved state's meta has no {k}")
+        if saved[k] != now[k]:
+            raise ValueError(f"resume: {k} = {now[k]!r} in this run, {saved[k]!r} in the saved state")
+
+
+def _to_cpu(x):
+    if torch.is_tensor(x):
+        return x.detach().cpu().clone()
+    if isinstance(x, dict):
+        return {k: _to_cpu(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_to_cpu(v) for v in x)
+    return x
+
+
+def training_state(model, optimizer, plateau, epoch, history, meta):
+    """Everything fit needs to continue a run as the same run, as a plain dict of host copies: the raw weights `theta` (never the
+    average), the optimizer's and the plateau scheduler's state_dict, the module's Philox call counter, `epoch` = the next epoch to run,
+    the per-epoch history so far and `meta` (run_meta).  Reads the device (one copy per tensor)."""
+    return dict(theta=_to_cpu(model.decoder.theta.data), optimizer=_to_cpu(optimizer.state_dict()),
+                plateau=None if plateau is None else _to_cpu(plateau.state_dict()), noise_calls=int(getattr(model, "_noise_calls", 0)),
+                epoch=int(epoch), history=[dict(d) for d in history], meta=dict(meta))
+
+
+def save_training_state(path, state, _save=None):
+    """Write `state` to `path` through a temporary file in the same directory and os.replace: a job killed in the middle leaves the old
+    file (or none), never half of one, and no temporary file.  (_save(obj, file): the writer, torch.save; a test passes one that fails.)"""
+    path = os.path.abspath(path)
+    fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(path))
+    try:
+        with os.fdopen(fd, "wb") as f:
+            (_save or torch.save)(state, f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return path
+
+
+def load_training_state(path):
+    """The inverse of save_training_state, on the host (map_location="cpu")."""
+    return torch.load(path, map_location="cpu", weights_only=False)
+
+
+def _restore(model, optimizer, plateau, state, meta):
+    check_meta(state["meta"], meta)
+    theta = model.decoder.theta
+    with torch.no_grad():
+        theta.data.copy_(state["theta"].to(theta.device))
+    model.decoder.mark_dirty()
+    optimizer.load_state_dict(state["optimizer"])
+    if plateau is not None:
+        plateau.load_state_dict(state["plateau"])
+    model._noise_calls = int(state["noise_calls"])
+    return int(state["epoch"]), [dict(d) for d in state["history"]]
+
+
+def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging.info, on_epoch_end=None, times_fn=None, checkpoint=None,
+        resume=None):
     """Train `model` (a DiffCSPModule of the trained grid) on `data_list` (CrystalData records).  cfg (key or attribute access): lr,
     epochs, batch_size; accum_steps (default 1: mini-batches per optimizer step, each normalised by its own counts and 1 / accum_steps);
     shuffle (default true); max_grad_norm / skip_nonfinite_steps (optim.clip_options); lr_plateau = {factor, patience, min_lr}
     (ReduceLROnPlateau on the validation loss, or on the training loss without a validation set); handle_pool = false (default), true or
     {max_bytes: ...}: one pool.HandlePool for the run, behind every mini-batch's handle, closed at the end (pool.parse_handle_pool; its last
-    stats() are left in model.handle_pool_stats).
+    stats() are left in model.handle_pool_stats); ema = null (default), a decay or {decay, warmup: true, validate: true} (optim.parse_ema): the
+    optimizer keeps an exponential moving average of the weights in its own pass, with `validate` the validation pass runs on the
+    average (FusedAdam.ema_weights: val_loss, and lr_plateau behind it, follow the average) and every epoch dict gains `ema_decay`, the
+    decay of the epoch's last step.  The optimizer is then left in model.fit_optimizer (ema_weights for sampling or saving the average).
+    checkpoint(epoch, state) runs after on_epoch_end with state = training_state(...) -- at the epochs its optional attribute
+    `due(epoch)` accepts, every epoch without one -- and resume=state continues such a run at
+    state["epoch"] as the same run, bit for bit: weights, moments, average, the device's step count, learning rate, plateau counters, the
+    Philox call counter.  `epochs` may be larger than the saved run's; any other difference (META_KEYS) is a ValueError naming the key.
+    The returned history then starts with the loaded epochs.
     One FusedAdam for the whole run; an optimizer step wherever optim.window_closes says so; one host read per epoch (the validation
     pass of `val_list` -- pretrain.evaluate's, same times and noise every epoch -- rides in it).  noise_fn(epoch, step) -> (rand_l,
     rand_x, rand_t) of the whole mini-batch injects the noise and times_fn(epoch, step, B) -> [B] ints in 1..T replaces draw_times (parity
@@ -243,35 +333,45 @@ def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging
     shuffle = bool(cfg_get(cfg, "shuffle", True))
     opt = clip_options(cfg)
     pool_kw = parse_handle_pool(cfg_get(cfg, "handle_pool"))
+    ema = parse_ema(cfg_get(cfg, "ema"))
     rank, world = rank_world()
     dev = model.device
     theta = model.decoder.theta
     T = model.beta_scheduler.timesteps
+    if ema is not None:
+        opt = dict(opt, ema_decay=ema["decay"], ema_warmup=ema["warmup"])
     optimizer = FusedAdam([theta], lr=lr, **opt)
     plateau = plateau_scheduler(optimizer, cfg_get(cfg, "lr_plateau"))
     if theta.grad is None:
         theta.grad = torch.zeros_like(theta)
     n = len(data_list)
-    out = []
+    out, first, meta = [], 0, None
+    if checkpoint is not None or resume is not None:
+        meta = run_meta(model, optimizer, plateau, seed, batch_size, accum, shuffle, n, 0 if val_list is None else len(val_list), ema)
+    if resume is not None:
+        first, out = _restore(model, optimizer, plateau, resume, meta)
+    if ema is not None:
+        model.__dict__["fit_optimizer"] = optimizer
     pool = None if pool_kw is None else HandlePool(**pool_kw)
     try:
         return _fit_epochs(model, data_list, val_list, seed, noise_fn, log, on_epoch_end, times_fn, epochs, batch_size, accum, shuffle, optimizer,
-                           plateau, pool, out)
+                           plateau, pool, out, first, ema, checkpoint, meta)
     finally:
         if pool is not None:
             model.__dict__["handle_pool_stats"] = pool.stats()   # (the run's pool just before it is closed: HandlePool.stats())
             pool.close()
 
 
-def _fit_epochs(model, data_list, val_list, seed, noise_fn, log, on_epoch_end, times_fn, epochs, batch_size, accum, shuffle, optimizer, plateau, pool, out):
-    """fit's epoch loop (its docstring); `pool`: the run's HandlePool or None."""
+def _fit_epochs(model, data_list, val_list, seed, noise_fn, log, on_epoch_end, times_fn, epochs, batch_size, accum, shuffle, optimizer, plateau, pool, out,
+                first=0, ema=None, checkpoint=None, meta=None):
+    """fit's epoch loop (its docstring); `pool`: the run's HandlePool or None; `first`: the epoch to start at; `ema`: parse_ema's dict."""
     from .finetune import _epoch_reduce
     rank, world = rank_world()
     dev = model.device
     theta = model.decoder.theta
     T = model.beta_scheduler.timesteps
     n = len(data_list)
-    for epoch in range(epochs):
+    for epoch in range(first, epochs):
         model.train()
         optimizer.zero_grad(set_to_none=False)
         acc = torch.zeros(4, device=dev)
@@ -291,8 +391,20 @@ def _fit_epochs(model, data_list, val_list, seed, noise_fn, log, on_epoch_end, t
                 optimizer.step()
                 optimizer.zero_grad(set_to_none=False)
         if val_list is not None:
-            acc = torch.cat([acc, _eval_enqueue(model, val_list, batch_size, seed, None, torch.zeros(4, device=dev), pool=pool)])
+            # (with ema.validate the set's loss is the average's: one exchange and one re-pack of the weights each way, all enqueued)
+            with optimizer.ema_weights(model.decoder) if ema is not None and ema["validate"] else contextlib.nullcontext():
+                acc = torch.cat([acc, _eval_enqueue(model, val_list, batch_size, seed, None, torch.zeros(4, device=dev), pool=pool)])
+        k_ema = None
+        if ema is not None and optimizer.guarded:   # the applied-step count rides in the epoch's read (rank 0's: the ranks agree)
+            k_ema = acc.numel()
+            s_dev = optimizer.adam_steps()
+            acc = torch.cat([acc, s_dev if rank == 0 else torch.zeros_like(s_dev)])
         a = _epoch_reduce(acc, "fit", optimizer)   # the epoch's only host read
+        s_ema = None
+        if k_ema is not None:
+            s_ema = int(round(a.pop(k_ema)))
+        elif ema is not None:
+            s_ema = int(optimizer.state[theta]["step"])
         d = dict(train_loss=a[0] / len(plan), lattice_loss=a[1] / len(plan), coord_loss=a[2] / len(plan), type_loss=a[3] / len(plan))
         k = 4
         if val_list is not None:
@@ -301,6 +413,8 @@ def _fit_epochs(model, data_list, val_list, seed, noise_fn, log, on_epoch_end, t
         d["lr"] = float(optimizer.param_groups[0]["lr"])
         if len(a) > k:
             d.update(epoch_grad_stats(a[k:]))
+        if ema is not None:
+            d["ema_decay"] = ema_decay_at(ema["decay"], ema["warmup"], s_ema)
         if plateau is not None:
             plateau.step(d["val_loss"] if val_list is not None else d["train_loss"])
         out.append(d)
@@ -308,4 +422,6 @@ def _fit_epochs(model, data_list, val_list, seed, noise_fn, log, on_epoch_end, t
             log(f"Epoch {epoch}: " + ", ".join(f"{k_}: {v_:.6g}" for k_, v_ in d.items()))
         if on_epoch_end is not None:
             on_epoch_end(epoch, d)
+        if checkpoint is not None and getattr(checkpoint, "due", lambda e: True)(epoch):   # (`due`: the state is copied off the device only then)
+            checkpoint(epoch, training_state(model, optimizer, plateau, epoch + 1, out, meta))
     return out

@@ -106,11 +106,12 @@ class DiffCSPSuite(ModelSuite):
             batch_size = self.finetune_cfg.batch_size
         return CrystalLoader(CrystalDataset(samples, rewards), batch_size=batch_size, shuffle=shuffle)
 
-    def save_model(self, model, save_dir):
-        """Same artefacts as the reference: last.ckpt = {"state_dict", "config"} + hparams.yaml."""
+    def save_model(self, model, save_dir, extra=None):
+        """Same artefacts as the reference: last.ckpt = {"state_dict", "config"} + hparams.yaml.  extra: further entries of last.ckpt
+        (pipeline.Pretrain marks averaged weights with {"weights": "ema"})."""
         os.makedirs(save_dir, exist_ok=True)
         cfg = model.config
-        torch.save({"state_dict": {k: v.cpu() for k, v in model.state_dict().items()}, "config": C.to_container(cfg, resolve=True)},
+        torch.save({"state_dict": {k: v.cpu() for k, v in model.state_dict().items()}, "config": C.to_container(cfg, resolve=True), **(extra or {})},
                    os.path.join(save_dir, "last.ckpt"))
         C.save(cfg, os.path.join(save_dir, "hparams.yaml"))
 
