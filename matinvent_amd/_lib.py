@@ -271,9 +271,24 @@ EMA_SIGNATURES = {
     "mi_adam_step_ema": (_I, [_P, _P, _P, _P, _P, _L, _I, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _I, _P, _P]),
 }
 
+# the guidance extension, include/matinvent_hip_guidance.h (the property-conditioned embedding, its training micro-step, the guided step)
+GUIDANCE_MAX_FREQS, GUIDANCE_CLAMP = 12, 8.0   # include/matinvent_hip_guidance.h
+
+GUIDANCE_SIGNATURES = {
+    "mi_net_set_latent": (_I, [_P, _I, _I]),
+    "mi_net_latent_dim": (_I, [_P]),
+    "mi_crystal_embedding": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "mi_guidance_drop_mask": (_I, [_U64, _U32, _L, _I, C.c_float, _P, _P]),
+    "mi_pretrain_micro_step_cond": (_I, PRETRAIN_SIGNATURES["mi_pretrain_micro_step"][1][:-1] + [_P, _P, _P, C.c_float, _P]),
+    "mi_batch_set_guidance": (_I, [_P, _P, C.POINTER(C.c_float), C.POINTER(_I), _I, _I, C.c_float]),
+    "mi_batch_clear_guidance": (_I, [_P]),
+    "mi_guidance_combine": (_I, [_P, _P, C.c_float, _L, _L, _L, _P, _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
-                        DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, PRETRAIN_SIGNATURES)
+                        DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
+                        PRETRAIN_SIGNATURES)
 
 _lib = None
 

@@ -1639,6 +1639,8 @@ int mi_ft_micro_step(mi_net* agent, mi_batch* ab, mi_net* prior, mi_batch* pb, c
                      float sigma_t, float sigma_norm, uint64_t seed, uint32_t noise_step, const float* rand_l, const float* rand_x,
                      const float* rand_t, float cost_lattice, float cost_coord, float cost_type, float kl_sigma, int b_global, int accum_steps,
                      float* grad_theta, float* stats, float* out_sample_loss, float* out_kl, void* stream, void* aux_stream) {
+    MI_NO_LATENT(agent, "mi_ft_micro_step");
+    MI_NO_LATENT(prior, "mi_ft_micro_step");
     MI_NO_POOLED(ab, "mi_ft_micro_step");
     MI_NO_POOLED(pb, "mi_ft_micro_step");
     return ft_micro_impl(agent, ab, prior, pb, lengths, angles, frac0, atom_types, reward, time_freqs, t, c0, c1, sigma_t, sigma_norm, 0, nullptr,
@@ -1652,6 +1654,8 @@ int mi_ft_micro_steps_stacked(mi_net* agent, mi_batch* ab, mi_net* prior, mi_bat
                               const float* sigma_norm_host, uint64_t seed, uint32_t noise_step, const float* rand_l, const float* rand_x,
                               const float* rand_t, float cost_lattice, float cost_coord, float cost_type, float kl_sigma, int b_global,
                               int accum_steps, float* grad_theta, float* stats, void* stream, void* aux_stream) {
+    MI_NO_LATENT(agent, "mi_ft_micro_steps_stacked");
+    MI_NO_LATENT(prior, "mi_ft_micro_steps_stacked");
     MI_NO_POOLED(ab, "mi_ft_micro_steps_stacked");
     MI_NO_POOLED(pb, "mi_ft_micro_steps_stacked");
     MI_CHECK(copies >= 1, MI_EINVAL, "copies must be positive");

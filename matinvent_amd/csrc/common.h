@@ -186,6 +186,7 @@ enum : uint32_t {
     DRAW_COND_L = 21, DRAW_COND_X = 22, DRAW_COND_T = 23,   // replacement conditioning (condition.hip); step field = the noise level
     DRAW_JUMP_L = 24, DRAW_JUMP_X = 25, DRAW_JUMP_T = 26,   // resampling jumps (resample.hip); step field = the level jumped TO
     DRAW_VISIT = 27,                                        // ... and the per-visit seed: counter (0, 0, 27, v) under the chain's seed
+    DRAW_COND_DROP = 28,                                    // condition dropout of the supervised micro-step (guidance.hip): one uniform per crystal
 };
 
 }  // namespace mi

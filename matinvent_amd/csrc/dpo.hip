@@ -216,6 +216,8 @@ int mi_dpo_micro_step(mi_net* agent, mi_batch* ab, mi_net* prior, mi_batch* pb, 
                       float sigma_norm, uint64_t seed, uint32_t noise_step, const float* rand_l, const float* rand_x, const float* rand_t,
                       float cost_lattice, float cost_coord, float cost_type, float beta, int p_global, int accum_steps, float* grad_theta,
                       float* stats, float* out_delta, float* out_margin, void* stream, void* aux_stream) {
+    MI_NO_LATENT(agent, "mi_dpo_micro_step");
+    MI_NO_LATENT(prior, "mi_dpo_micro_step");
     MI_NO_POOLED(ab, "mi_dpo_micro_step");
     MI_NO_POOLED(pb, "mi_dpo_micro_step");
     MI_CHECK(ab, MI_EINVAL, "null argument");

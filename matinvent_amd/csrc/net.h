@@ -17,6 +17,7 @@ struct mi_net {
     mi_net_config cfg;
     int H, L, F, TD, KP, NT;  // KP = 3*FP (sin,cos) pairs, FP = F rounded up to 8; NT = H/32
     int edge_in;              // 2H + 9 + 6F
+    int Z = 0, lat_P = 0, lat_F = 0;   // property part of the embedding input (guidance.hip, mi_net_set_latent): the last Z = 2 lat_F lat_P of the TD columns; 0: none
     std::vector<ParamInfo> params;
     int64_t nparams = 0;
     const float* theta = nullptr;  // caller-owned flat parameters (device)
@@ -246,6 +247,16 @@ struct mi_batch {
     float* pt_noised = nullptr;                       // in_lat | in_frac | in_types | tar_x | rnd_l | rnd_t
     // pooled handle (pool.hip, mi_batch_create_pooled): the pool every buffer above was lent by (NULL: the handle owns them),
     // the two prefix arrays next to node_off_h that the index-table kernels read, and the device copy of the edge prefix
+    // supervised training with a condition (guidance.hip, mi_pretrain_micro_step_cond; allocated on first use): the crystals' dropout draws
+    int* gd_drop = nullptr;                           // [B] 0 / 1
+    // classifier-free guidance (guidance.hip, mi_batch_set_guidance): the crystals' normalised properties, the frequency table and the
+    // handle the null evaluation runs on
+    bool gd_on = false;
+    int gd_P = 0, gd_F = 0, gd_cap = 0;
+    float gd_gamma = 0.f;
+    mi_batch* gd_partner = nullptr;
+    float *gd_yhat = nullptr, *gd_freqs = nullptr;    // [B][gd_P], [MI_GUIDANCE_MAX_FREQS]
+    int* gd_have = nullptr;                           // [B][gd_P]
     mi_pool* pool = nullptr;
     std::vector<int> edge_off_h, pair_off_h;
     int* edge_off = nullptr;   // [B + 1] first edge of each crystal (pooled handles only)
@@ -302,8 +313,27 @@ inline hipError_t batch_memset(const mi_batch* b, void* p, int v, size_t bytes) 
 // the one-line checks of the entries: a pooled handle where none is taken; a pooled handle used on another stream than its pool's
 #define MI_NO_POOLED(b, what) \
     MI_CHECK(!(b) || !(b)->pool, MI_EINVAL, what ": a pooled batch handle is not taken here (include/matinvent_hip_pool.h lists the entries that take one)")
+#define MI_NO_LATENT(net, what) \
+    MI_CHECK(!(net) || (net)->Z == 0, MI_EINVAL, what ": the network has a property-conditioned embedding (mi_net_set_latent), which this entry does not fill (include/matinvent_hip_guidance.h lists the entries that do)")
 #define MI_POOL_STREAM(b, stream, what) \
     MI_CHECK(!(b) || !(b)->pool || mi::pool_stream((b)->pool) == (hipStream_t)(stream), MI_EINVAL, what ": a pooled batch handle is used on its pool's stream only")
+// pretrain.hip: the supervised micro-step's sequence -- time gather, the EMBEDDING STAGE, noising, the network, loss, statistics, backward --
+// with the embedding stage passed in: it fills b->temb [B][TD] from b->times on `s`.  mi_pretrain_micro_step's stage is the time embedding
+// (pretrain.hip), mi_pretrain_micro_step_cond's the crystal embedding with condition dropout (guidance.hip).
+typedef int (*pretrain_embed_stage_fn)(mi_net* net, mi_batch* b, const float* time_freqs, void* ctx, hipStream_t s);
+int pretrain_micro_run(const char* what, mi_net* net, mi_batch* b, const float* lengths, const float* angles, const float* frac0, const int* atom_types,
+                       const float* time_freqs, const int* t_host, const int* t_dev, const float* sched_table_dev, int T, uint64_t seed,
+                       uint32_t noise_step, const float* rand_l, const float* rand_x, const float* rand_t, float cost_lattice, float cost_coord,
+                       float cost_type, int b_global, int n_global, int accum_steps, float* grad_theta, float* stats, float* out_parts,
+                       pretrain_embed_stage_fn stage, void* stage_ctx, void* stream);
+// guidance.hip: the crystal embedding [time | property] into `out` (yhat == NULL: the null row for every crystal; `b`: the handle whose time
+// map the time part reads, or NULL), mi_sampler_run's host-side check of a handle with guidance (MI_EINVAL with the message set), and
+// p_c + gamma (p_c - p_u) over up to three arrays in one launch, in place in the p_c arrays
+int crystal_embedding(const mi_net* net, const mi_batch* b, int B, const int* times, int t_all, const float* time_freqs, const float* prop_freqs,
+                      const float* yhat, const int* have, const int* drop, float* out, hipStream_t s);
+int guidance_check(const mi_net* net, const mi_batch* b, bool has_rec, const char* what);
+int guidance_combine(float* pl, const float* ul, size_t nl, float* px, const float* ux, size_t nx, float* pt, const float* ut, size_t nt, float gamma,
+                     hipStream_t s);
 int knn_alloc(mi_batch* b, int max_neighbors, int cap_per_node);
 // node_bwd.hip: the node-level BACKWARD chain between two edge stages of the backward pass as one launch per layer boundary
 extern int g_node_bwd, g_node_bwd_min_blocks;

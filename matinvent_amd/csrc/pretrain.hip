@@ -116,24 +116,20 @@ static int pretrain_buffers(mi_batch* b, bool forward_only) {
     return MI_OK;
 }
 
-}  // namespace mi
-
-using namespace mi;
-
-extern "C" {
-
-int mi_pretrain_micro_step(mi_net* net, mi_batch* b, const float* lengths, const float* angles, const float* frac0, const int* atom_types,
-                           const float* time_freqs, const int* t_host, const int* t_dev, const float* sched_table_dev, int T, uint64_t seed,
-                           uint32_t noise_step, const float* rand_l, const float* rand_x, const float* rand_t, float cost_lattice,
-                           float cost_coord, float cost_type, int b_global, int n_global, int accum_steps, float* grad_theta, float* stats,
-                           float* out_parts, void* stream) {
-    MI_POOL_STREAM(b, stream, "mi_pretrain_micro_step");
+// the body of the two entries (net.h): `what` names the entry in the messages, `stage` fills b->temb from b->times
+int pretrain_micro_run(const char* what, mi_net* net, mi_batch* b, const float* lengths, const float* angles, const float* frac0, const int* atom_types,
+                       const float* time_freqs, const int* t_host, const int* t_dev, const float* sched_table_dev, int T, uint64_t seed,
+                       uint32_t noise_step, const float* rand_l, const float* rand_x, const float* rand_t, float cost_lattice, float cost_coord,
+                       float cost_type, int b_global, int n_global, int accum_steps, float* grad_theta, float* stats, float* out_parts,
+                       pretrain_embed_stage_fn stage, void* stage_ctx, void* stream) {
+    MI_CHECK(!b || !b->pool || pool_stream(b->pool) == (hipStream_t)stream, MI_EINVAL, "%s: a pooled batch handle is used on its pool's stream only", what);
     MI_CHECK(net && b, MI_EINVAL, "null handle");
     MI_CHECK(b->H == net->H && b->L == net->L, MI_EINVAL, "batch was created for a different network");
-    MI_CHECK(!b->time_map, MI_EINVAL, "mi_pretrain_micro_step: the handle carries a time map (training runs on the trained grid)");
-    MI_CHECK(!b->cond_on && !b->lik_on, MI_EINVAL, "mi_pretrain_micro_step: the handle carries a condition or a likelihood mask");
-    MI_CHECK(b->tape.wcur == 0, MI_EINVAL, "mi_pretrain_micro_step: the handle has pending deferred weight gradients (mi_cspnet_wgrad_flush first)");
-    MI_CHECK(!grad_theta || b->tape.wslots == 0, MI_EINVAL, "mi_pretrain_micro_step: the handle has an open weight-gradient window (mi_batch_set_wgrad_window(.., 0) first)");
+    MI_CHECK(!b->time_map, MI_EINVAL, "%s: the handle carries a time map (training runs on the trained grid)", what);
+    MI_CHECK(!b->cond_on && !b->lik_on, MI_EINVAL, "%s: the handle carries a condition or a likelihood mask", what);
+    MI_CHECK(!b->gd_on, MI_EINVAL, "%s: the handle carries guidance (mi_batch_clear_guidance first)", what);
+    MI_CHECK(b->tape.wcur == 0, MI_EINVAL, "%s: the handle has pending deferred weight gradients (mi_cspnet_wgrad_flush first)", what);
+    MI_CHECK(!grad_theta || b->tape.wslots == 0, MI_EINVAL, "%s: the handle has an open weight-gradient window (mi_batch_set_wgrad_window(.., 0) first)", what);
     const int B = b->B, N = b->N;
     MI_CHECK(T >= 1 && accum_steps >= 1, MI_EINVAL, "T = %d, accum_steps = %d: both must be >= 1", T, accum_steps);
     MI_CHECK(b_global >= B && n_global >= N, MI_EINVAL, "b_global = %d / n_global = %d are below the handle's %d crystals / %d atoms", b_global, n_global, B, N);
@@ -141,7 +137,7 @@ int mi_pretrain_micro_step(mi_net* net, mi_batch* b, const float* lengths, const
     MI_CHECK(lengths && angles && frac0 && atom_types && time_freqs && t_host && t_dev && sched_table_dev, MI_EINVAL, "null argument");
     for (int c = 0; c < B; ++c) MI_CHECK(t_host[c] >= 1 && t_host[c] <= T, MI_EINVAL, "t[%d] = %d: a training time lies in 1..T = %d", c, t_host[c], T);
     MI_CHECK(!grad_theta || net->W2T != nullptr, MI_ESTATE, "mi_net_set_params must run before backward");
-    TraceRange range("mi_pretrain_micro_step");
+    TraceRange range(what);
     hipStream_t s = (hipStream_t)stream;
     const bool train = grad_theta != nullptr;
     if (train) MI_TRY(net_tape_prepare(net, b));
@@ -158,7 +154,7 @@ int mi_pretrain_micro_step(mi_net* net, mi_batch* b, const float* lengths, const
 
     hipLaunchKernelGGL(pretrain_time_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, t_dev, sched_table_dev, b->times, b->pt_sched, B, T);
     MI_KERNEL_CHECK();
-    MI_TRY(mi_time_embedding(b->times, time_freqs, B, net->TD, b->temb, stream));
+    MI_TRY(stage(net, b, time_freqs, stage_ctx, s));
     MI_TRY(mi_add_noise_per_crystal(b, lengths, angles, frac0, atom_types, b->pt_sched, seed, noise_step, rand_l, rand_x, rand_t, nz_lat, nz_frac,
                                     nz_types, tar_x, rnd_l, rnd_t, stream));
     if (train) {
@@ -181,6 +177,27 @@ int mi_pretrain_micro_step(mi_net* net, mi_batch* b, const float* lengths, const
     if (out_parts) MI_HIP(hipMemcpyAsync(out_parts, b->pt_parts, (size_t)B * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (!train) return MI_OK;
     return net_backward(net, b, tp.d_l, tp.d_x, tp.d_t, grad_theta, s);
+}
+
+static int pretrain_time_stage(mi_net* net, mi_batch* b, const float* time_freqs, void*, hipStream_t s) {
+    return mi_time_embedding(b->times, time_freqs, b->B, net->TD, b->temb, s);
+}
+
+}  // namespace mi
+
+using namespace mi;
+
+extern "C" {
+
+int mi_pretrain_micro_step(mi_net* net, mi_batch* b, const float* lengths, const float* angles, const float* frac0, const int* atom_types,
+                           const float* time_freqs, const int* t_host, const int* t_dev, const float* sched_table_dev, int T, uint64_t seed,
+                           uint32_t noise_step, const float* rand_l, const float* rand_x, const float* rand_t, float cost_lattice,
+                           float cost_coord, float cost_type, int b_global, int n_global, int accum_steps, float* grad_theta, float* stats,
+                           float* out_parts, void* stream) {
+    MI_NO_LATENT(net, "mi_pretrain_micro_step");
+    return pretrain_micro_run("mi_pretrain_micro_step", net, b, lengths, angles, frac0, atom_types, time_freqs, t_host, t_dev, sched_table_dev, T, seed,
+                              noise_step, rand_l, rand_x, rand_t, cost_lattice, cost_coord, cost_type, b_global, n_global, accum_steps, grad_theta, stats,
+                              out_parts, pretrain_time_stage, nullptr, stream);
 }
 
 }  // extern "C"

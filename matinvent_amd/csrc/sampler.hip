@@ -184,7 +184,14 @@ static int sampler_step(mi_net* net, mi_batch* b, int t, uint64_t seed, const fl
     const int N = b->N, B = b->B;
     const size_t n3 = (size_t)N * 3, nA = (size_t)N * MI_NUM_TYPES, b9 = (size_t)B * 9;
     TraceRange range("mi_sampler_step");
-    if (b->time_map) {   // a strided chain: t is the step index, the network sees the trained time map[t]
+    // classifier-free guidance (guidance.hip): with gamma != 0 every evaluation is two -- the conditional one on b, the null one on the
+    // partner handle (same state, same x_mid, its own caches) -- and the predictions become p_c + gamma (p_c - p_u) in b's arrays
+    mi_batch* const q = (b->gd_on && b->gd_gamma != 0.f) ? b->gd_partner : nullptr;
+    if (net->Z > 0) {   // a net with a property part: the crystal embedding -- the condition with guidance attached, the null row without
+        MI_TRY(crystal_embedding(net, b, B, nullptr, t, time_freqs, b->gd_on ? b->gd_freqs : nullptr, b->gd_on ? b->gd_yhat : nullptr,
+                                 b->gd_on ? b->gd_have : nullptr, nullptr, b->temb, s));
+        if (q) MI_TRY(crystal_embedding(net, b, B, nullptr, t, time_freqs, nullptr, nullptr, nullptr, nullptr, q->temb, s));
+    } else if (b->time_map) {   // a strided chain: t is the step index, the network sees the trained time map[t]
         MI_TRY(time_embedding_mapped(b, nullptr, t, time_freqs, B, net->TD, b->temb, s));
     } else {
         hipLaunchKernelGGL(time_embedding_kernel, dim3(cdiv((int64_t)B * net->TD, 256)), dim3(256), 0, s, (const int*)nullptr, time_freqs, b->temb, B,
@@ -193,6 +200,10 @@ static int sampler_step(mi_net* net, mi_batch* b, int t, uint64_t seed, const fl
     // corrector
     // (the Langevin corrector reads the coordinate score alone, diffusion.py:310-322: the type columns of the heads and the lattice head are not evaluated)
     MI_TRY(net_forward(net, b, b->temb, atom_types, frac, lattices, b->pred_l, b->pred_x, b->pred_t, s, false, false, true));
+    if (q) {
+        MI_TRY(net_forward(net, q, q->temb, atom_types, frac, lattices, q->pred_l, q->pred_x, q->pred_t, s, false, false, true));
+        MI_TRY(guidance_combine(nullptr, nullptr, 0, b->pred_x, q->pred_x, n3, nullptr, nullptr, 0, b->gd_gamma, s));
+    }
     hipLaunchKernelGGL(corrector_kernel, dim3(B), dim3(64), 0, s, frac, b->pred_x, noise ? noise->corr_x + t * n3 : nullptr,
                        b->coef, t, seed, b->node_offset, b->node_off, b->x_mid, (rec && rec->log_prob_x) ? b->lp_corr : nullptr,
                        (rec && rec->frac_coords_mid) ? rec->frac_coords_mid + t * n3 : nullptr, b->keep_coords);
@@ -200,6 +211,10 @@ static int sampler_step(mi_net* net, mi_batch* b, int t, uint64_t seed, const fl
     // predictor
     // the corrector moved the coordinates only (diffusion.py:320-322): layer-0 node features are those of the evaluation above
     MI_TRY(net_forward(net, b, b->temb, atom_types, b->x_mid, lattices, b->pred_l, b->pred_x, b->pred_t, s, false, true));
+    if (q) {   // (the partner's own corrector evaluation left its layer-0 features behind: the same reuse on its side)
+        MI_TRY(net_forward(net, q, q->temb, atom_types, b->x_mid, lattices, q->pred_l, q->pred_x, q->pred_t, s, false, true));
+        MI_TRY(guidance_combine(b->pred_l, q->pred_l, b9, b->pred_x, q->pred_x, n3, b->pred_t, q->pred_t, nA, b->gd_gamma, s));
+    }
     PredictorArgs a;
     a.x_mid = b->x_mid;
     a.pred_x = b->pred_x;
@@ -279,6 +294,7 @@ int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int 
     MI_TRY(time_map_check(b, T, "the batch handle"));
     MI_TRY(condition_check(b, T, "the batch handle"));
     MI_TRY(resample_check(b, T, t_start, t_stop, noise != nullptr, rec != nullptr, "the batch handle"));
+    MI_TRY(guidance_check(net, b, rec != nullptr, "the batch handle"));
     hipStream_t s = (hipStream_t)stream;
     const int N = b->N, B = b->B;
     if (N == 0 || B == 0) return MI_OK;

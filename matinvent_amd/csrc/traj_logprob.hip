@@ -676,6 +676,7 @@ int mi_traj_logprob(mi_net* net, mi_batch* bc, mi_batch* bp, const int* t_dev, c
                     const float* atom_types, const float* frac, const float* frac_mid, const float* lattices, const float* next_atom_types,
                     const float* next_frac, const float* next_lattices, float* log_prob, float* pred_corr_l, float* pred_corr_x,
                     float* pred_corr_t, int keep_tape, void* stream) {
+    MI_NO_LATENT(net, "mi_traj_logprob");
     MI_NO_POOLED(bc, "mi_traj_logprob");
     MI_NO_POOLED(bp, "mi_traj_logprob");
     MI_CHECK(net && bc && bp, MI_EINVAL, "null handle");
@@ -726,6 +727,7 @@ int mi_traj_pg_step(mi_net* net, mi_batch* bc, mi_batch* bp, const float* coef_d
                     const float* traj_atom_types, const float* traj_frac, const float* traj_frac_mid, const float* traj_lattices,
                     const float* traj_lp_old, const int* t_host, const int* t_dev, const float* adv_dev, float clip_range,
                     const float* w_host, float loss_scale, float* log_prob, float* grad_theta, float* stats, void* stream) {
+    MI_NO_LATENT(net, "mi_traj_pg_step");
     MI_NO_POOLED(bc, "mi_traj_pg_step");
     MI_NO_POOLED(bp, "mi_traj_pg_step");
     MI_TRY(pg_check(net, bc, bp, coef_dev, T, time_freqs, traj_atom_types, traj_frac, traj_frac_mid, traj_lattices, traj_lp_old, t_host, t_dev,
@@ -739,6 +741,8 @@ int mi_traj_pg_kl_step(mi_net* net, mi_batch* bc, mi_batch* bp, mi_net* prior, m
                        const float* traj_lattices, const float* traj_lp_old, const int* t_host, const int* t_dev, const float* adv_dev,
                        float clip_range, const float* w_host, float loss_scale, float kl_coef, float* log_prob, float* kl_out,
                        float* grad_theta, float* stats, void* stream, void* aux_stream) {
+    MI_NO_LATENT(net, "mi_traj_pg_kl_step");
+    MI_NO_LATENT(prior, "mi_traj_pg_kl_step");
     MI_NO_POOLED(bc, "mi_traj_pg_kl_step");
     MI_NO_POOLED(bp, "mi_traj_pg_kl_step");
     MI_NO_POOLED(pb, "mi_traj_pg_kl_step");

@@ -20,6 +20,7 @@ class CrystalData:
     angles: torch.Tensor                 # [1, 3] degrees
     num_atoms: int = 0
     reward: Optional[torch.Tensor] = None  # [1], attached by CrystalDataset (finetune.py:13)
+    properties: Optional[dict] = None      # name -> scalar value (None / NaN: missing), what a property-conditioned prior trains on (guidance.py)
 
     def __post_init__(self):
         self.num_atoms = int(self.num_atoms) if self.num_atoms else int(self.frac_coords.shape[0])

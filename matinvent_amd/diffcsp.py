@@ -94,7 +94,68 @@ class DiffCSPModule(nn.Module):
         self.cost_lattice, self.cost_coord, self.cost_type = cost_lattice, cost_coord, cost_type
         self.keep_lattice = cost_lattice < 1e-5   # diffusion.py:78-79: CSP mode, that part of the structure is given
         self.keep_coords = cost_coord < 1e-5
+        self._init_condition(kwargs.get("condition"), latent_dim)
         self.to(dev)
+
+    # ---- property-conditioned prior (guidance.py) ---------------------------------------
+    condition = None    # guidance.parse_condition's dict of a module with a property part (latent_dim = 2 F P); None: the unconditional prior
+    normalizer = None   # ... and its guidance.PropertyNormalizer (mean 0, std 1 until pretrain.fit has fitted it)
+
+    def _init_condition(self, spec, latent_dim):
+        """latent_dim > 0 takes hparams `condition` = {properties, num_freqs[, p_uncond, mean, std]} with 2 F P = latent_dim and records the
+        layout on the network (mi_net_set_latent: every fused entry then fills or refuses the property columns); latent_dim = 0 takes none."""
+        from . import guidance
+        cond = guidance.parse_condition(spec)
+        if cond is None and not latent_dim:
+            return
+        if cond is None or not latent_dim or guidance.latent_dim(len(cond["properties"]), cond["num_freqs"]) != int(latent_dim):
+            raise ValueError(f"DiffCSPModule: latent_dim = {latent_dim} and condition = {spec!r} do not go together: a property-conditioned prior has "
+                             "condition = {properties: [P names], num_freqs: F} and latent_dim = 2 F P, an unconditional one neither")
+        _lib.check(_lib.load().mi_net_set_latent(self.decoder._h, len(cond["properties"]), cond["num_freqs"]), "mi_net_set_latent")
+        self.condition = cond
+        self.normalizer = guidance.PropertyNormalizer(cond["properties"], cond.get("mean"), cond.get("std"))
+        self.register_buffer("prop_freqs", guidance.property_freqs(cond["num_freqs"]), persistent=False)
+
+    def set_normalizer(self, normalizer):
+        """Adopt a fitted PropertyNormalizer (pretrain.fit): into the module and into hparams["condition"], so that a saved model reloads with it."""
+        if self.condition is None or list(normalizer.names) != list(self.condition["properties"]):
+            raise ValueError("set_normalizer: the normaliser's properties are not the module's")
+        self.normalizer = normalizer
+        self.condition = dict(self.condition, **{k: v for k, v in normalizer.to_dict().items() if k != "properties"})
+        self.hparams["condition"] = dict(self.condition)
+
+    def _yhat(self, y, B, where):
+        """(yhat, have) device tensors [B][P] of raw property values `y` ([B][P] or [B] for P = 1; NaN: missing), or (None, None)."""
+        if y is None:
+            return None, None
+        import numpy as np
+        a = np.asarray(y.cpu() if torch.is_tensor(y) else y, dtype=np.float64)
+        nm = (self.base if self.base is not None else self).normalizer   # (a view made before fit fitted it reads the module's)
+        if a.size != B * nm.P:
+            raise ValueError(f"{where}: y holds {a.size} values for {B} crystals x {nm.P} properties")
+        yhat, have = nm.normalise(a)
+        return torch.from_numpy(yhat).to(self.device), torch.from_numpy(have).to(self.device)
+
+    def crystal_embedding(self, times, y=None, drop=None):
+        """[B][time_dim + Z]: the embedding rows the network of a property-conditioned prior reads (mi_crystal_embedding) at the per-crystal
+        `times` -- the time embedding, then per property sin / cos of w_k clamp(y^); y: raw property values [B][P] (NaN: missing), None: the
+        null row for every crystal; drop: [B] bool, the crystals whose condition is dropped.  On a respaced view `times` are step indices."""
+        from . import guidance
+        guidance.module_condition(self, "crystal_embedding")
+        dev = self.device
+        times = torch.as_tensor(times).to(dev, torch.int32).contiguous().reshape(-1)
+        B = times.shape[0]
+        yhat, have = self._yhat(y, B, "crystal_embedding")
+        dr = None if drop is None else torch.as_tensor(drop).to(dev).reshape(-1).to(torch.int32).contiguous()
+        if dr is not None and dr.shape[0] != B:
+            raise ValueError(f"crystal_embedding: drop holds {dr.shape[0]} entries for {B} crystals")
+        out = torch.empty(B, self.decoder.latent_dim, device=dev)
+        cb = None
+        if self.time_map is not None:   # (a view: the map rides on a handle, and the entry reads nothing else of it -- the view's one-atom handle serves every B)
+            cb = self._batch_for(torch.ones(1, dtype=torch.long))
+        _lib.check(_lib.load().mi_crystal_embedding(self.decoder._h, None if cb is None else cb._h, B, _ptr(times), 0, _ptr(self.time_embedding.freqs),
+                                                    _ptr(self.prop_freqs), _ptr(yhat), _ptr(have), _ptr(dr), _ptr(out), _stream()), "mi_crystal_embedding")
+        return out
 
     @property
     def device(self):
@@ -140,6 +201,9 @@ class DiffCSPModule(nn.Module):
             view.time_dim, view.time_embedding = self.time_dim, self.time_embedding
             view.cost_lattice, view.cost_coord, view.cost_type = self.cost_lattice, self.cost_coord, self.cost_type
             view.keep_lattice, view.keep_coords = self.keep_lattice, self.keep_coords
+            if self.condition is not None:
+                view.condition, view.normalizer = self.condition, self.normalizer
+                view.register_buffer("prop_freqs", self.prop_freqs, persistent=False)
             view.time_map = torch.tensor(tau, dtype=torch.int32)
             object.__setattr__(view, "base", self)   # (not a submodule of its own view)
             view.train(self.training)
@@ -185,12 +249,14 @@ class DiffCSPModule(nn.Module):
         return cb
 
     # ---- fine-tune surface (pipeline/mat_invent.py:152-161) ------------------------------------
-    def add_noise(self, batch, time=None, noise=None, seed=None, times=None):
+    def add_noise(self, batch, time=None, noise=None, seed=None, times=None, y=None, drop=None):
         """DiffCSPModule.add_noise (diffusion.py:81-119) for an explicit timestep index
         (`time` in 0..T-1 -> diffusion time T - time, :86-87).  Returns the reference's triple
         (noised_input, noises, batch.batch).  Fresh Gaussian noise per call from the Philox
         stream (seed, running call counter) unless `noise` = (rand_l, rand_x, rand_t).
-        `times` (with time=None): the per-crystal diffusion times, [B] ints in 1..T, in place of the numpy draw."""
+        `times` (with time=None): the per-crystal diffusion times, [B] ints in 1..T, in place of the numpy draw.
+        On a property-conditioned module the first element of noised_input is the crystal embedding (crystal_embedding): under the raw
+        property values `y` with the crystals of `drop` left without, or -- y = None -- the null row."""
         lib = _lib.load()
         dev = self.device
         T = self.beta_scheduler.timesteps
@@ -216,7 +282,12 @@ class DiffCSPModule(nn.Module):
             ac = self.beta_scheduler.alphas_cumprod[t]
             c0, c1 = float(torch.sqrt(ac)), float(torch.sqrt(1.0 - ac))
             sig, sn = float(self.sigma_scheduler.sigmas[t]), float(self.sigma_scheduler.sigmas_norm[t])
-        time_emb = self.time_embedding(times)
+        if self.condition is not None:
+            time_emb = self.crystal_embedding(times, y, drop)
+        elif y is not None or drop is not None:
+            raise ValueError("add_noise: y / drop need a property-conditioned module (latent_dim > 0)")
+        else:
+            time_emb = self.time_embedding(times)
         f = lambda x: x.to(dev, torch.float32).contiguous()
         lengths, angles, frac0 = f(batch.lengths), f(batch.angles), f(batch.frac_coords)
         at = batch.atom_types.to(dev, torch.int32).contiguous()
@@ -270,14 +341,14 @@ class DiffCSPModule(nn.Module):
         k2 = _scatter_mean(torch.pow(pt - ptp, 2).mean(dim=1), node2graph, B)
         return k0 + k1 + k2
 
-    def training_step(self, batch, times=None, noise=None):
+    def training_step(self, batch, times=None, noise=None, y=None, drop=None):
         """DiffCSPModule.training_step (diffusion.py:457-486) on the module surface: add_noise with one time per crystal (`times`: [B]
         ints in 1..T in place of the numpy draw), the network, three F.mse_loss over all elements of the batch, the cost-weighted sum.
         Returns (loss, dict(loss, loss_lattice, loss_coord, loss_type)); differentiable through the decoder's autograd function.  The
         unfused yardstick of pretrain.train_step, as ft_step(fused=False) is of the fused fine-tune step."""
         if self.base is not None:
             raise ValueError("training_step: a respaced view is for sampling; train its .base, the module of the trained grid")
-        input_all = self.add_noise(batch, None, noise=noise, times=times)
+        input_all = self.add_noise(batch, None, noise=noise, times=times, y=y, drop=drop)   # (y, drop: add_noise's, a property-conditioned module)
         _, (rand_l, tar_x, rand_t), _ = input_all
         pred_l, pred_x, pred_t = self.predict(input_all)
         mse = nn.functional.mse_loss
@@ -319,6 +390,8 @@ class DiffCSPModule(nn.Module):
         predictor terms of c's known elements leave the three log-probabilities and their gradients -- the trajectory likelihood of the
         conditioned chain up to a constant of theta.  The handle pair carries c's masks for the call alone (one device synchronisation)."""
         from .conditioning import check_likelihood
+        from .guidance import refuse_latent
+        refuse_latent(self, "forward_logprb")
         masked = check_likelihood("forward_logprb", likelihood, condition)
         if condition is not None and not masked:
             raise ValueError("forward_logprb: a condition is not supported -- the recorded log-probabilities of a conditioned chain are those "
@@ -392,7 +465,8 @@ class DiffCSPModule(nn.Module):
 
     @torch.no_grad()
     def sample(self, batch, diff_ratio=1.0, step_lr=1e-5, seed=0, noise=None, init=None, record=False, t_start=None,
-               t_stop=0, node_offset=0, graph_offset=0, streams=None, rec_sink=None, condition=None, likelihood=None, resample=None):
+               t_stop=0, node_offset=0, graph_offset=0, streams=None, rec_sink=None, condition=None, likelihood=None, resample=None,
+               guidance=None):
         """DiffCSPModule.sample (diffusion.py:273-399).
 
         `rec_sink` (a list; with record=True): receives one (first crystal, first atom, buffers) per chain, in crystal order -- the
@@ -425,9 +499,25 @@ class DiffCSPModule(nn.Module):
         (resampling.visit_seed); (1, j) is the plain conditioned chain, bit for bit.  The chain's handles carry (r, j) and the jump table
         for this call, like the condition.  ValueError before any device work: no condition, record=True, `noise`, `likelihood`,
         t_stop != 0, r < 1, j < 1, or no jump-off level (1 + j > t_start).
+
+        `guidance` = guidance.Guidance(values, factor) (a property-conditioned module): the chain runs under the crystals' property
+        values, and with factor != 0 every network evaluation is two -- the conditional one and the null one, on a cached partner handle
+        per chain -- and the step takes p_c + factor (p_c - p_u).  Attached to the chain's handles for this call and cleared afterwards,
+        like a condition; each stream group gets its crystals' slice.  Without it a property-conditioned module samples under the null
+        row.  ValueError before any device work: a module without a property part, an unknown property, record=True, `condition`,
+        `likelihood`, `resample`, CSP mode.
         """
         from .conditioning import check_likelihood
         from .resampling import check_chain
+        gd = None
+        if guidance is not None:
+            from .guidance import module_condition
+            module_condition(self, "sample(guidance=)")
+            for name, v in (("record=True", record), ("a condition", condition is not None), ("likelihood", likelihood is not None),
+                            ("resample", resample is not None), ("CSP mode", self.keep_lattice or self.keep_coords)):
+                if v:
+                    raise ValueError(f"sample: guidance together with {name} is not supported")
+            gd = (guidance,) + guidance.arrays((self.base if self.base is not None else self).normalizer, len(batch.num_atoms))
         rj = None if resample is None else check_chain("sample", resample, self.beta_scheduler.timesteps, t_start, t_stop, condition, record,
                                                        noise, likelihood)
         lik = check_likelihood("sample", likelihood, condition)
@@ -437,7 +527,7 @@ class DiffCSPModule(nn.Module):
             self.check_graph()   # (the verdict of the previous call's chains: by now they have long finished)
         if isinstance(batch, CrystalBatch):
             return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink,
-                                    condition=condition, likelihood=lik, resample=rj)
+                                    condition=condition, likelihood=lik, resample=rj, guidance=gd)
         if (self.keep_lattice or self.keep_coords) and init is None and condition is None:
             # CSP mode (diffusion.py:283-287): the known part of the structure replaces the drawn initial state and is never moved
             cb0 = self.crystal_batch(batch, node_offset, graph_offset)
@@ -460,7 +550,7 @@ class DiffCSPModule(nn.Module):
         streams = max(1, min(int(streams), len(na)))
         if streams == 1:
             return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink,
-                                    condition=condition, likelihood=lik, resample=rj)
+                                    condition=condition, likelihood=lik, resample=rj, guidance=gd)
         key = ("split", streams, tuple(na))
         parts = getattr(batch, "_mi_split", {}).get(key)
         if parts is None:  # contiguous crystal groups, cached on the batch object like its CrystalBatch
@@ -508,7 +598,10 @@ class DiffCSPModule(nn.Module):
         # the chains), and cleared when all of them are: each group gets its crystals' slice
         conds = [] if condition is None else [(self.crystal_batch(parts[k], node_offset + n0[k], graph_offset + g0[k]), condition.slice(g0[k], g0[k + 1]))
                                               for k in range(streams)]
-        with self._conditioned(conds, likelihood=lik, resample=rj):
+        # ... and so is guidance: every group's handle gets its crystals' rows and a partner handle of its own
+        guided = [] if gd is None else [(self.crystal_batch(parts[k], node_offset + n0[k], graph_offset + g0[k]), (node_offset + n0[k], graph_offset + g0[k]),
+                                         gd[1][g0[k]:g0[k + 1]], gd[2][g0[k]:g0[k + 1]]) for k in range(streams)]
+        with self._conditioned(conds, likelihood=lik, resample=rj), self._guided(guided, gd):
             out = workers.run(run, streams)
         if rec_sink is not None:
             for k, sk in enumerate(sinks):
@@ -583,8 +676,33 @@ class DiffCSPModule(nn.Module):
                 if resample is not None:
                     resampling.clear(cb)
 
+    @contextlib.contextmanager
+    def _guided(self, handles, gd):
+        """Attach guidance to each (batch handle, (node offset, graph offset), yhat rows, have rows) of `handles` for the duration of the block
+        and clear the handles afterwards, whatever happens inside (_conditioned's contract: one drain of the device first).  gd =
+        (Guidance, yhat, have) of the call.  With factor != 0 each handle gets a partner handle of its atom counts and offsets for the null
+        evaluation, created on first use and kept on the handle."""
+        if not handles:
+            yield
+            return
+        import numpy as np
+        from . import guidance as G
+        torch.cuda.synchronize(self.device)
+        try:
+            for cb, off, yhat, have in handles:
+                partner = None
+                if gd[0].factor != 0.0:
+                    partner = cb.__dict__.get("_mi_partner")
+                    if partner is None:
+                        partner = cb._mi_partner = self.make_batch(cb.num_atoms_list, int(off[0]), int(off[1]))
+                G.attach(cb, partner, np.ascontiguousarray(yhat), np.ascontiguousarray(have), self.condition["num_freqs"], gd[0].factor)
+            yield
+        finally:
+            for cb, *_ in handles:
+                G.clear(cb)
+
     def _sample_one(self, batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, inplace=None, drawn=False,
-                    rec_sink=None, condition=None, likelihood=False, resample=None):
+                    rec_sink=None, condition=None, likelihood=False, resample=None, guidance=None):
         """One chain over one CrystalBatch on the current stream.
 
         Returns (traj[t_stop], traj) like the reference.  `traj` holds every step only when
@@ -627,7 +745,8 @@ class DiffCSPModule(nn.Module):
                          frac_coords_mid=z(T + 1, N, 3), log_prob_l=z(T + 1, B), log_prob_t=z(T + 1, B), log_prob_x=z(T + 1, B))
             rec = _lib.SamplerRecord(*(rec_t[k].data_ptr() for k in ("atom_types", "frac_coords", "lattices", "frac_coords_mid",
                                                                      "log_prob_l", "log_prob_t", "log_prob_x")))
-        with self._conditioned([] if condition is None else [(cb, condition)], likelihood=likelihood, resample=resample):
+        with self._conditioned([] if condition is None else [(cb, condition)], likelihood=likelihood, resample=resample), \
+                self._guided([] if guidance is None else [(cb, (node_offset, graph_offset), guidance[1], guidance[2])], guidance):
             _lib.check(lib.mi_sampler_run(self.decoder._h, cb._h, coef.numpy().ctypes.data_as(C.POINTER(C.c_float)), T, t_start, t_stop,
                                           _ptr(self.time_embedding.freqs), seed, C.byref(nz) if nz is not None else None,
                                           C.byref(rec) if rec is not None else None, _ptr(a), _ptr(x), _ptr(l), _stream()),

@@ -205,6 +205,8 @@ def ft_step(agent, prior, data_list, rewards, cfg, device=None, noise_fn=None, l
     global norm / leaves out a step whose gradient holds inf or NaN, on the device inside FusedAdam.step (optim.py); the epoch
     dicts then also carry grad_norm, grad_norm_max, clipped_steps, skipped_steps.  The norm is taken after the all-reduce of the gradient
     (and after the groups' gradients are summed), so every rank computes the same coefficient and takes the same decision."""
+    from .guidance import refuse_latent
+    refuse_latent((agent, prior), "ft_step")
     v = [cfg_get(cfg, k) for k in _Config._fields[:5]]
     if None in v:   # (before any device work)
         raise KeyError(f"ft_step: the config has no {_Config._fields[v.index(None)]}")

@@ -73,6 +73,8 @@ class MatInvent(ReinL):
         """mat_invent.py:62-72: agent (trainable) + frozen prior, two separate loads."""
         self.agent = self.model_suite.load_model()
         self.prior = self.model_suite.load_model()
+        from .guidance import refuse_latent
+        refuse_latent((self.agent, self.prior), type(self).__name__)   # (before any device work of the run: RL on a conditional prior is not built)
         for p in self.agent.parameters():
             p.requires_grad = True
         for p in self.prior.parameters():
@@ -393,7 +395,8 @@ class MatInventDPO(MatInvent):
 class Pretrain:
     """Supervised denoising training of a DiffCSP prior on a crystal dataset (pretrain.fit): the pipeline that produces the
     model the RL pipelines start from.  train_path / val_path: extxyz files (structure.read_extxyz); train_cfg: pretrain.fit's config
-    (lr, epochs, batch_size, accum_steps, max_grad_norm, skip_nonfinite_steps, lr_plateau, handle_pool, ema), merged over the suite's finetune_cfg (the
+    (lr, epochs, batch_size, accum_steps, max_grad_norm, skip_nonfinite_steps, lr_plateau, handle_pool, ema, condition -- the property
+    values are each frame's scalar `key=value` entries of its comment line), merged over the suite's finetune_cfg (the
     pipeline wins).  DiffCSPSuite.save_model writes <save_dir>/models/epoch_NNNN every save_freq epochs and <save_dir>/models/final at the
     end: directories that load_model(model_path=...) of this build loads.  `run_rl` is the entry the drop-in's main calls; `reward`,
     `logger` rows and sampling play no part (the logger, when given, receives every epoch's dict).  The MatterGen suite is refused.
@@ -430,8 +433,14 @@ class Pretrain:
         out = []
         for s in read_extxyz(path):
             frac = torch.as_tensor(np.asarray(s.frac_coords), dtype=torch.float64) % 1.0
+            props = {}
+            for k, v in s.info.items():   # the frame's scalar `key=value` entries: what train_cfg.condition.properties may name
+                try:
+                    props[k] = float(v)
+                except ValueError:
+                    pass
             out.append(CrystalData(frac.float(), torch.tensor(s.species, dtype=torch.long), torch.tensor([s.lengths], dtype=torch.float32),
-                                   torch.tensor([s.angles], dtype=torch.float32)))
+                                   torch.tensor([s.angles], dtype=torch.float32), properties=props or None))
         return out
 
     def load_model(self):

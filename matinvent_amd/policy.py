@@ -73,6 +73,8 @@ def pg_step(agent, rollout, rewards, cfg, seed=None, log=logging.info, prior=Non
     handles -- the agent pair and, with kl_coef > 0, the prior's -- carry its masks as their likelihood mask from before the first
     micro-step until the return: log-probabilities, KL terms and gradients leave out the predictor terms of the known elements."""
     opt = clip_options(cfg)
+    from .guidance import refuse_latent
+    refuse_latent((agent, prior), "pg_step")
     lr, epochs = float(cfg_get(cfg, "lr")), int(cfg_get(cfg, "epochs"))
     timesteps, accum_steps = int(cfg_get(cfg, "timesteps")), int(cfg_get(cfg, "accum_steps"))
     clip_range = float(cfg_get(cfg, "clip_range", DEFAULTS["clip_range"]))

@@ -64,6 +64,8 @@ def dpo_step(agent, prior, data_list, pairs, cfg, device=None, noise_fn=None, lo
     d_l - d_w), and the optimiser's statistics when it clips or guards.  `noise_fn(epoch, t)` -> (rand_l, rand_x, rand_t) of the COMPACTED
     set injects noise (parity tests); default Philox, agent._noise_calls advancing once per timestep as in ft_step.
     Scope: one group, unstacked, one GPU, the DiffCSP module."""
+    from .guidance import refuse_latent
+    refuse_latent((agent, prior), "dpo_step")
     fields = _Config._fields[:4] + ("dpo_beta",)
     v = [cfg_get(cfg, k) for k in fields]
     if None in v:   # (before any device work)

@@ -76,7 +76,7 @@ def _counts(batch):
 
 
 def train_step(model, batch, times, noise=None, grad=None, stats=None, b_global=None, n_global=None, accum_steps=1, seed=0, call_id=None,
-               offsets=(0, 0), forward_only=False, out_parts=None, pool=None):
+               offsets=(0, 0), forward_only=False, out_parts=None, pool=None, y=None, p_uncond=0.0):
     """One fused micro-step on the current stream: `batch` (num_atoms, lengths, angles, frac_coords, atom_types; a CrystalBatchData) at
     the per-crystal `times` ([B] ints in 1..T).  Accumulates (+=) into `grad` (default: theta.grad, allocated when absent) and `stats`
     (4 device floats in STATS order; returned).  noise = (rand_l, rand_x, rand_t) injects the draws; otherwise Philox draws 7-9 at
@@ -84,8 +84,16 @@ def train_step(model, batch, times, noise=None, grad=None, stats=None, b_global=
     in the mini-batch.  b_global / n_global: the crystal / atom counts the loss is normalised by (default: the batch's own).
     forward_only=True: no tape, no backward, `grad` untouched (the validation loss).  The batch handle lives for this call only.
     pool: a pool.HandlePool of the current stream -- the handle's memory comes from it and goes back to it, and this call waits for
-    nothing; None: the handle allocates and frees its own memory, which waits for the micro-step."""
+    nothing; None: the handle allocates and frees its own memory, which waits for the micro-step.
+    A property-conditioned module (DESIGN 41) runs mi_pretrain_micro_step_cond: y = the crystals' raw property values [B][P] (NaN: missing;
+    None: every crystal under the null condition), p_uncond = the probability with which the device drops a crystal's condition (draw id 28
+    at `call_id`, indexed through offsets[1]: guidance.drop_mask is the same draw on the host)."""
     _refuse(model, "train_step")
+    cond = getattr(model, "condition", None)
+    if cond is None and (y is not None or float(p_uncond) != 0.0):
+        raise ValueError("train_step: y / p_uncond need a property-conditioned module (latent_dim > 0)")
+    if not 0.0 <= float(p_uncond) <= 1.0:
+        raise ValueError(f"train_step: p_uncond = {p_uncond} lies outside [0, 1]")
     lib = _lib.load()
     dev = model.device
     na = _counts(batch)
@@ -114,15 +122,26 @@ def train_step(model, batch, times, noise=None, grad=None, stats=None, b_global=
     # (with a pool nothing below waits for the device: the times go up from pinned memory, behind the stream's work)
     t_dev = torch.from_numpy(th).to(dev) if pool is None else torch.from_numpy(th).pin_memory().to(dev, non_blocking=True)
     nz = (None, None, None) if noise is None else tuple(f(x) for x in noise)
+    yhat = have = None
+    if cond is not None and y is not None:
+        ya = np.asarray(y.cpu() if torch.is_tensor(y) else y, dtype=np.float64)
+        if ya.size != B * model.normalizer.P:
+            raise ValueError(f"train_step: y holds {ya.size} values for {B} crystals x {model.normalizer.P} properties")
+        up = (lambda a: torch.from_numpy(a).to(dev)) if pool is None else (lambda a: torch.from_numpy(a).pin_memory().to(dev, non_blocking=True))
+        yhat, have = (up(a) for a in model.normalizer.normalise(ya))
     model.decoder.sync()
     cb = model.make_batch(na, int(offsets[0]), int(offsets[1]), pool=pool)   # (its own handle: never the module's cache)
     try:
-        _lib.check(lib.mi_pretrain_micro_step(
-            model.decoder._h, cb._h, _ptr(lengths), _ptr(angles), _ptr(frac0), _ptr(at), _ptr(model.time_embedding.freqs),
-            th.ctypes.data_as(C.POINTER(C.c_int)), _ptr(t_dev), _ptr(schedule_table(model)), T, int(seed), int(call_id) & 0xFFFFFFFF,
-            _ptr(nz[0]), _ptr(nz[1]), _ptr(nz[2]), model.cost_lattice, model.cost_coord, model.cost_type,
-            B if b_global is None else int(b_global), N if n_global is None else int(n_global), int(accum_steps),
-            None if forward_only else _ptr(grad), _ptr(stats), _ptr(out_parts), _stream()), "mi_pretrain_micro_step")
+        args = (model.decoder._h, cb._h, _ptr(lengths), _ptr(angles), _ptr(frac0), _ptr(at), _ptr(model.time_embedding.freqs),
+                th.ctypes.data_as(C.POINTER(C.c_int)), _ptr(t_dev), _ptr(schedule_table(model)), T, int(seed), int(call_id) & 0xFFFFFFFF,
+                _ptr(nz[0]), _ptr(nz[1]), _ptr(nz[2]), model.cost_lattice, model.cost_coord, model.cost_type,
+                B if b_global is None else int(b_global), N if n_global is None else int(n_global), int(accum_steps),
+                None if forward_only else _ptr(grad), _ptr(stats), _ptr(out_parts))
+        if cond is None:
+            _lib.check(lib.mi_pretrain_micro_step(*args, _stream()), "mi_pretrain_micro_step")
+        else:
+            _lib.check(lib.mi_pretrain_micro_step_cond(*args, _ptr(model.prop_freqs), _ptr(yhat), _ptr(have), float(p_uncond), _stream()),
+                       "mi_pretrain_micro_step_cond")
     finally:
         # the handle's memory is freed here, which makes the host wait for the micro-step (hipFree waits for the device in any case; the
         # explicit wait on this stream keeps that from resting on the runtime's behaviour)
@@ -152,7 +171,7 @@ def _slice_noise(noise, rows, na_all):
     return noise[0][lo:hi], noise[1][n0:n1], noise[2][n0:n1]
 
 
-def _eval_enqueue(model, data_list, batch_size, seed, times, acc, pool=None):
+def _eval_enqueue(model, data_list, batch_size, seed, times, acc, pool=None, condition=True):
     """`evaluate` without the read-back: every mini-batch of the set in order, forward-only, normalised by the counts of the WHOLE set (so
     the four sums are the set's losses whatever batch_size is), into the 4 device floats `acc`."""
     n = len(data_list)
@@ -165,6 +184,7 @@ def _eval_enqueue(model, data_list, batch_size, seed, times, acc, pool=None):
             raise ValueError(f"evaluate: times = {times} lies outside 1..{T}")
         tt = np.full(n, int(times), dtype=np.int32)
     rank, world = rank_world()
+    use_y = getattr(model, "condition", None) is not None and bool(condition)
     was_training = model.training
     model.eval()
     try:
@@ -174,24 +194,28 @@ def _eval_enqueue(model, data_list, batch_size, seed, times, acc, pool=None):
             if not own:
                 continue
             # (the noise is indexed by the crystal's and the atom's position in the SET: the draws do not depend on batch_size either)
-            train_step(model, _as_batch([data_list[i] for i in own], model.device), tt[own], stats=acc, b_global=n, n_global=sum(na), seed=seed,
-                       call_id=EVAL_CALL, offsets=(sum(na[:own[0]]), own[0]), forward_only=True, pool=pool)
+            items = [data_list[i] for i in own]
+            y = model.normalizer.raw(items) if use_y else None   # (a property-conditioned module: the crystals' values, never dropped; or the null row)
+            train_step(model, _as_batch(items, model.device), tt[own], stats=acc, b_global=n, n_global=sum(na), seed=seed,
+                       call_id=EVAL_CALL, offsets=(sum(na[:own[0]]), own[0]), forward_only=True, pool=pool, y=y)
     finally:
         model.train(was_training)
     return acc
 
 
-def evaluate(model, data_list, batch_size, seed=0, times=None, pool=None):
+def evaluate(model, data_list, batch_size, seed=0, times=None, pool=None, condition=True):
     """The four losses of `data_list` under the current weights, forward-only: dict(loss, loss_lattice, loss_coord, loss_type), each the
     mean over ALL elements of the set (mini-batches weighted by their element counts: the result does not depend on batch_size beyond
     fp32 summation order).  times=None: one time per crystal from draw_times(len, T, 0, 0, seed); times=k: every crystal at time k
-    (the per-time loss curve).  Noise: Philox at call id 0 under `seed`.  One host read.  pool: train_step's."""
+    (the per-time loss curve).  Noise: Philox at call id 0 under `seed`.  One host read.  pool: train_step's.
+    condition (a property-conditioned module): True -- every crystal under its own property values, none dropped; False -- every crystal
+    under the null condition (the two losses' difference is what the model has learnt to read from the property)."""
     _refuse(model, "evaluate")
     if int(batch_size) < 1:
         raise ValueError(f"evaluate: batch_size = {batch_size}: must be >= 1")
     if len(data_list) == 0:
         raise ValueError("evaluate: an empty set")
-    acc = _eval_enqueue(model, data_list, batch_size, seed, times, torch.zeros(4, device=model.device), pool=pool)
+    acc = _eval_enqueue(model, data_list, batch_size, seed, times, torch.zeros(4, device=model.device), pool=pool, condition=condition)
     allreduce_flat_(acc)
     return dict(zip(STATS, acc.tolist()))
 
@@ -215,11 +239,13 @@ META_KEYS = ("seed", "batch_size", "accum_steps", "shuffle", "n_train", "n_val",
              "ema_decay", "ema_warmup", "ema_validate", "lr_plateau")
 
 
-def run_meta(model, optimizer, plateau, seed, batch_size, accum_steps, shuffle, n_train, n_val, ema):
+def run_meta(model, optimizer, plateau, seed, batch_size, accum_steps, shuffle, n_train, n_val, ema, condition=None):
     """What decides a run's batch plan, noise and arithmetic besides its weights (META_KEYS): a checkpoint is continued only under the
-    same values (check_meta)."""
+    same values (check_meta); plus `condition` for a property-conditioned run."""
     o = optimizer.options()
-    return dict(seed=int(seed), batch_size=int(batch_size), accum_steps=int(accum_steps), shuffle=bool(shuffle), n_train=int(n_train),
+    extra = {} if condition is None else dict(condition=dict(properties=list(condition["properties"]), num_freqs=int(condition["num_freqs"]),
+                                                             p_uncond=float(condition["p_uncond"])))
+    return dict(extra, seed=int(seed), batch_size=int(batch_size), accum_steps=int(accum_steps), shuffle=bool(shuffle), n_train=int(n_train),
                 n_val=int(n_val), world_size=int(rank_world()[1]), T=int(model.beta_scheduler.timesteps), numel=int(model.decoder.theta.numel()),
                 max_grad_norm=o["max_grad_norm"], skip_nonfinite=o["skip_nonfinite"], ema_decay=o["ema_decay"], ema_warmup=o["ema_warmup"],
                 ema_validate=None if ema is None else bool(ema["validate"]), lr_plateau=plateau is not None)
@@ -233,6 +259,9 @@ def check_meta(saved, now):
             raise ValueError(f"resume: the saved state's meta has no {k}")
         if saved[k] != now[k]:
             raise ValueError(f"resume: {k} = {now[k]!r} in this run, {saved[k]!r} in the saved state")
+    # (the condition of a property-conditioned run, DESIGN 41: the key exists in such a run's meta alone, so an unconditional run's meta is META_KEYS)
+    if saved.get("condition") != now.get("condition"):
+        raise ValueError(f"resume: condition = {now.get('condition')!r} in this run, {saved.get('condition')!r} in the saved state")
 
 
 def _to_cpu(x):
@@ -289,6 +318,29 @@ def _restore(model, optimizer, plateau, state, meta):
     return int(state["epoch"]), [dict(d) for d in state["history"]]
 
 
+def _fit_condition(model, data_list, spec):
+    """fit's cfg.condition = {properties: [...], num_freqs: F, p_uncond: 0.1} (guidance.parse_condition) against the module: the module must
+    be property-conditioned on exactly these properties and F (ValueError otherwise, and for a condition on an unconditional module or
+    none on a conditional one).  Fits the normaliser on the training set (every rank holds the whole set) and leaves it in the module and
+    in model.hparams["condition"].  Returns the parsed dict or None."""
+    from .guidance import PropertyNormalizer, parse_condition
+    cond = parse_condition(spec)
+    have = getattr(model, "condition", None)
+    if cond is None and have is None:
+        return None
+    if cond is None:
+        raise ValueError("fit: the module is property-conditioned (latent_dim > 0) and the config has no `condition`")
+    if have is None or list(have["properties"]) != cond["properties"] or int(have["num_freqs"]) != cond["num_freqs"]:
+        raise ValueError(f"fit: condition = {cond['properties']} with num_freqs = {cond['num_freqs']} is not what the module was built for "
+                         f"({None if have is None else (have['properties'], have['num_freqs'])}): DiffCSPModule(latent_dim=2 F P, condition=...)")
+    nm = PropertyNormalizer(cond["properties"]).fit(data_list)
+    if not np.isfinite(nm.raw(data_list)).any():
+        raise ValueError(f"fit: no training crystal carries any of the properties {cond['properties']} (CrystalData.properties)")
+    model.set_normalizer(nm)
+    model.condition["p_uncond"] = model.hparams["condition"]["p_uncond"] = cond["p_uncond"]
+    return cond
+
+
 def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging.info, on_epoch_end=None, times_fn=None, checkpoint=None,
         resume=None):
     """Train `model` (a DiffCSPModule of the trained grid) on `data_list` (CrystalData records).  cfg (key or attribute access): lr,
@@ -311,6 +363,10 @@ def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging
     tests).  on_epoch_end(epoch, stats) runs after every epoch.
     Data parallel: every mini-batch is sharded over the ranks (dist.shard_range) with the whole mini-batch's counts, one flat all-reduce
     precedes each optimizer step, and a rank whose shard is empty still reduces, steps and advances its Philox call id.
+    condition = null (default) or {properties: [...], num_freqs: F, p_uncond: 0.1} on a property-conditioned module: the
+    normaliser is fitted on the training set and stored in model.hparams["condition"] (a saved model reloads with it), every micro-step
+    trains under the crystals' values with the device's condition dropout, the validation pass under the values without dropout, and the
+    condition is part of run_meta (a resume under another one is refused by name).
     Returns the list of per-epoch dicts: train_loss, lattice_loss, coord_loss, type_loss (means over the epoch's mini-batches), val_loss,
     val_lattice_loss, val_coord_loss, val_type_loss with a validation set, lr (the epoch's), and the optimizer's grad statistics when it
     clips or guards."""
@@ -334,6 +390,7 @@ def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging
     opt = clip_options(cfg)
     pool_kw = parse_handle_pool(cfg_get(cfg, "handle_pool"))
     ema = parse_ema(cfg_get(cfg, "ema"))
+    cond = _fit_condition(model, data_list, cfg_get(cfg, "condition"))
     rank, world = rank_world()
     dev = model.device
     theta = model.decoder.theta
@@ -347,7 +404,7 @@ def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging
     n = len(data_list)
     out, first, meta = [], 0, None
     if checkpoint is not None or resume is not None:
-        meta = run_meta(model, optimizer, plateau, seed, batch_size, accum, shuffle, n, 0 if val_list is None else len(val_list), ema)
+        meta = run_meta(model, optimizer, plateau, seed, batch_size, accum, shuffle, n, 0 if val_list is None else len(val_list), ema, cond)
     if resume is not None:
         first, out = _restore(model, optimizer, plateau, resume, meta)
     if ema is not None:
@@ -355,7 +412,7 @@ def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging
     pool = None if pool_kw is None else HandlePool(**pool_kw)
     try:
         return _fit_epochs(model, data_list, val_list, seed, noise_fn, log, on_epoch_end, times_fn, epochs, batch_size, accum, shuffle, optimizer,
-                           plateau, pool, out, first, ema, checkpoint, meta)
+                           plateau, pool, out, first, ema, checkpoint, meta, cond)
     finally:
         if pool is not None:
             model.__dict__["handle_pool_stats"] = pool.stats()   # (the run's pool just before it is closed: HandlePool.stats())
@@ -363,7 +420,7 @@ def fit(model, data_list, cfg, val_list=None, seed=0, noise_fn=None, log=logging
 
 
 def _fit_epochs(model, data_list, val_list, seed, noise_fn, log, on_epoch_end, times_fn, epochs, batch_size, accum, shuffle, optimizer, plateau, pool, out,
-                first=0, ema=None, checkpoint=None, meta=None):
+                first=0, ema=None, checkpoint=None, meta=None, cond=None):
     """fit's epoch loop (its docstring); `pool`: the run's HandlePool or None; `first`: the epoch to start at; `ema`: parse_ema's dict."""
     from .finetune import _epoch_reduce
     rank, world = rank_world()
@@ -383,9 +440,10 @@ def _fit_epochs(model, data_list, val_list, seed, noise_fn, log, on_epoch_end, t
             if own:
                 noise = None if noise_fn is None else _slice_noise(noise_fn(epoch, step), rows, [int(d.num_atoms) for d in items])
                 times = draw_times(len(idx), T, epoch, step, seed) if times_fn is None else np.asarray(times_fn(epoch, step, len(idx)))
+                kw = {} if cond is None else dict(y=model.normalizer.raw(own), p_uncond=cond["p_uncond"])
                 train_step(model, _as_batch(own, dev), times[rows[0]:rows[1]], noise=noise, grad=theta.grad,
                            stats=acc, b_global=b_glob, n_global=n_glob, accum_steps=accum, seed=seed, call_id=model._noise_calls, offsets=offsets,
-                           pool=pool)
+                           pool=pool, **kw)
             if window_closes(step + 1, accum, len(plan)):
                 allreduce_flat_(theta.grad)
                 optimizer.step()

@@ -42,7 +42,8 @@ class DiffCSPSampler:
     seed: int = 0
 
     def generate(self, model, batch_size=None, num_batches=None, sample_steps=None, condition=None, target_compositions_dict=None,
-                 resample_times=None, jump_length=None, **kwargs) -> Tuple[List[CrystalData], list]:
+                 resample_times=None, jump_length=None, properties_to_condition_on=None, diffusion_guidance_factor=None,
+                 **kwargs) -> Tuple[List[CrystalData], list]:
         """sample.py:148-201.  Extra kwargs (`max_num`, `filter`, ...) are tolerated like the reference.
         `sample_steps` = S: the chains run on S of the model's T trained steps (model.respaced(S)); None: all of them.
         As in the reference, every batch is sampled but only the LAST batch's outputs are unpacked
@@ -54,7 +55,10 @@ class DiffCSPSampler:
         fixed (Condition.composition) and the atom counts come from the compositions instead of the mp_20 draw.  `condition`: an explicit
         conditioning.Condition for all batch_size x num_batches crystals, or for batch_size of them (then used for every batch).
         `resample_times` = r with `jump_length` = j (DiffCSPModule.sample's `resample`): the conditioned chains make RePaint's
-        resampling jumps; both or neither, and only with a condition (ValueError).  Levels are step indices under `sample_steps`."""
+        resampling jumps; both or neither, and only with a condition (ValueError).  Levels are step indices under `sample_steps`.
+        `properties_to_condition_on` = {name: value} with `diffusion_guidance_factor` = gamma (default 0; DiffCSPModule.sample's
+        `guidance`): every crystal is sampled under these property values by a property-conditioned model, with classifier-free guidance
+        of that factor.  ValueError: a factor without properties, either together with a condition."""
         batch_size = batch_size or self.batch_size
         num_batches = num_batches or self.num_batches
         assert batch_size is not None and num_batches is not None
@@ -74,6 +78,14 @@ class DiffCSPSampler:
         resample = None if resample_times is None else (resample_times, jump_length)
         if resample is not None and condition is None:
             raise ValueError("DiffCSPSampler.generate: resample_times / jump_length need a condition (target_compositions_dict or condition)")
+        guide = None
+        if properties_to_condition_on:
+            if condition is not None:
+                raise ValueError("DiffCSPSampler.generate: properties_to_condition_on together with a condition is not supported")
+            from .guidance import Guidance
+            guide = Guidance({k: float(v) for k, v in dict(properties_to_condition_on).items()}, diffusion_guidance_factor or 0.0)
+        elif diffusion_guidance_factor:
+            raise ValueError("DiffCSPSampler.generate: diffusion_guidance_factor needs properties_to_condition_on")
         rank, world = int(kwargs.get("rank", 0)), int(kwargs.get("world_size", 1))
         model = _strided(model, sample_steps)
         model.eval()
@@ -102,7 +114,7 @@ class DiffCSPSampler:
                 c0 = bi * batch_size % len(condition)
                 cond = condition.slice(c0 + lo, c0 + hi)
             outputs, _ = model.sample(counts, step_lr=step_lr, seed=self.seed, node_offset=node_off, graph_offset=lo, condition=cond,
-                                      **({} if resample is None else {"resample": resample}))
+                                      **({} if resample is None else {"resample": resample}), **({} if guide is None else {"guidance": guide}))
         data_list = _unpack(model, counts, outputs, node_off, lo, where="DiffCSPSampler.generate")
         struc_list = [data2struc(d) for d in data_list]
         if world > 1 or collectives_on():
@@ -183,6 +195,8 @@ def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_st
     from .filters import invalid_filter
     from .resampling import refuse
     refuse("sample_mdp", resample=resample)
+    from .guidance import refuse_latent
+    refuse_latent(model, "sample_mdp")
     _refuse_condition("sample_mdp", condition)
     model = _strided(model, sample_steps)
     counts, step_lr = _prelude(sample_size, model, step_lr)
@@ -271,6 +285,8 @@ def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=T
     from .filters import invalid_filter
     from .resampling import refuse
     refuse("sample_rollout", resample=resample)
+    from .guidance import refuse_latent
+    refuse_latent(model, "sample_rollout")
     if not check_likelihood("sample_rollout", likelihood, condition):
         _refuse_condition("sample_rollout", condition)
     elif len(condition) != int(sample_size):

@@ -111,6 +111,9 @@ class DiffCSPSuite(ModelSuite):
         (pipeline.Pretrain marks averaged weights with {"weights": "ema"})."""
         os.makedirs(save_dir, exist_ok=True)
         cfg = model.config
+        if getattr(model, "condition", None) is not None:   # a property-conditioned prior: the fitted normaliser travels in hparams.yaml (DESIGN 41)
+            cfg = C.create(C.to_container(cfg, resolve=True))
+            (cfg["model"] if "model" in cfg else cfg)["condition"] = C.create(dict(model.hparams["condition"]))
         torch.save({"state_dict": {k: v.cpu() for k, v in model.state_dict().items()}, "config": C.to_container(cfg, resolve=True), **(extra or {})},
                    os.path.join(save_dir, "last.ckpt"))
         C.save(cfg, os.path.join(save_dir, "hparams.yaml"))
