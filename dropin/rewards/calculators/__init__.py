@@ -1,1 +1,1 @@
-from matinvent_amd.rewards import PyMatGen  # noqa: F401
+from matinvent_amd.rewards import PyMatGen, Surrogate  # noqa: F401

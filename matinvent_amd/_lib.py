@@ -285,10 +285,19 @@ GUIDANCE_SIGNATURES = {
     "mi_guidance_combine": (_I, [_P, _P, C.c_float, _L, _L, _L, _P, _P]),
 }
 
+# the property-predictor extension, include/matinvent_hip_scalar.h (the trunk with a scalar head: inference forward, training micro-step)
+SCALAR_LOSS_MSE, SCALAR_LOSS_L1 = 0, 1   # include/matinvent_hip_scalar.h
+
+SCALAR_SIGNATURES = {
+    "mi_scalar_forward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "mi_scalar_micro_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, C.POINTER(_I), _P, C.POINTER(_I), _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mi_scalar_read": (_I, [_P, _I, _P, _P, _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        PRETRAIN_SIGNATURES)
+                        SCALAR_SIGNATURES, PRETRAIN_SIGNATURES)
 
 _lib = None
 

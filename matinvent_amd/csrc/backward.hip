@@ -907,8 +907,11 @@ int net_wgrad_flush(mi_net* net, mi_batch* b, float* grad, hipStream_t s) {
 
 static inline dim3 g1(int64_t n) { return dim3((unsigned)cdiv(n, 256)); }
 
-int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_coord, const float* d_type, float* grad, hipStream_t s) {
+int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_coord, const float* d_type, float* grad, hipStream_t s,
+                 const float* dgf_seed) {
     MI_CHECK(b->tape.allocated && b->tape.valid, MI_ESTATE, "mi_cspnet_backward without a preceding training forward on this batch");
+    // (dgf_seed -- scalar_head.hip: the pass starts from d gf alone, the three heads are not part of it; its entry refuses a deferred window)
+    MI_CHECK(!dgf_seed || b->tape.wslots == 0, MI_ESTATE, "a backward seeded from the graph features runs without a weight-gradient window");
     const int H = net->H, L = net->L, N = b->N, B = b->B, TD = net->TD, F = net->F;
     const int64_t E = b->E;
     if (N == 0 || B == 0) return MI_OK;
@@ -927,6 +930,9 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
     float* const dlo = hw ? t.w_dlo + hs * B * 12 : t.dlo;
     float* const dh = hw ? t.w_dh + hs * NH : t.dh;
     // ---------------- heads ----------------
+    if (dgf_seed) {   // d hf[i] = dgf[g(i)] / n_g and nothing else: no head's data or weight gradient, their slices of `grad` stay as they are
+        MI_TRY(scalar_seed_hf(b, dgf_seed, t.dY, H, s));
+    } else {
     hipLaunchKernelGGL(lattice_head_bwd_kernel, dim3(B), dim3(256), 0, s, d_lat, t.in_lat, net->p("lattice_out.weight"), dlo, t.dgf, H);
     MI_KERNEL_CHECK();
     hipLaunchKernelGGL(heads_bwd_kernel, g1(NH), dim3(256), 0, s, d_type, d_coord, t.dgf, net->p("type_out.weight"),
@@ -942,6 +948,7 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
         MI_TRY(gemm_tn_auto(d_type, MI_NUM_TYPES, b->hf, H, G("type_out.weight"), H, N, MI_NUM_TYPES, H, sc, scf, s));
         MI_TRY(colsum_acc(d_type, MI_NUM_TYPES, G("type_out.bias"), N, MI_NUM_TYPES, sc, scf, s));
         MI_TRY(gemm_tn_auto(d_coord, 3, b->hf, H, G("coord_out.weight"), H, N, 3, H, sc, scf, s));
+    }
     }
 
     auto ln_bwd = [&](const float* dy, int ld_dy, const float* x, const float* stats, const std::string& wname, float* dx, int accumulate) {
@@ -1346,19 +1353,7 @@ int net_pack_transposes(mi_net* n, hipStream_t s) {
 }
 
 // ---- forward noising (diffusion.py:81-119) --------------------------------------------------------
-// lattice_params_to_matrix_torch (models/diffcsp/utils.py:68-96)
-__device__ __forceinline__ void lattice_matrix(const float* len, const float* ang, float* M) {
-    const float d2r = 0.017453292519943295f;
-    float c0 = cosf(ang[0] * d2r), c1 = cosf(ang[1] * d2r), c2 = cosf(ang[2] * d2r);
-    float s0 = sinf(ang[0] * d2r), s1 = sinf(ang[1] * d2r);
-    float val = (c0 * c1 - c2) / (s0 * s1);
-    val = fminf(1.f, fmaxf(-1.f, val));
-    float gs = acosf(val);
-    M[0] = len[0] * s1; M[1] = 0.f; M[2] = len[0] * c1;
-    M[3] = -len[1] * s0 * cosf(gs); M[4] = len[1] * s0 * sinf(gs); M[5] = len[1] * c0;
-    M[6] = 0.f; M[7] = 0.f; M[8] = len[2];
-}
-
+// (lattice_matrix -- lattice_params_to_matrix_torch -- is in common.h: scalar_head.hip builds its clean inputs with it as well)
 // d_log_p_wrapped_normal(x, sigma) (scheduler.py:39-43), 21 images
 __device__ __forceinline__ float d_log_p_wn(float x, float sigma) {
     float num = 0.f, den = 0.f;

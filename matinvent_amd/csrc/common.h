@@ -100,6 +100,20 @@ __device__ __forceinline__ float pymod1(float x) {
     return r;
 }
 
+// lattice_params_to_matrix_torch (models/diffcsp/utils.py:68-96): the forward noising (backward.hip) and the property predictor's clean
+// inputs (scalar_head.hip) build the lattice matrix with this one function
+__device__ __forceinline__ void lattice_matrix(const float* len, const float* ang, float* M) {
+    const float d2r = 0.017453292519943295f;
+    float c0 = cosf(ang[0] * d2r), c1 = cosf(ang[1] * d2r), c2 = cosf(ang[2] * d2r);
+    float s0 = sinf(ang[0] * d2r), s1 = sinf(ang[1] * d2r);
+    float val = (c0 * c1 - c2) / (s0 * s1);
+    val = fminf(1.f, fmaxf(-1.f, val));
+    float gs = acosf(val);
+    M[0] = len[0] * s1; M[1] = 0.f; M[2] = len[0] * c1;
+    M[3] = -len[1] * s0 * cosf(gs); M[4] = len[1] * s0 * sinf(gs); M[5] = len[1] * c0;
+    M[6] = 0.f; M[7] = 0.f; M[8] = len[2];
+}
+
 // Branch-free sin & cos for |x| <~ 1e4 (Fourier arguments are bounded by 2*pi*F*|d|): three-term
 // Cody-Waite reduction by pi/2 with FMAs, then the classic degree-7/8 minimax kernels on
 // [-pi/4, pi/4].  Max abs error ~1.2e-7 over the range (measured against fp64 in

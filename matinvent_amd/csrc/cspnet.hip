@@ -962,7 +962,8 @@ static int launch_edge(mi_net* net, mi_batch* b, int layer, const float* frac, f
 }
 
 int net_forward(mi_net* net, mi_batch* b, const float* t_emb, const float* atom_types, const float* frac,
-                const float* lattices, float* lattice_out, float* coord_out, float* type_out, hipStream_t s, bool train, bool reuse_embedding, bool coords_only) {
+                const float* lattices, float* lattice_out, float* coord_out, float* type_out, hipStream_t s, bool train, bool reuse_embedding, bool coords_only,
+                bool trunk_only) {
     MI_CHECK(net->theta != nullptr, MI_ESTATE, "mi_cspnet_forward before mi_net_set_params");
     const int H = net->H, L = net->L, N = b->N, B = b->B, TD = net->TD;
     if (N == 0 || B == 0) return MI_OK;
@@ -1320,6 +1321,10 @@ int net_forward(mi_net* net, mi_batch* b, const float* t_emb, const float* atom_
         hipLaunchKernelGGL(copy_rows_kernel, dim3(cdiv(NH, 256)), dim3(256), 0, s, h_last, b->hf, H, N, H);
     }
     MI_KERNEL_CHECK();
+    if (trunk_only) {   // (scalar_head.hip: the property head pools b->hf itself; none of the three heads below is evaluated)
+        tp.valid = train;
+        return MI_OK;
+    }
     MI_CHECK(!(coords_only && train), MI_EINVAL, "a training forward evaluates every head");
     if (!train && net->WheadT && g_fused_heads && H % 64 == 0) {
         const int ncols = (coords_only && (g_eval_reuse & 4)) ? 3 : 3 + MI_NUM_TYPES;

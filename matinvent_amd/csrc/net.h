@@ -257,6 +257,11 @@ struct mi_batch {
     mi_batch* gd_partner = nullptr;
     float *gd_yhat = nullptr, *gd_freqs = nullptr;    // [B][gd_P], [MI_GUIDANCE_MAX_FREQS]
     int* gd_have = nullptr;                           // [B][gd_P]
+    // property predictor (scalar_head.hip, include/matinvent_hip_scalar.h; allocated on first use): the clean network inputs of the
+    // inference form (the taped form keeps them in the tape), the pooled features, and for sc_P properties the seeds d out and the crystals' loss terms
+    float* sc_in = nullptr;                           // in_lat [B][9] | in_frac [N][3] | in_types [N][100]
+    float *sc_gf = nullptr, *sc_dout = nullptr, *sc_parts = nullptr;   // [B][H], [B][sc_P], [B][sc_P][3] = e^2, |e|, present
+    int sc_P = 0, sc_last_P = 0;                      // the per-property buffers' capacity; the P of the last call (their layout)
     mi_pool* pool = nullptr;
     std::vector<int> edge_off_h, pair_off_h;
     int* edge_off = nullptr;   // [B + 1] first edge of each crystal (pooled handles only)
@@ -270,10 +275,15 @@ namespace mi {
 // its parameter epoch, so another network or an mi_net_set_params in between falls back to recomputing G / PQ0; unchanged lattices are the caller's promise.
 int net_forward(mi_net* net, mi_batch* b, const float* t_emb, const float* atom_types, const float* frac,
                 const float* lattices, float* lattice_out, float* coord_out, float* type_out, hipStream_t s, bool train = false,
-                bool reuse_embedding = false, bool coords_only = false);
+                bool reuse_embedding = false, bool coords_only = false, bool trunk_only = false);
 int net_tape_prepare(mi_net* net, mi_batch* b);
 int net_pack_transposes(mi_net* net, hipStream_t s);
-int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_coord, const float* d_type, float* grad, hipStream_t s);
+// dgf_seed [B][H] (scalar_head.hip): the pass is seeded from d gf ALONE -- d hf[i] = dgf_seed[g(i)] / n_g, no head's backward, the lattice_out.* /
+// type_out.* / coord_out.* slices of `grad` untouched; d_lat / d_coord / d_type are not read.  NULL: the three heads' seeds, as ever.
+int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_coord, const float* d_type, float* grad, hipStream_t s,
+                 const float* dgf_seed = nullptr);
+// scalar_head.hip: that broadcast (one launch), and the trunk's forward alone -- net_forward(trunk_only) ends behind the final LayerNorm, b->hf
+int scalar_seed_hf(const mi_batch* b, const float* dgf, float* dhf, int H, hipStream_t s);
 // backward.hip: the fine-tune micro-step's sequence -- time fill and embedding, add_noise_kernel (draw ids 7-9 at call `noise_step`, or the
 // injected noise), the agent's training forward, the frozen prior's forward (forked onto aux_stream when given), the LOSS STAGE, net_backward
 // into grad_theta -- with the loss stage passed in: it reads both networks' predictions and the targets, writes the three gradient seeds

@@ -488,3 +488,61 @@ class Pretrain:
         if rank == 0:
             self._save("final")
         return self.history
+
+
+class TrainPredictor:
+    """Train a property predictor (predictor.fit_predictor) on labelled crystals: extxyz in, model directory out -- the
+    counterpart of Pretrain for the CSPNet trunk with a scalar head.  train_path / val_path: extxyz files whose frames carry the
+    properties as scalar `key=value` entries of the comment line; properties: the names to learn, one head row each; model: the
+    PropertyPredictor's arguments (hidden_dim, num_layers, time_dim, num_freqs, ln); train_cfg: fit_predictor's config (lr, epochs,
+    batch_size, accum_steps, loss, max_grad_norm, skip_nonfinite_steps, lr_plateau, handle_pool, ema).  predictor.save_predictor writes
+    <save_dir>/models/final -- a directory rewards.Surrogate(model_path=...) loads -- holding the averaged weights when train_cfg.ema is
+    set.  `run_rl` is the entry the drop-in's main calls; model_suite and reward play no part.  One GPU only."""
+
+    def __init__(self, train_path, save_dir, properties, model=None, train_cfg=None, val_path=None, seed=0, device=None, logger=None,
+                 model_suite=None, reward=None, **kwargs):
+        if not train_path:
+            raise ValueError("TrainPredictor: train_path (an extxyz file) is required")
+        names = [properties] if isinstance(properties, str) else [str(p) for p in (properties or [])]
+        if not names:
+            raise ValueError("TrainPredictor: properties (the names of the frames' key=value entries to learn) is required")
+        self.train_path, self.val_path, self.names, self.logger = train_path, val_path, names, logger
+        self.save_dir, self.seed = save_dir, int(seed)
+        self.device = get_device(device)
+        self.model_cfg = C.to_container(C.create(model or {}), resolve=True)
+        self.train_cfg = C.create(train_cfg or {})
+        self.cfg = C.create(kwargs)
+        self.models_dir = os.path.join(save_dir, "models")
+        os.makedirs(self.models_dir, exist_ok=True)
+        self.model, self.history = None, []
+
+    read_dataset = staticmethod(Pretrain.read_dataset)
+
+    def load_model(self):
+        from .predictor import PropertyPredictor
+        self.model = PropertyPredictor(self.names, device=self.device, seed=self.seed, **self.model_cfg)
+        return self.model
+
+    def _save(self, name):
+        from .predictor import save_predictor
+        path = os.path.join(self.models_dir, name)
+        opt = self.model.__dict__.get("fit_optimizer")
+        if opt is not None and opt.ema_decay is not None:
+            with opt.ema_weights(self.model):
+                return save_predictor(self.model, path)
+        return save_predictor(self.model, path)
+
+    def run_rl(self):
+        from .predictor import fit_predictor
+        train = self.read_dataset(self.train_path)
+        val = self.read_dataset(self.val_path) if self.val_path else None
+        if self.model is None:
+            self.load_model()
+        logging.info(f"training a predictor of {self.names} on {len(train)} crystals" + (f", validating on {len(val)}" if val is not None else ""))
+
+        def on_epoch_end(epoch, d):
+            if self.logger is not None:
+                self.logger.log(dict(d), step=epoch)
+        self.history = fit_predictor(self.model, train, self.train_cfg, val_list=val, seed=self.seed, on_epoch_end=on_epoch_end)
+        self._save("final")
+        return self.history

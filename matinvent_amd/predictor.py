@@ -1,0 +1,523 @@
+"""Property predictor: the CSPNet trunk with a scalar head, trained on labelled crystals and used as a reward.
+
+The reference's CSPNet(pred_scalar=True) (models/diffcsp/cspnet.py:145-147, 281-284) pools the final node features per crystal with a mean
+and applies scalar_out = nn.Linear(hidden_dim, 1).  Here the head has P >= 1 outputs (P = 1: the reference), one per property name:
+
+    out[b][p] = bias[p] + sum_f mean_i(hf_i)[f] W[p][f]                                    (normalised units)
+    loss      = sum_p (1 / P) sum_{b: target present} l(out - yhat) / count[p]             l = e^2 ("mse") or |e| ("l1")
+
+Every call is one entry of include/matinvent_hip_scalar.h: the clean inputs at time 0, the trunk, the head, the loss with its statistics
+and -- training -- the backward, enqueued with no host synchronisation.  The model keeps ONE flat vector [trunk theta | W | bias]; the
+trunk's parameter vector is a view of its head, so FusedAdam's clipping, guard and average work on it as on any flat parameter.
+"""
+import contextlib
+import ctypes as C
+import logging
+import os
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from . import config as CFG
+from .guidance import PropertyNormalizer
+
+LOSS_KINDS = {"mse": _lib.SCALAR_LOSS_MSE, "l1": _lib.SCALAR_LOSS_L1}
+HPARAMS_FILE, WEIGHTS_FILE = "hparams.yaml", "last.ckpt"
+HPARAM_KEYS = ("names", "hidden_dim", "num_layers", "time_dim", "num_freqs", "ln", "edge_style")
+
+
+def stats_len(P):
+    """mi_scalar_micro_step's stats: [0] loss, then per property sum e^2, sum |e|, present targets."""
+    return 1 + 3 * int(P)
+
+
+def _names(names):
+    names = [names] if isinstance(names, str) else [str(n) for n in (names or [])]
+    if not names or len(set(names)) != len(names):
+        raise ValueError(f"PropertyPredictor: the property names {names} must be distinct and at least one")
+    return names
+
+
+class PropertyPredictor(nn.Module):
+    """The trunk (a CSPNet of the DiffCSPModule configuration, whose three heads are never evaluated here), the head and the normaliser.
+    names: the properties, one head row each.  seed: the initial weights are drawn under it (None: torch's global generator).
+    latent_dim > 0 (a property-conditioned trunk) is refused: ValueError, before any device work."""
+
+    def __init__(self, names, hidden_dim=128, num_layers=4, time_dim=256, num_freqs=10, ln=True, edge_style="fc", normalizer=None, device=None,
+                 seed=None, latent_dim=0):
+        super().__init__()
+        self.names = _names(names)
+        if int(latent_dim) != 0:
+            raise ValueError(f"PropertyPredictor: latent_dim = {latent_dim}: a latent (property-conditioned) net has no predictor form; "
+                             "the trunk's embedding input is the time embedding alone")
+        if normalizer is not None and list(normalizer.names) != self.names:
+            raise ValueError(f"PropertyPredictor: the normaliser's names {list(normalizer.names)} differ from the model's {self.names}")
+        from .cspnet import CSPNet
+        from .schedules import time_embedding_freqs
+        self.hparams = dict(names=list(self.names), hidden_dim=int(hidden_dim), num_layers=int(num_layers), time_dim=int(time_dim),
+                            num_freqs=int(num_freqs), ln=bool(ln), edge_style=str(edge_style))
+        with contextlib.ExitStack() as st:
+            if seed is not None:
+                st.enter_context(torch.random.fork_rng(devices=[]))
+                torch.manual_seed(int(seed))
+            trunk = CSPNet(hidden_dim=hidden_dim, latent_dim=time_dim, num_layers=num_layers, num_freqs=num_freqs, edge_style=edge_style, ln=ln,
+                           smooth=True, pred_type=True, device=device)
+            H, P = int(hidden_dim), len(self.names)
+            head = nn.Linear(H, P)   # (nn.Linear's default init, drawn behind the trunk's: the reference's construction order)
+        self.__dict__["trunk"] = trunk   # (not a sub-module: its parameter is a view of `flat`, the one parameter of this module)
+        self.n_trunk = trunk.theta.numel()
+        dev = trunk.theta.device
+        flat = torch.cat([trunk.theta.data.reshape(-1), head.weight.data.reshape(-1).to(dev), head.bias.data.reshape(-1).to(dev)])
+        self.flat = nn.Parameter(flat.contiguous())
+        self.register_buffer("time_freqs", time_embedding_freqs(time_dim).to(dev, torch.float32).contiguous(), persistent=False)
+        self.normalizer = normalizer if normalizer is not None else PropertyNormalizer(self.names)
+        self._tie()
+
+    # ---- the flat vector ---------------------------------------------------------------------------
+    def _tie(self):
+        """The trunk's theta becomes the head of `flat` (same memory), and `flat` names this module as the owner an optimizer tells about
+        an in-place update."""
+        t = nn.Parameter(self.flat.data[:self.n_trunk], requires_grad=False)
+        t._mi_owner = self.trunk
+        self.trunk.theta = t
+        self.trunk.mark_dirty()
+        self.flat._mi_owner = self
+
+    def _apply(self, fn, *a, **k):
+        r = super()._apply(fn, *a, **k)
+        self._tie()
+        return r
+
+    def mark_dirty(self):
+        self.trunk.mark_dirty()
+
+    @property
+    def P(self):
+        return len(self.names)
+
+    @property
+    def hidden_dim(self):
+        return self.trunk.hidden_dim
+
+    @property
+    def device(self):
+        return self.flat.device
+
+    def head_slices(self, v=None):
+        """(trunk, W [P H], bias [P]) views of a vector laid out like `flat` (default: flat's data)."""
+        v = self.flat.data if v is None else v
+        n, k = self.n_trunk, self.P * self.hidden_dim
+        return v[:n], v[n:n + k], v[n + k:]
+
+    def set_normalizer(self, nm):
+        if list(nm.names) != self.names:
+            raise ValueError(f"PropertyPredictor: the normaliser's names {list(nm.names)} differ from the model's {self.names}")
+        self.normalizer = nm
+
+    def state_dict(self, *args, destination=None, prefix="", keep_vars=False):
+        """The reference's names: scalar_out.weight [P, H], scalar_out.bias [P], then the trunk's tensors."""
+        from collections import OrderedDict
+        out = destination if destination is not None else OrderedDict()
+        _, W, b = self.head_slices()
+        out[prefix + "scalar_out.weight"] = W.detach().clone().view(self.P, self.hidden_dim)
+        out[prefix + "scalar_out.bias"] = b.detach().clone()
+        return self.trunk.state_dict(destination=out, prefix=prefix)
+
+    def load_state_dict(self, state_dict, strict=True):
+        _, W, b = self.head_slices()
+        missing = [k for k in ("scalar_out.weight", "scalar_out.bias") if k not in state_dict]
+        with torch.no_grad():
+            if "scalar_out.weight" in state_dict:
+                W.copy_(state_dict["scalar_out.weight"].reshape(-1))
+            if "scalar_out.bias" in state_dict:
+                b.copy_(state_dict["scalar_out.bias"].reshape(-1))
+        errs = []
+        self.trunk._load_from_state_dict(state_dict, "", {}, strict, missing, [], errs)
+        if strict and missing:
+            raise KeyError(f"PropertyPredictor.load_state_dict: missing {missing}")
+        self.trunk.mark_dirty()
+        return missing
+
+    def make_batch(self, num_atoms, node_offset=0, graph_offset=0, pool=None):
+        return self.trunk.make_batch(num_atoms, node_offset, graph_offset, pool=pool)
+
+    def predict(self, records_or_batch, batch_size=64, pool=None):
+        return predict(self, records_or_batch, batch_size=batch_size, pool=pool)
+
+
+# ---- records --------------------------------------------------------------------------------------------
+def _record_fields(r):
+    """(atomic numbers [n] int64, frac [n, 3] float32, lengths [3], angles [3]) of a CrystalData, a SimpleStructure, a read_extxyz frame or
+    a pymatgen Structure; raises for anything that is not a crystal."""
+    if hasattr(r, "atom_types"):
+        z = np.asarray(r.atom_types.cpu() if torch.is_tensor(r.atom_types) else r.atom_types).reshape(-1)
+        tn = lambda x: np.asarray(x.cpu() if torch.is_tensor(x) else x, dtype=np.float64)
+        return z.astype(np.int64), tn(r.frac_coords).reshape(-1, 3), tn(r.lengths).reshape(3), tn(r.angles).reshape(3)
+    if hasattr(r, "lattice") and hasattr(r.lattice, "abc"):   # pymatgen
+        return (np.asarray(r.atomic_numbers, dtype=np.int64), np.asarray(r.frac_coords, dtype=np.float64).reshape(-1, 3),
+                np.asarray(r.lattice.abc, dtype=np.float64), np.asarray(r.lattice.angles, dtype=np.float64))
+    return (np.asarray([int(z) for z in r.species], dtype=np.int64), np.asarray(r.frac_coords, dtype=np.float64).reshape(-1, 3),
+            np.asarray(r.lengths, dtype=np.float64).reshape(3), np.asarray(r.angles, dtype=np.float64).reshape(3))
+
+
+def _valid_fields(r):
+    """_record_fields, or None for a record the network cannot take: no atom, an atomic number outside 1..100, a non-finite value."""
+    try:
+        z, x, le, an = _record_fields(r)
+    except Exception:
+        return None
+    if z.size < 1 or x.shape[0] != z.size or z.min() < 1 or z.max() > 100:
+        return None
+    if not (np.isfinite(x).all() and np.isfinite(le).all() and np.isfinite(an).all()):
+        return None
+    return z, x, le, an
+
+
+class _Arrays:
+    """The collated arrays of a list of _record_fields tuples (what train_step reads of a CrystalBatchData)."""
+
+    def __init__(self, fields):
+        self.num_atoms = [int(f[0].size) for f in fields]
+        self.atom_types = torch.from_numpy(np.concatenate([f[0] for f in fields])) if fields else torch.zeros(0, dtype=torch.long)
+        self.frac_coords = torch.from_numpy(np.concatenate([f[1] for f in fields]).astype(np.float32)) if fields else torch.zeros(0, 3)
+        self.lengths = torch.from_numpy(np.stack([f[2] for f in fields]).astype(np.float32)) if fields else torch.zeros(0, 3)
+        self.angles = torch.from_numpy(np.stack([f[3] for f in fields]).astype(np.float32)) if fields else torch.zeros(0, 3)
+
+
+def _counts(batch):
+    na = batch.num_atoms
+    return [int(v) for v in (na.tolist() if torch.is_tensor(na) else na)]
+
+
+def _times(times, B, dev):
+    tm = torch.as_tensor(times).reshape(-1).to(dev, torch.int32).contiguous()
+    if tm.numel() != B:
+        raise ValueError(f"times holds {tm.numel()} values for {B} crystals")
+    return tm
+
+
+# ---- one call ---------------------------------------------------------------------------------------------
+def train_step(model, batch, y=None, grad=None, stats=None, count_global=None, accum_steps=1, loss="mse", forward_only=False, out=None,
+               pool=None, offsets=(0, 0), yhat=None, have=None, handle=None, t_all=0, times=None):
+    """One micro-step on the current stream (mi_scalar_micro_step): `batch` (num_atoms, lengths, angles, frac_coords, atom_types) against
+    the raw targets y [B][P] (NaN: missing), normalised by the model's normaliser -- or yhat / have, already normalised.  Accumulates (+=)
+    into `grad` (laid out like model.flat; default flat.grad, allocated when absent) and `stats` (stats_len(P) device floats; returned).
+    count_global [P]: the present targets per property the loss is normalised by (default: this batch's own).  forward_only=True: no tape,
+    no backward, `grad` untouched (the validation form).  out: [B][P] device floats for the normalised predictions, or None.
+    handle: a CrystalBatch of these atom counts to run on (kept by the caller); None: a handle for this call only, from `pool` when given
+    (nothing then waits for the device).  times [B] ints: the crystals' time steps of the time embedding (default: t_all for all; the
+    predictor of this module is trained and used at time 0)."""
+    if loss not in LOSS_KINDS:
+        raise ValueError(f"train_step: loss = {loss!r}: it takes 'mse' or 'l1'")
+    lib = _lib.load()
+    from .cspnet import _ptr, _stream
+    dev = model.device
+    na = _counts(batch)
+    B, P = len(na), model.P
+    if yhat is None:
+        if y is None:
+            raise ValueError("train_step: no targets (y, or yhat and have)")
+        ya = np.asarray(y.cpu() if torch.is_tensor(y) else y, dtype=np.float64)
+        if ya.size != B * P:
+            raise ValueError(f"train_step: y holds {ya.size} values for {B} crystals x {P} properties")
+        yhat, have = model.normalizer.normalise(ya)
+    yhat = np.ascontiguousarray(np.asarray(yhat, dtype=np.float32).reshape(B, P))
+    have = np.ascontiguousarray(np.asarray(have, dtype=np.int32).reshape(B, P))
+    cg = have.sum(axis=0) if count_global is None else np.asarray(count_global)
+    cg = np.ascontiguousarray(cg.reshape(P), dtype=np.int32)
+    if stats is None:
+        stats = torch.zeros(stats_len(P), device=dev)
+    if not forward_only and grad is None:
+        if model.flat.grad is None:
+            model.flat.grad = torch.zeros_like(model.flat)
+        grad = model.flat.grad
+    if B == 0:
+        return stats
+    f = lambda x: x.to(dev, torch.float32).contiguous()
+    lengths, angles, frac0 = f(batch.lengths).view(-1, 3), f(batch.angles).view(-1, 3), f(batch.frac_coords)
+    at = batch.atom_types.to(dev, torch.int32).contiguous()
+    tm = None if times is None else _times(times, B, dev)
+    up = (lambda a: torch.from_numpy(a).to(dev)) if pool is None else (lambda a: torch.from_numpy(a).pin_memory().to(dev, non_blocking=True))
+    yhat_d, have_d, cg_d = up(yhat), up(have), up(cg)
+    model.trunk.sync()
+    _, W, bias = model.head_slices()
+    g = (None, None, None) if forward_only else model.head_slices(grad)
+    cb = handle if handle is not None else model.make_batch(na, int(offsets[0]), int(offsets[1]), pool=pool)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    try:
+        _lib.check(lib.mi_scalar_micro_step(model.trunk._h, cb._h, _ptr(lengths), _ptr(angles), _ptr(frac0), _ptr(at), _ptr(model.time_freqs), _ptr(tm),
+                                            int(t_all), _ptr(W), _ptr(bias), P, _ptr(yhat_d), _ptr(have_d), ip(have), _ptr(cg_d), ip(cg),
+                                            int(accum_steps), LOSS_KINDS[loss], _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(stats), _ptr(out), _stream()),
+                   "mi_scalar_micro_step")
+    finally:
+        if handle is None:
+            if pool is None:   # (the handle's memory is freed here: the host waits for the micro-step; a pooled handle frees nothing)
+                torch.cuda.current_stream().synchronize()
+            cb.release()
+    return stats
+
+
+def forward(model, batch, handle=None, pool=None, t_all=0, times=None):
+    """The normalised predictions [B][P] (device) of `batch` on the current stream: mi_scalar_forward.  times: as train_step's."""
+    lib = _lib.load()
+    from .cspnet import _ptr, _stream
+    dev = model.device
+    na = _counts(batch)
+    B, P = len(na), model.P
+    out = torch.empty(B, P, device=dev)
+    if B == 0:
+        return out
+    f = lambda x: x.to(dev, torch.float32).contiguous()
+    lengths, angles, frac0 = f(batch.lengths).view(-1, 3), f(batch.angles).view(-1, 3), f(batch.frac_coords)
+    at = batch.atom_types.to(dev, torch.int32).contiguous()
+    tm = None if times is None else _times(times, B, dev)
+    model.trunk.sync()
+    _, W, bias = model.head_slices()
+    cb = handle if handle is not None else model.make_batch(na, pool=pool)
+    try:
+        _lib.check(lib.mi_scalar_forward(model.trunk._h, cb._h, _ptr(lengths), _ptr(angles), _ptr(frac0), _ptr(at), _ptr(model.time_freqs), _ptr(tm),
+                                         int(t_all), _ptr(W), _ptr(bias), P, _ptr(out), _stream()), "mi_scalar_forward")
+    finally:
+        if handle is None:
+            if pool is None:
+                torch.cuda.current_stream().synchronize()
+            cb.release()
+    return out
+
+
+def predict(model, records_or_batch, batch_size=64, pool=None):
+    """De-normalised predictions, np.ndarray [n][P] float64, of a list of records (CrystalData, structures, read_extxyz frames) or of a
+    CrystalBatchData.  A crystal that cannot be evaluated -- no atoms, an atomic number outside 1..100, a non-finite value, an atom count
+    the batch handle refuses -- is a row of NaN, never an exception for the others."""
+    if int(batch_size) < 1:
+        raise ValueError(f"predict: batch_size = {batch_size}: must be >= 1")
+    P = model.P
+    mean, std = np.asarray(model.normalizer.mean, dtype=np.float64), np.asarray(model.normalizer.std, dtype=np.float64)
+    if hasattr(records_or_batch, "num_atoms") and hasattr(records_or_batch, "frac_coords") and not hasattr(records_or_batch, "properties"):
+        b = records_or_batch   # a collated batch: cut back into records
+        na = _counts(b)
+        off = np.concatenate([[0], np.cumsum(na)])
+        ten = lambda x: np.asarray(x.detach().cpu())
+        z, x, le, an = ten(b.atom_types), ten(b.frac_coords), ten(b.lengths).reshape(-1, 3), ten(b.angles).reshape(-1, 3)
+        from types import SimpleNamespace
+        records = [SimpleNamespace(species=z[off[i]:off[i + 1]].tolist(), frac_coords=x[off[i]:off[i + 1]], lengths=le[i], angles=an[i])
+                   for i in range(len(na))]
+    else:
+        records = list(records_or_batch)
+    out = np.full((len(records), P), np.nan, dtype=np.float64)
+    fields = [_valid_fields(r) for r in records]
+    ok = [i for i, f in enumerate(fields) if f is not None]
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            pend = []   # (rows, device result): read once at the end
+            for s in range(0, len(ok), int(batch_size)):
+                rows = ok[s:s + int(batch_size)]
+                try:
+                    pend.append((rows, forward(model, _Arrays([fields[i] for i in rows]), pool=pool)))
+                except _lib.MIError:
+                    for i in rows:   # one crystal of the batch is refused: each on its own, the refused one stays NaN
+                        try:
+                            pend.append(([i], forward(model, _Arrays([fields[i]]), pool=pool)))
+                        except _lib.MIError:
+                            pass
+            for rows, o in pend:
+                out[rows] = o.double().cpu().numpy() * std + mean
+    finally:
+        model.train(was_training)
+    return out
+
+
+def _eval_enqueue(model, data_list, batch_size, acc, loss="mse", pool=None):
+    """`evaluate` without the read-back: every mini-batch of the set in order, forward-only, normalised by the counts of the WHOLE set."""
+    from .data import CrystalBatchData
+    from .pretrain import batch_plan
+    yh, hv = model.normalizer(data_list)
+    cg = hv.sum(axis=0)
+    for idx in batch_plan(len(data_list), batch_size, 0, 0, shuffle=False):
+        train_step(model, CrystalBatchData([data_list[i] for i in idx]), yhat=yh[idx], have=hv[idx], stats=acc, count_global=cg, loss=loss,
+                   forward_only=True, pool=pool)
+    return acc
+
+
+def _metrics(model, a):
+    """stats (host list, stats_len(P)) -> per-property dict(mse, mae, mse_raw, mae_raw, count)."""
+    out = {}
+    for p, name in enumerate(model.names):
+        s2, sa, n = a[1 + 3 * p], a[2 + 3 * p], a[3 + 3 * p]
+        sd = float(model.normalizer.std[p])
+        mse, mae = (s2 / n, sa / n) if n > 0 else (float("nan"), float("nan"))
+        out[name] = dict(mse=mse, mae=mae, mse_raw=mse * sd * sd, mae_raw=mae * sd, count=int(round(n)))
+    return out
+
+
+def evaluate(model, data_list, batch_size, pool=None):
+    """Per property: mean squared and mean absolute error over the set's present targets, in normalised units (mse, mae) and in the
+    property's own (mse_raw, mae_raw), and the count.  Forward-only; mini-batches are weighted by their counts, so the result does not
+    depend on batch_size beyond fp32 summation order.  One host read."""
+    if int(batch_size) < 1:
+        raise ValueError(f"evaluate: batch_size = {batch_size}: must be >= 1")
+    if len(data_list) == 0:
+        raise ValueError("evaluate: an empty set")
+    was_training = model.training
+    model.eval()
+    try:
+        acc = _eval_enqueue(model, data_list, batch_size, torch.zeros(stats_len(model.P), device=model.device), pool=pool)
+    finally:
+        model.train(was_training)
+    return _metrics(model, acc.tolist())
+
+
+def _refuse_world(where):
+    from .dist import rank_world
+    world = int(rank_world()[1])
+    if world > 1:
+        raise ValueError(f"{where}: world size {world}: the predictor trains on one GPU only (data-parallel fit_predictor is out of scope)")
+
+
+def fit_predictor(model, data_list, cfg, val_list=None, seed=0, log=logging.info, on_epoch_end=None):
+    """Train `model` on `data_list` (CrystalData records carrying `properties`).  cfg (key or attribute access): lr, epochs, batch_size;
+    accum_steps (default 1); shuffle (default true); loss = "mse" (default) or "l1"; max_grad_norm / skip_nonfinite_steps; lr_plateau;
+    handle_pool; ema -- all as pretrain.fit reads them, and with its machinery: epochs of pretrain.batch_plan mini-batches (the only random
+    thing, a function of (seed, epoch)), one FusedAdam on the flat vector, one host read per epoch.  The normaliser is fitted on the
+    training set first.  With ema the optimizer is left in model.fit_optimizer (ema_weights(model) to predict or save the average).
+    One GPU only: a world size above 1 is a ValueError.  Returns the per-epoch dicts: train_loss, train_mse_<name>, with a validation set
+    val_loss and val_mse_<name> / val_mae_<name> (normalised units), lr, the optimizer's statistics."""
+    _refuse_world("fit_predictor")
+    from .data import CrystalBatchData
+    from .finetune import _epoch_reduce
+    from .optim import FusedAdam, cfg_get, clip_options, ema_decay_at, epoch_grad_stats, parse_ema, window_closes
+    from .pool import HandlePool, parse_handle_pool
+    from .pretrain import batch_plan, plateau_scheduler
+    v = {k: cfg_get(cfg, k) for k in ("lr", "epochs", "batch_size")}
+    for k, x in v.items():
+        if x is None:
+            raise KeyError(f"fit_predictor: the config has no {k}")
+    lr, epochs, batch_size = float(v["lr"]), int(v["epochs"]), int(v["batch_size"])
+    if batch_size < 1:
+        raise ValueError(f"fit_predictor: batch_size = {batch_size}: must be >= 1")
+    if len(data_list) == 0:
+        raise ValueError("fit_predictor: an empty training set")
+    if val_list is not None and len(val_list) == 0:
+        raise ValueError("fit_predictor: an empty validation set (pass None for no validation)")
+    accum = int(cfg_get(cfg, "accum_steps", 1))
+    if accum < 1:
+        raise ValueError(f"fit_predictor: accum_steps = {accum}: must be >= 1")
+    loss = str(cfg_get(cfg, "loss", "mse"))
+    if loss not in LOSS_KINDS:
+        raise ValueError(f"fit_predictor: loss = {loss!r}: it takes 'mse' or 'l1'")
+    shuffle = bool(cfg_get(cfg, "shuffle", True))
+    opt = clip_options(cfg)
+    pool_kw = parse_handle_pool(cfg_get(cfg, "handle_pool"))
+    ema = parse_ema(cfg_get(cfg, "ema"))
+    nm = PropertyNormalizer(model.names).fit(data_list)
+    if not np.isfinite(nm.raw(data_list)).any():
+        raise ValueError(f"fit_predictor: no training crystal carries any of the properties {model.names} (CrystalData.properties)")
+    model.set_normalizer(nm)
+    if ema is not None:
+        opt = dict(opt, ema_decay=ema["decay"], ema_warmup=ema["warmup"])
+    flat = model.flat
+    optimizer = FusedAdam([flat], lr=lr, **opt)
+    plateau = plateau_scheduler(optimizer, cfg_get(cfg, "lr_plateau"))
+    if flat.grad is None:
+        flat.grad = torch.zeros_like(flat)
+    if ema is not None:
+        model.__dict__["fit_optimizer"] = optimizer
+    dev, P, n = model.device, model.P, len(data_list)
+    yh, hv = nm(data_list)
+    pool = None if pool_kw is None else HandlePool(**pool_kw)
+    out = []
+    try:
+        for epoch in range(epochs):
+            model.train()
+            optimizer.zero_grad(set_to_none=False)
+            acc = torch.zeros(stats_len(P), device=dev)
+            plan = batch_plan(n, batch_size, epoch, seed, shuffle)
+            for step, idx in enumerate(plan):
+                train_step(model, CrystalBatchData([data_list[i] for i in idx]), yhat=yh[idx], have=hv[idx], grad=flat.grad, stats=acc,
+                           accum_steps=accum, loss=loss, pool=pool)
+                if window_closes(step + 1, accum, len(plan)):
+                    optimizer.step()
+                    optimizer.zero_grad(set_to_none=False)
+            if val_list is not None:
+                with optimizer.ema_weights(model) if ema is not None and ema["validate"] else contextlib.nullcontext():
+                    acc = torch.cat([acc, _eval_enqueue(model, val_list, batch_size, torch.zeros(stats_len(P), device=dev), loss=loss, pool=pool)])
+            k_ema = None
+            if ema is not None and optimizer.guarded:
+                k_ema = acc.numel()
+                acc = torch.cat([acc, optimizer.adam_steps()])
+            a = _epoch_reduce(acc, "fit_predictor", optimizer)   # the epoch's only host read
+            s_ema = None
+            if k_ema is not None:
+                s_ema = int(round(a.pop(k_ema)))
+            elif ema is not None:
+                s_ema = int(optimizer.state[flat]["step"])
+            d = dict(train_loss=a[0] / len(plan))
+            for name, m in _metrics(model, a[:stats_len(P)]).items():
+                d[f"train_mse_{name}"] = m["mse"]
+            k = stats_len(P)
+            if val_list is not None:
+                d["val_loss"] = a[k]
+                for name, m in _metrics(model, a[k:2 * k]).items():
+                    d[f"val_mse_{name}"], d[f"val_mae_{name}"] = m["mse"], m["mae"]
+                k *= 2
+            d["lr"] = float(optimizer.param_groups[0]["lr"])
+            if len(a) > k:
+                d.update(epoch_grad_stats(a[k:]))
+            if ema is not None:
+                d["ema_decay"] = ema_decay_at(ema["decay"], ema["warmup"], s_ema)
+            if plateau is not None:
+                plateau.step(d["val_loss"] if val_list is not None else d["train_loss"])
+            out.append(d)
+            log(f"Epoch {epoch}: " + ", ".join(f"{k_}: {v_:.6g}" for k_, v_ in d.items()))
+            if on_epoch_end is not None:
+                on_epoch_end(epoch, d)
+    finally:
+        if pool is not None:
+            model.__dict__["handle_pool_stats"] = pool.stats()
+            pool.close()
+    return out
+
+
+# ---- model directories ------------------------------------------------------------------------------------------
+def write_hparams(save_dir, hparams, normalizer):
+    os.makedirs(save_dir, exist_ok=True)
+    hp = {k: hparams[k] for k in HPARAM_KEYS}
+    hp.update(mean=[float(x) for x in normalizer.mean], std=[float(x) for x in normalizer.std])
+    CFG.save(CFG.create({"predictor": hp}), os.path.join(save_dir, HPARAMS_FILE))
+
+
+def read_hparams(model_dir, names=None):
+    """The `predictor` entry of <model_dir>/hparams.yaml as a dict.  names: the properties the caller expects, in order; a saved model
+    whose names differ is refused (ValueError naming both lists) before any weight is read."""
+    path = os.path.join(str(model_dir), HPARAMS_FILE)
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"load_predictor: {path} does not exist")
+    cfg = CFG.to_container(CFG.load(path), resolve=True)
+    if "predictor" not in cfg:
+        raise ValueError(f"load_predictor: {path} has no `predictor` entry (not a directory written by save_predictor)")
+    hp = dict(cfg["predictor"])
+    hp["names"] = [str(n) for n in hp["names"]]
+    if names is not None and _names(names) != hp["names"]:
+        raise ValueError(f"load_predictor: the saved model's names {hp['names']} differ from the expected names {_names(names)}")
+    return hp
+
+
+def save_predictor(model, save_dir):
+    """<save_dir>/hparams.yaml (the constructor's arguments and the normaliser) + last.ckpt ({"state_dict"}: scalar_out.*, then the trunk)."""
+    write_hparams(save_dir, model.hparams, model.normalizer)
+    torch.save({"state_dict": {k: v.cpu() for k, v in model.state_dict().items()}}, os.path.join(save_dir, WEIGHTS_FILE))
+    return save_dir
+
+
+def load_predictor(model_dir, device=None, names=None):
+    """The inverse of save_predictor.  names: see read_hparams."""
+    hp = read_hparams(model_dir, names)
+    nm = PropertyNormalizer(hp["names"], hp.get("mean"), hp.get("std"))
+    model = PropertyPredictor(normalizer=nm, device=device, **{k: hp[k] for k in HPARAM_KEYS})
+    ck = torch.load(os.path.join(str(model_dir), WEIGHTS_FILE), map_location="cpu", weights_only=False)
+    model.load_state_dict(ck["state_dict"])
+    return model

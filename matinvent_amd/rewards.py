@@ -82,6 +82,46 @@ class Reward:
         return rewards, prop_dict, failed
 
 
+class Surrogate:
+    """A trained property predictor (predictor.PropertyPredictor) as a calculator of `Reward.prop_cfg`: `.calc(samples, label)`
+    returns the de-normalised prediction of property `task` per structure, NaN for a structure the predictor cannot evaluate (-> failed ->
+    reward 0).  model_path: a directory written by predictor.save_predictor, loaded on first use; or predictor: a loaded model (anything
+    with `.names` and `.predict(records, batch_size=) -> [n][P]`).  An unknown `task` is a ValueError as soon as the names are known."""
+
+    def __init__(self, root_dir="rewards", model_path=None, predictor=None, task=None, batch_size=64, device=None, **kwargs):
+        if (model_path is None) == (predictor is None):
+            raise ValueError("Surrogate: give exactly one of model_path (a save_predictor directory) and predictor (a loaded model)")
+        if task is None:
+            raise ValueError("Surrogate: task (the name of the property to return) is required")
+        self.root_dir, self.model_path, self.task, self.batch_size, self.device = root_dir, model_path, str(task), int(batch_size), device
+        self.predictor = None
+        if predictor is not None:
+            self._adopt(predictor)
+        elif model_path is not None:
+            from .predictor import read_hparams
+            self._column(read_hparams(model_path)["names"])   # (the names are in hparams.yaml: an unknown task is refused before any weight is read)
+
+    def _column(self, names):
+        names = [str(n) for n in names]
+        if self.task not in names:
+            raise ValueError(f"Surrogate: unknown property name {self.task!r}: the predictor has {names}")
+        return names.index(self.task)
+
+    def _adopt(self, predictor):
+        self.col = self._column(predictor.names)
+        self.predictor = predictor
+
+    def calc(self, samples, label="tmp"):
+        strucs = samples[0] if isinstance(samples, tuple) else samples
+        if self.predictor is None:
+            from .predictor import load_predictor
+            self._adopt(load_predictor(self.model_path, device=self.device))
+        if len(strucs) == 0:
+            return np.zeros(0, dtype=float)
+        y = np.asarray(self.predictor.predict(list(strucs), batch_size=self.batch_size), dtype=float).reshape(len(strucs), -1)
+        return y[:, self.col].copy()
+
+
 class PyMatGen:
     """The composition / cell properties of rewards/calculators/pymatgen/calc.py:163-205 that need no external database:
     `density` (g/cm^3, :45-53).  `hhi` (:57-73) is the mass-fraction-weighted Herfindahl-Hirschman index of the elements'
