@@ -294,10 +294,21 @@ SCALAR_SIGNATURES = {
     "mi_scalar_read": (_I, [_P, _I, _P, _P, _P]),
 }
 
+# the steering extension, include/matinvent_hip_steer.h (the noise-aware predictor's two entries and the particle resampling)
+STEER_MODE_MAX, STEER_MODE_MIN, STEER_MODE_TARGET = 0, 1, 2   # include/matinvent_hip_steer.h
+STEER_MAX_PARTICLES, STEER_DRAW, STEER_NSTATS = 256, 29, 3
+
+STEER_SIGNATURES = {
+    "mi_scalar_micro_step_noised": (_I, [_P, _P, _P, _P, _P, _P, _P, C.POINTER(_I), _P, _P, _I, _U64, _U32, _P, _P, _P, _P, _P, _I, _P, _P, C.POINTER(_I),
+                                         _P, C.POINTER(_I), _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mi_scalar_forward_state": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "mi_steer_resample": (_I, [_P, _I, _P, _I, _I, _I, C.c_float, C.c_float, C.c_float, _U64, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, PRETRAIN_SIGNATURES)
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, PRETRAIN_SIGNATURES)
 
 _lib = None
 

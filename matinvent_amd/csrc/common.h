@@ -201,6 +201,7 @@ enum : uint32_t {
     DRAW_JUMP_L = 24, DRAW_JUMP_X = 25, DRAW_JUMP_T = 26,   // resampling jumps (resample.hip); step field = the level jumped TO
     DRAW_VISIT = 27,                                        // ... and the per-visit seed: counter (0, 0, 27, v) under the chain's seed
     DRAW_COND_DROP = 28,                                    // condition dropout of the supervised micro-step (guidance.hip): one uniform per crystal
+    DRAW_STEER = 29,                                        // particle resampling (steer.hip): one uniform per group; step field = the level, element = the group's first crystal
 };
 
 }  // namespace mi

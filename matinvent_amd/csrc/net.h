@@ -262,6 +262,10 @@ struct mi_batch {
     float* sc_in = nullptr;                           // in_lat [B][9] | in_frac [N][3] | in_types [N][100]
     float *sc_gf = nullptr, *sc_dout = nullptr, *sc_parts = nullptr;   // [B][H], [B][sc_P], [B][sc_P][3] = e^2, |e|, present
     int sc_P = 0, sc_last_P = 0;                      // the per-property buffers' capacity; the P of the last call (their layout)
+    // predictor-steered sampling (steer.hip, include/matinvent_hip_steer.h; allocated on first use): the noised micro-step's schedule
+    // rows and -- forward-only form, which prepares no tape -- the noising's three by-products; the resampling's per-group flags and ESS
+    float *st_sched = nullptr, *st_noise = nullptr;   // [B][4]; tar_x [N][3] | rnd_l [B][9] | rnd_t [N][100]
+    float* st_parts = nullptr;                        // [B][2] = (flags, ESS) of group g in row g (B rows: room for K = 1)
     mi_pool* pool = nullptr;
     std::vector<int> edge_off_h, pair_off_h;
     int* edge_off = nullptr;   // [B + 1] first edge of each crystal (pooled handles only)
@@ -284,6 +288,22 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
                  const float* dgf_seed = nullptr);
 // scalar_head.hip: that broadcast (one launch), and the trunk's forward alone -- net_forward(trunk_only) ends behind the final LayerNorm, b->hf
 int scalar_seed_hf(const mi_batch* b, const float* dgf, float* dhf, int H, hipStream_t s);
+// scalar_head.hip: the body of the predictor's entries with the INPUT STAGE passed in (steer.hip: the noised micro-step, the forward on a
+// chain state).  The stage runs behind every host-side check and the buffers' allocation; it fills b->temb [B][TD] and either writes the
+// network inputs into w_lat / w_frac / w_types (the tape's noised-input arrays when `train`, the handle's sc_in otherwise) or -- a stage
+// that reads the caller's arrays, own_inputs: nothing is allocated for it, the three w_* are NULL -- points in_* at them.  stage == NULL:
+// the clean inputs of (lengths, angles, frac0, atom_types) at `times` / t_all, as ever.
+struct ScalarStageIO {
+    float *w_lat, *w_frac, *w_types;
+    const float *in_lat, *in_frac, *in_types;
+    bool train;
+};
+typedef int (*scalar_input_stage_fn)(mi_net* net, mi_batch* b, ScalarStageIO* io, void* ctx, hipStream_t s);
+int scalar_run(const char* what, mi_net* net, mi_batch* b, const float* lengths, const float* angles, const float* frac0, const int* atom_types,
+               const float* time_freqs, const int* times, int t_all, const float* W, const float* bias, int P, const float* yhat, const int* have,
+               const int* have_host, const int* count_global, const int* count_global_host, int accum_steps, int loss_kind, float* grad_theta,
+               float* grad_W, float* grad_bias, float* stats, float* out, void* stream, scalar_input_stage_fn stage = nullptr,
+               void* stage_ctx = nullptr, bool own_inputs = false);
 // backward.hip: the fine-tune micro-step's sequence -- time fill and embedding, add_noise_kernel (draw ids 7-9 at call `noise_step`, or the
 // injected noise), the agent's training forward, the frozen prior's forward (forked onto aux_stream when given), the LOSS STAGE, net_backward
 // into grad_theta -- with the loss stage passed in: it reads both networks' predictions and the targets, writes the three gradient seeds

@@ -210,11 +210,11 @@ static int scalar_buffers(mi_batch* b, int P, bool forward_only) {
     return MI_OK;
 }
 
-// the body of the two entries: `what` names the entry in the messages
-static int scalar_run(const char* what, mi_net* net, mi_batch* b, const float* lengths, const float* angles, const float* frac0, const int* atom_types,
-                      const float* time_freqs, const int* times, int t_all, const float* W, const float* bias, int P, const float* yhat, const int* have,
-                      const int* have_host, const int* count_global, const int* count_global_host, int accum_steps, int loss_kind, float* grad_theta,
-                      float* grad_W, float* grad_bias, float* stats, float* out, void* stream) {
+// the body of the entries (net.h): `what` names the entry in the messages, `stage` replaces the clean-input launch
+int scalar_run(const char* what, mi_net* net, mi_batch* b, const float* lengths, const float* angles, const float* frac0, const int* atom_types,
+               const float* time_freqs, const int* times, int t_all, const float* W, const float* bias, int P, const float* yhat, const int* have,
+               const int* have_host, const int* count_global, const int* count_global_host, int accum_steps, int loss_kind, float* grad_theta,
+               float* grad_W, float* grad_bias, float* stats, float* out, void* stream, scalar_input_stage_fn stage, void* stage_ctx, bool own_inputs) {
     MI_CHECK(!b || !b->pool || pool_stream(b->pool) == (hipStream_t)stream, MI_EINVAL, "%s: a pooled batch handle is used on its pool's stream only", what);
     MI_CHECK(net && b, MI_EINVAL, "null handle");
     MI_CHECK(b->H == net->H && b->L == net->L, MI_EINVAL, "batch was created for a different network");
@@ -243,21 +243,32 @@ static int scalar_run(const char* what, mi_net* net, mi_batch* b, const float* l
                      count_global_host[p], own);
         }
     if (B == 0 || N == 0) return MI_OK;
-    MI_CHECK(lengths && angles && frac0 && atom_types && time_freqs && W && bias, MI_EINVAL, "null argument");
+    MI_CHECK((stage || (lengths && angles && frac0 && atom_types)) && time_freqs && W && bias, MI_EINVAL, "null argument");
     MI_CHECK(!grad_theta || net->W2T != nullptr, MI_ESTATE, "mi_net_set_params must run before backward");
     TraceRange range(what);
     hipStream_t s = (hipStream_t)stream;
     const bool train = grad_theta != nullptr;
     if (train) MI_TRY(net_tape_prepare(net, b));
-    MI_TRY(scalar_buffers(b, P, !train));
+    MI_TRY(scalar_buffers(b, P, !train && !own_inputs));
     Tape& tp = b->tape;
-    float* const in_lat = train ? tp.nz_lat : b->sc_in;
-    float* const in_frac = train ? tp.nz_frac : b->sc_in + (size_t)B * 9;
-    float* const in_types = train ? tp.nz_types : b->sc_in + (size_t)B * 9 + (size_t)N * 3;
-
-    ScalarInputArgs ia{lengths, angles, frac0, atom_types, b->node_off, time_freqs, times, t_all, net->TD, in_lat, in_frac, in_types, b->temb};
-    hipLaunchKernelGGL(scalar_inputs_kernel, dim3(B), dim3(256), 0, s, ia);
-    MI_KERNEL_CHECK();
+    ScalarStageIO io{};
+    io.train = train;
+    if (!own_inputs) {
+        io.w_lat = train ? tp.nz_lat : b->sc_in;
+        io.w_frac = train ? tp.nz_frac : b->sc_in + (size_t)B * 9;
+        io.w_types = train ? tp.nz_types : b->sc_in + (size_t)B * 9 + (size_t)N * 3;
+    }
+    io.in_lat = io.w_lat;
+    io.in_frac = io.w_frac;
+    io.in_types = io.w_types;
+    if (stage) {
+        MI_TRY(stage(net, b, &io, stage_ctx, s));
+    } else {
+        ScalarInputArgs ia{lengths, angles, frac0, atom_types, b->node_off, time_freqs, times, t_all, net->TD, io.w_lat, io.w_frac, io.w_types, b->temb};
+        hipLaunchKernelGGL(scalar_inputs_kernel, dim3(B), dim3(256), 0, s, ia);
+        MI_KERNEL_CHECK();
+    }
+    const float *in_lat = io.in_lat, *in_frac = io.in_frac, *in_types = io.in_types;
     if (train) {
         tp.borrow_inputs = true;   // (the inputs live in this tape and the time embedding in this batch until the backward below has run)
         const int rc = net_forward(net, b, b->temb, in_types, in_frac, in_lat, nullptr, nullptr, nullptr, s, true, false, false, true);

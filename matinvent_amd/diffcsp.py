@@ -466,7 +466,7 @@ class DiffCSPModule(nn.Module):
     @torch.no_grad()
     def sample(self, batch, diff_ratio=1.0, step_lr=1e-5, seed=0, noise=None, init=None, record=False, t_start=None,
                t_stop=0, node_offset=0, graph_offset=0, streams=None, rec_sink=None, condition=None, likelihood=None, resample=None,
-               guidance=None):
+               guidance=None, steer=None):
         """DiffCSPModule.sample (diffusion.py:273-399).
 
         `rec_sink` (a list; with record=True): receives one (first crystal, first atom, buffers) per chain, in crystal order -- the
@@ -506,7 +506,23 @@ class DiffCSPModule(nn.Module):
         like a condition; each stream group gets its crystals' slice.  Without it a property-conditioned module samples under the null
         row.  ValueError before any device work: a module without a property part, an unknown property, record=True, `condition`,
         `likelihood`, `resample`, CSP mode.
+
+        `steer` = steering.Steering(predictor, task, ...): predictor-steered sampling.  `batch` holds K-replicated atom counts
+        (Steering.replicate); the chain is walked as segments between the steering levels, and at each level the noise-aware predictor
+        scores the particles' states and each group of K is resampled on the device -- one chain on one stream, nothing read inside it.
+        Returns (final, traj, info): info = dict(levels, times, ancestors [E][B], stats [E][3]) from one read at the end.  On a view the
+        levels are step indices and the predictor is given their trained times.  ValueError by name before any device work: a predictor
+        that is not noised or of another T / schedule, atom counts that are not K-replicated, streams > 1, `record`, `noise`,
+        `condition`, `likelihood`, `resample`, `guidance`, CSP mode.
         """
+        if steer is not None:
+            from . import steering
+            steering.check_call(self, steer, streams=streams, record=record, noise=noise, condition=condition, likelihood=likelihood,
+                                resample=resample, guidance=guidance)
+            steer.check_counts(batch.num_atoms_list if isinstance(batch, CrystalBatch) else batch.num_atoms)
+            if self.__dict__.get("_knn_pending"):
+                self.check_graph()
+            return steering.run_chain(self, batch, steer, step_lr, seed, init, t_start, t_stop, node_offset, graph_offset)
         from .conditioning import check_likelihood
         from .resampling import check_chain
         gd = None

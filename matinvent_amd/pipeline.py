@@ -239,6 +239,8 @@ class MatInventPG(MatInvent):
                                  "of the unconditioned proposal, not a trajectory likelihood (use pipeline=mat_invent)")
         from .resampling import refuse
         refuse("MatInventPG", **{f"sample_cfg.{k}": merged.get(k) for k in ("resample_times", "jump_length")})
+        from .steering import refuse as refuse_steer
+        refuse_steer("MatInventPG", **{"sample_cfg.steer": merged.get("steer")})   # 
         if kwargs.get("div_filter"):
             raise ValueError("MatInventPG: div_filter=True is not built -- the diversity filter penalises the rewards that rank a top-k, and the "
                              "policy gradient has no top-k (use pipeline=mat_invent)")

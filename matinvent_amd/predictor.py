@@ -102,6 +102,13 @@ class PropertyPredictor(nn.Module):
         return self.trunk.hidden_dim
 
     @property
+    def noised(self):
+        """None: a predictor of clean inputs at time 0 (every predictor saved before DESIGN 43).  A dict (noised_spec: T and the schedules'
+        defining parameters): trained by fit_predictor(diffusion=) on forward-noised inputs at drawn times 0..T of that schedule -- what
+        steering.Steering and every other caller that needs a noise-aware predictor ask for by name (require_noised)."""
+        return self.hparams.get("noised")
+
+    @property
     def device(self):
         return self.flat.device
 
@@ -287,6 +294,139 @@ def forward(model, batch, handle=None, pool=None, t_all=0, times=None):
     return out
 
 
+# ---- the noise-aware predictor (include/matinvent_hip_steer.h) ------------------------------------------------------------------
+_NOISED_TIME_TAG = 0x6E74696D   # (draw_noised_times' generator shares a key with no other)
+
+
+def noised_spec(diffusion):
+    """What a noise-aware predictor records of the diffusion module it was trained under: T and the scalar constructor arguments of the
+    two schedulers (of the module of the trained grid: a respaced view gives its base's)."""
+    base = diffusion.base if getattr(diffusion, "base", None) is not None else diffusion
+    if hasattr(base, "collate") or not hasattr(base, "beta_scheduler"):
+        raise ValueError("a noise-aware predictor is trained under a DiffCSPModule (the MatterGen-shaped module has no such schedule here)")
+    scal = lambda d: {str(k): (v if isinstance(v, (bool, int, str)) else float(v)) for k, v in dict(d).items()
+                      if not str(k).startswith("_") and isinstance(v, (bool, int, float, str))}
+    return dict(T=int(base.beta_scheduler.timesteps), beta_scheduler=scal(base.hparams["beta_scheduler"]),
+                sigma_scheduler=scal(base.hparams["sigma_scheduler"]))
+
+
+def require_noised(model, where, diffusion=None):
+    """ValueError by name unless `model` is a noise-aware predictor -- and, with `diffusion`, one of that module's T and schedule."""
+    spec = getattr(model, "noised", None)
+    if spec is None:
+        raise ValueError(f"{where}: the predictor is not noised (PropertyPredictor.noised is None: it was trained on clean inputs at time 0; "
+                         "train one with fit_predictor(..., diffusion=module))")
+    if diffusion is not None:
+        want = noised_spec(diffusion)
+        if int(spec.get("T", -1)) != want["T"]:
+            raise ValueError(f"{where}: the predictor was trained with T = {spec.get('T')}, the module has T = {want['T']}")
+        if dict(spec) != want:
+            raise ValueError(f"{where}: the predictor's schedule {dict(spec)} differs from the module's {want}")
+    return spec
+
+
+def draw_noised_times(B, T, epoch, step, seed):
+    """[B] int32 times, uniform in 0..T (0: the clean row -- a predictor that steers a chain is also asked at its end), from a numpy
+    Generator keyed by (seed, epoch, step)."""
+    return np.random.default_rng([_NOISED_TIME_TAG, int(seed), int(epoch), int(step)]).integers(0, int(T) + 1, size=int(B)).astype(np.int32)
+
+
+def train_step_noised(model, batch, times, diffusion, y=None, noise=None, grad=None, stats=None, count_global=None, accum_steps=1, loss="mse",
+                      forward_only=False, out=None, pool=None, offsets=(0, 0), yhat=None, have=None, handle=None, seed=0, call_id=None):
+    """train_step on FORWARD-NOISED inputs (mi_scalar_micro_step_noised): crystal c at times[c] in 0..T of `diffusion`'s schedule (its
+    pretrain.schedule_table; a respaced view gives its base's), noised by Philox draws 7-9 at `call_id` (default: the model's running
+    counter, advanced) under `seed`, indexed through `offsets` -- or by the injected noise = (rand_l [B][9], rand_x [N][3], rand_t [N][100]).
+    Everything else is train_step's."""
+    if loss not in LOSS_KINDS:
+        raise ValueError(f"train_step_noised: loss = {loss!r}: it takes 'mse' or 'l1'")
+    from .pretrain import schedule_table
+    base = diffusion.base if getattr(diffusion, "base", None) is not None else diffusion
+    noised_spec(base)
+    T = int(base.beta_scheduler.timesteps)
+    lib = _lib.load()
+    from .cspnet import _ptr, _stream
+    dev = model.device
+    na = _counts(batch)
+    B, P = len(na), model.P
+    th = np.ascontiguousarray(np.asarray(times.cpu() if torch.is_tensor(times) else times), dtype=np.int32).reshape(-1)
+    if th.shape[0] != B:
+        raise ValueError(f"train_step_noised: {th.shape[0]} times for {B} crystals")
+    if B and (int(th.min()) < 0 or int(th.max()) > T):
+        raise ValueError(f"train_step_noised: times must lie in 0..{T} (got {int(th.min())}..{int(th.max())})")
+    if yhat is None:
+        if y is None:
+            raise ValueError("train_step_noised: no targets (y, or yhat and have)")
+        ya = np.asarray(y.cpu() if torch.is_tensor(y) else y, dtype=np.float64)
+        if ya.size != B * P:
+            raise ValueError(f"train_step_noised: y holds {ya.size} values for {B} crystals x {P} properties")
+        yhat, have = model.normalizer.normalise(ya)
+    yhat = np.ascontiguousarray(np.asarray(yhat, dtype=np.float32).reshape(B, P))
+    have = np.ascontiguousarray(np.asarray(have, dtype=np.int32).reshape(B, P))
+    cg = have.sum(axis=0) if count_global is None else np.asarray(count_global)
+    cg = np.ascontiguousarray(cg.reshape(P), dtype=np.int32)
+    if stats is None:
+        stats = torch.zeros(stats_len(P), device=dev)
+    if not forward_only and grad is None:
+        if model.flat.grad is None:
+            model.flat.grad = torch.zeros_like(model.flat)
+        grad = model.flat.grad
+    if call_id is None:
+        model.__dict__["_noise_calls"] = model.__dict__.get("_noise_calls", 0) + 1
+        call_id = model.__dict__["_noise_calls"]
+    if B == 0:
+        return stats
+    f = lambda x: x.to(dev, torch.float32).contiguous()
+    lengths, angles, frac0 = f(batch.lengths).view(-1, 3), f(batch.angles).view(-1, 3), f(batch.frac_coords)
+    at = batch.atom_types.to(dev, torch.int32).contiguous()
+    up = (lambda a: torch.from_numpy(a).to(dev)) if pool is None else (lambda a: torch.from_numpy(a).pin_memory().to(dev, non_blocking=True))
+    yhat_d, have_d, cg_d, t_dev = up(yhat), up(have), up(cg), up(th)
+    nz = (None, None, None) if noise is None else tuple(None if x is None else f(x) for x in noise)
+    table = schedule_table(base).to(dev)
+    model.trunk.sync()
+    _, W, bias = model.head_slices()
+    g = (None, None, None) if forward_only else model.head_slices(grad)
+    cb = handle if handle is not None else model.make_batch(na, int(offsets[0]), int(offsets[1]), pool=pool)
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    try:
+        _lib.check(lib.mi_scalar_micro_step_noised(model.trunk._h, cb._h, _ptr(lengths), _ptr(angles), _ptr(frac0), _ptr(at), _ptr(model.time_freqs), ip(th),
+                                                   _ptr(t_dev), _ptr(table), T, int(seed), int(call_id) & 0xFFFFFFFF, _ptr(nz[0]), _ptr(nz[1]), _ptr(nz[2]),
+                                                   _ptr(W), _ptr(bias), P, _ptr(yhat_d), _ptr(have_d), ip(have), _ptr(cg_d), ip(cg), int(accum_steps),
+                                                   LOSS_KINDS[loss], _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(stats), _ptr(out), _stream()),
+                   "mi_scalar_micro_step_noised")
+    finally:
+        if handle is None:
+            if pool is None:
+                torch.cuda.current_stream().synchronize()
+            cb.release()
+    return stats
+
+
+def forward_state(model, state, handle, t, out=None):
+    """The normalised predictions [B][P] (device) of a chain STATE on the current stream (mi_scalar_forward_state): state = a dict with
+    atom_types [N][100] float rows, frac_coords [N][3], lattices [B][3][3] (a chain's arrays, read where they are and left unchanged) or
+    the tuple (frac_coords, lattices, atom_types) of sample(init=); handle: a batch handle of THIS model (model.make_batch) with the
+    state's atom counts -- never the chain's; t: the trained time, one int for all or [B] ints.  No host synchronisation."""
+    lib = _lib.load()
+    from .cspnet import _ptr, _stream
+    dev = model.device
+    x, l, a = (state["frac_coords"], state["lattices"], state["atom_types"]) if isinstance(state, dict) else state
+    B, N, P = handle.num_graphs, handle.num_nodes, model.P
+    f = lambda v: v.to(dev, torch.float32).contiguous()
+    x, l, a = f(x), f(l), f(a)
+    if a.numel() != N * _lib.NUM_TYPES or x.numel() != N * 3 or l.numel() != B * 9:
+        raise ValueError(f"forward_state: the state's shapes {tuple(a.shape)}, {tuple(x.shape)}, {tuple(l.shape)} are not the handle's {N} atoms in {B} crystals")
+    tm, t_all = (None, int(t)) if isinstance(t, (int, np.integer)) else (_times(t, B, dev), 0)
+    if out is None:
+        out = torch.empty(B, P, device=dev)
+    if B == 0:
+        return out
+    model.trunk.sync()
+    _, W, bias = model.head_slices()
+    _lib.check(lib.mi_scalar_forward_state(model.trunk._h, handle._h, _ptr(a), _ptr(x), _ptr(l), _ptr(model.time_freqs), _ptr(tm), t_all, _ptr(W),
+                                           _ptr(bias), P, _ptr(out), _stream()), "mi_scalar_forward_state")
+    return out
+
+
 def predict(model, records_or_batch, batch_size=64, pool=None):
     """De-normalised predictions, np.ndarray [n][P] float64, of a list of records (CrystalData, structures, read_extxyz frames) or of a
     CrystalBatchData.  A crystal that cannot be evaluated -- no atoms, an atomic number outside 1..100, a non-finite value, an atom count
@@ -331,15 +471,28 @@ def predict(model, records_or_batch, batch_size=64, pool=None):
     return out
 
 
-def _eval_enqueue(model, data_list, batch_size, acc, loss="mse", pool=None):
-    """`evaluate` without the read-back: every mini-batch of the set in order, forward-only, normalised by the counts of the WHOLE set."""
+EVAL_CALL = 0   # the Philox call id of a noised evaluation (noised training counts from 1)
+
+
+def _eval_enqueue(model, data_list, batch_size, acc, loss="mse", pool=None, diffusion=None, t=None, seed=0):
+    """`evaluate` without the read-back: every mini-batch of the set in order, forward-only, normalised by the counts of the WHOLE set.
+    diffusion: the noised form -- every crystal at time `t`, or (t None) at times drawn under (seed, epoch 0, mini-batch index): the same
+    noised validation set every epoch."""
     from .data import CrystalBatchData
     from .pretrain import batch_plan
     yh, hv = model.normalizer(data_list)
     cg = hv.sum(axis=0)
-    for idx in batch_plan(len(data_list), batch_size, 0, 0, shuffle=False):
-        train_step(model, CrystalBatchData([data_list[i] for i in idx]), yhat=yh[idx], have=hv[idx], stats=acc, count_global=cg, loss=loss,
-                   forward_only=True, pool=pool)
+    n0 = 0
+    for step, idx in enumerate(batch_plan(len(data_list), batch_size, 0, 0, shuffle=False)):
+        b = CrystalBatchData([data_list[i] for i in idx])
+        if diffusion is None:
+            train_step(model, b, yhat=yh[idx], have=hv[idx], stats=acc, count_global=cg, loss=loss, forward_only=True, pool=pool)
+        else:
+            T = noised_spec(diffusion)["T"]
+            tm = np.full(len(idx), int(t), np.int32) if t is not None else draw_noised_times(len(idx), T, 0, step, seed)
+            train_step_noised(model, b, tm, diffusion, yhat=yh[idx], have=hv[idx], stats=acc, count_global=cg, loss=loss, forward_only=True, pool=pool,
+                              seed=seed, call_id=EVAL_CALL, offsets=(n0, step * int(batch_size)))
+            n0 += sum(_counts(b))
     return acc
 
 
@@ -354,18 +507,29 @@ def _metrics(model, a):
     return out
 
 
-def evaluate(model, data_list, batch_size, pool=None):
+def evaluate(model, data_list, batch_size, pool=None, t=None, diffusion=None, seed=0):
     """Per property: mean squared and mean absolute error over the set's present targets, in normalised units (mse, mae) and in the
     property's own (mse_raw, mae_raw), and the count.  Forward-only; mini-batches are weighted by their counts, so the result does not
-    depend on batch_size beyond fp32 summation order.  One host read."""
+    depend on batch_size beyond fp32 summation order.  One host read.
+    t (with `diffusion`, the module a noise-aware predictor was trained under): the error at that fixed time 0..T, on inputs noised under
+    `seed`; a predictor that is not noised, or one of another schedule, is refused by name."""
     if int(batch_size) < 1:
         raise ValueError(f"evaluate: batch_size = {batch_size}: must be >= 1")
     if len(data_list) == 0:
         raise ValueError("evaluate: an empty set")
+    if t is not None:
+        if diffusion is None:
+            raise ValueError("evaluate: t = needs diffusion = the module whose schedule noises the inputs")
+        T = require_noised(model, "evaluate(t=)", diffusion)["T"]
+        if not 0 <= int(t) <= T:
+            raise ValueError(f"evaluate: t = {t} lies outside 0..{T}")
+    elif diffusion is not None:
+        raise ValueError("evaluate: diffusion = without t = (the time the error is taken at)")
     was_training = model.training
     model.eval()
     try:
-        acc = _eval_enqueue(model, data_list, batch_size, torch.zeros(stats_len(model.P), device=model.device), pool=pool)
+        acc = _eval_enqueue(model, data_list, batch_size, torch.zeros(stats_len(model.P), device=model.device), pool=pool, diffusion=diffusion, t=t,
+                            seed=seed)
     finally:
         model.train(was_training)
     return _metrics(model, acc.tolist())
@@ -378,12 +542,16 @@ def _refuse_world(where):
         raise ValueError(f"{where}: world size {world}: the predictor trains on one GPU only (data-parallel fit_predictor is out of scope)")
 
 
-def fit_predictor(model, data_list, cfg, val_list=None, seed=0, log=logging.info, on_epoch_end=None):
+def fit_predictor(model, data_list, cfg, val_list=None, seed=0, log=logging.info, on_epoch_end=None, diffusion=None):
     """Train `model` on `data_list` (CrystalData records carrying `properties`).  cfg (key or attribute access): lr, epochs, batch_size;
     accum_steps (default 1); shuffle (default true); loss = "mse" (default) or "l1"; max_grad_norm / skip_nonfinite_steps; lr_plateau;
     handle_pool; ema -- all as pretrain.fit reads them, and with its machinery: epochs of pretrain.batch_plan mini-batches (the only random
     thing, a function of (seed, epoch)), one FusedAdam on the flat vector, one host read per epoch.  The normaliser is fitted on the
     training set first.  With ema the optimizer is left in model.fit_optimizer (ema_weights(model) to predict or save the average).
+    diffusion (a DiffCSPModule): the NOISE-AWARE predictor -- every crystal of every mini-batch is forward-noised at one time
+    drawn uniformly in 0..T, a function of (seed, epoch, step) (draw_noised_times), under the module's schedule tables; the noise is Philox
+    draws 7-9 under `seed` at a call id that counts the micro-steps from 1; the validation set is noised the same way every epoch.  T and
+    the schedule's parameters are recorded in model.hparams["noised"] (saved and loaded with the model).
     One GPU only: a world size above 1 is a ValueError.  Returns the per-epoch dicts: train_loss, train_mse_<name>, with a validation set
     val_loss and val_mse_<name> / val_mae_<name> (normalised units), lr, the optimizer's statistics."""
     _refuse_world("fit_predictor")
@@ -417,6 +585,13 @@ def fit_predictor(model, data_list, cfg, val_list=None, seed=0, log=logging.info
     if not np.isfinite(nm.raw(data_list)).any():
         raise ValueError(f"fit_predictor: no training crystal carries any of the properties {model.names} (CrystalData.properties)")
     model.set_normalizer(nm)
+    T_noise = None
+    if diffusion is None:
+        model.hparams.pop("noised", None)   # (trained on clean inputs from here on: no longer a noise-aware predictor)
+    else:
+        model.hparams["noised"] = noised_spec(diffusion)
+        T_noise = model.hparams["noised"]["T"]
+        calls = 0
     if ema is not None:
         opt = dict(opt, ema_decay=ema["decay"], ema_warmup=ema["warmup"])
     flat = model.flat
@@ -437,14 +612,21 @@ def fit_predictor(model, data_list, cfg, val_list=None, seed=0, log=logging.info
             acc = torch.zeros(stats_len(P), device=dev)
             plan = batch_plan(n, batch_size, epoch, seed, shuffle)
             for step, idx in enumerate(plan):
-                train_step(model, CrystalBatchData([data_list[i] for i in idx]), yhat=yh[idx], have=hv[idx], grad=flat.grad, stats=acc,
-                           accum_steps=accum, loss=loss, pool=pool)
+                if diffusion is None:
+                    train_step(model, CrystalBatchData([data_list[i] for i in idx]), yhat=yh[idx], have=hv[idx], grad=flat.grad, stats=acc,
+                               accum_steps=accum, loss=loss, pool=pool)
+                else:
+                    calls += 1
+                    train_step_noised(model, CrystalBatchData([data_list[i] for i in idx]), draw_noised_times(len(idx), T_noise, epoch, step, seed),
+                                      diffusion, yhat=yh[idx], have=hv[idx], grad=flat.grad, stats=acc, accum_steps=accum, loss=loss, pool=pool,
+                                      seed=seed, call_id=calls)
                 if window_closes(step + 1, accum, len(plan)):
                     optimizer.step()
                     optimizer.zero_grad(set_to_none=False)
             if val_list is not None:
                 with optimizer.ema_weights(model) if ema is not None and ema["validate"] else contextlib.nullcontext():
-                    acc = torch.cat([acc, _eval_enqueue(model, val_list, batch_size, torch.zeros(stats_len(P), device=dev), loss=loss, pool=pool)])
+                    acc = torch.cat([acc, _eval_enqueue(model, val_list, batch_size, torch.zeros(stats_len(P), device=dev), loss=loss, pool=pool,
+                                                          diffusion=diffusion, seed=seed)])
             k_ema = None
             if ema is not None and optimizer.guarded:
                 k_ema = acc.numel()
@@ -487,6 +669,8 @@ def write_hparams(save_dir, hparams, normalizer):
     os.makedirs(save_dir, exist_ok=True)
     hp = {k: hparams[k] for k in HPARAM_KEYS}
     hp.update(mean=[float(x) for x in normalizer.mean], std=[float(x) for x in normalizer.std])
+    if hparams.get("noised") is not None:   # (a noise-aware predictor; a directory without the entry loads with noised = None)
+        hp["noised"] = hparams["noised"]
     CFG.save(CFG.create({"predictor": hp}), os.path.join(save_dir, HPARAMS_FILE))
 
 
@@ -518,6 +702,9 @@ def load_predictor(model_dir, device=None, names=None):
     hp = read_hparams(model_dir, names)
     nm = PropertyNormalizer(hp["names"], hp.get("mean"), hp.get("std"))
     model = PropertyPredictor(normalizer=nm, device=device, **{k: hp[k] for k in HPARAM_KEYS})
+    if hp.get("noised") is not None:
+        nz = dict(hp["noised"])
+        model.hparams["noised"] = dict(T=int(nz["T"]), beta_scheduler=dict(nz.get("beta_scheduler") or {}), sigma_scheduler=dict(nz.get("sigma_scheduler") or {}))
     ck = torch.load(os.path.join(str(model_dir), WEIGHTS_FILE), map_location="cpu", weights_only=False)
     model.load_state_dict(ck["state_dict"])
     return model

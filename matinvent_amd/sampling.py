@@ -42,7 +42,7 @@ class DiffCSPSampler:
     seed: int = 0
 
     def generate(self, model, batch_size=None, num_batches=None, sample_steps=None, condition=None, target_compositions_dict=None,
-                 resample_times=None, jump_length=None, properties_to_condition_on=None, diffusion_guidance_factor=None,
+                 resample_times=None, jump_length=None, properties_to_condition_on=None, diffusion_guidance_factor=None, steer=None,
                  **kwargs) -> Tuple[List[CrystalData], list]:
         """sample.py:148-201.  Extra kwargs (`max_num`, `filter`, ...) are tolerated like the reference.
         `sample_steps` = S: the chains run on S of the model's T trained steps (model.respaced(S)); None: all of them.
@@ -58,7 +58,11 @@ class DiffCSPSampler:
         resampling jumps; both or neither, and only with a condition (ValueError).  Levels are step indices under `sample_steps`.
         `properties_to_condition_on` = {name: value} with `diffusion_guidance_factor` = gamma (default 0; DiffCSPModule.sample's
         `guidance`): every crystal is sampled under these property values by a property-conditioned model, with classifier-free guidance
-        of that factor.  ValueError: a factor without properties, either together with a condition."""
+        of that factor.  ValueError: a factor without properties, either together with a condition.
+        `steer` (DiffCSPModule.sample's `steer`): a steering.Steering, or the mapping of sample_cfg.steer (Steering.from_config).
+        The batch_size crystals become the groups: every drawn atom count is replicated K times and G K records come back; the events'
+        ancestors and statistics of the last batch are left in `self.last_steer`.  ValueError: together with a condition, resampling,
+        guidance, or more than one rank."""
         batch_size = batch_size or self.batch_size
         num_batches = num_batches or self.num_batches
         assert batch_size is not None and num_batches is not None
@@ -87,6 +91,13 @@ class DiffCSPSampler:
         elif diffusion_guidance_factor:
             raise ValueError("DiffCSPSampler.generate: diffusion_guidance_factor needs properties_to_condition_on")
         rank, world = int(kwargs.get("rank", 0)), int(kwargs.get("world_size", 1))
+        if steer is not None:
+            from .steering import Steering
+            for name, v in (("a condition", condition is not None), ("resample_times", resample is not None),
+                            ("properties_to_condition_on", guide is not None), (f"world_size = {world}", world > 1)):
+                if v:
+                    raise ValueError(f"DiffCSPSampler.generate: steer together with {name} is not supported")
+            steer = Steering.from_config(steer, device=getattr(model, "device", None))
         model = _strided(model, sample_steps)
         model.eval()
         from .dist import collectives_on
@@ -108,7 +119,10 @@ class DiffCSPSampler:
             lo, hi = shard_range(len(na), rank, world)
             node_off = int(np.sum(na[:lo]))
             self.seed += 1
-            counts = _AtomCounts(na[lo:hi])
+            counts = _AtomCounts(na[lo:hi] if steer is None else np.asarray(steer.replicate(na[lo:hi])))
+            if steer is not None:
+                outputs, _, self.last_steer = model.sample(counts, step_lr=step_lr, seed=self.seed, node_offset=node_off, graph_offset=lo, steer=steer)
+                continue
             cond = None
             if condition is not None:
                 c0 = bi * batch_size % len(condition)
@@ -184,7 +198,7 @@ def _refuse_condition(where, condition):
                          "unconditioned proposal, not a trajectory likelihood (DESIGN 31)")
 
 
-def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_steps=None, condition=None, resample=None):
+def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_steps=None, condition=None, resample=None, steer=None):
     """sample.py:249-309: sample with the trajectory recorded and return (sample_list, sample_traj), restricted to the crystals that
     pass invalid_filter.  sample_traj[k] is the step t = T - k (t = T .. 2) with the reference's keys (atom_types, lattices, frac_coords,
     frac_coords_mid, num_atoms, timesteps, log_prob_{t,x,l}; host tensors) plus next_frac_coords / next_lattices / next_atom_types --
@@ -195,6 +209,8 @@ def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_st
     from .filters import invalid_filter
     from .resampling import refuse
     refuse("sample_mdp", resample=resample)
+    from .steering import refuse as refuse_steer
+    refuse_steer("sample_mdp", steer=steer)   # (a resampled particle system has no per-chain trajectory likelihood)
     from .guidance import refuse_latent
     refuse_latent(model, "sample_mdp")
     _refuse_condition("sample_mdp", condition)
@@ -269,7 +285,7 @@ class Rollout:
 
 
 def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=True, sample_steps=None, condition=None, likelihood=None,
-                   resample=None):
+                   resample=None, steer=None):
     """Sample like sample_mdp (same atom-count draw, seed handling and invalid_filter; geometric_filter=False keeps every crystal) and
     keep the kept crystals' whole trajectories on the device as a Rollout -- compacted once per chain straight from the sampler's stacked
     record buffers, without the per-step dict or a host copy.  Returns (sample_list, rollout).  The policy gradient (policy.pg_step)
@@ -285,6 +301,8 @@ def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=T
     from .filters import invalid_filter
     from .resampling import refuse
     refuse("sample_rollout", resample=resample)
+    from .steering import refuse as refuse_steer
+    refuse_steer("sample_rollout", steer=steer)   # 
     from .guidance import refuse_latent
     refuse_latent(model, "sample_rollout")
     if not check_likelihood("sample_rollout", likelihood, condition):
