@@ -305,10 +305,19 @@ STEER_SIGNATURES = {
     "mi_steer_resample": (_I, [_P, _I, _P, _I, _I, _I, C.c_float, C.c_float, C.c_float, _U64, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
+# the classifier-guidance extension, include/matinvent_hip_inputgrad.h (the predictor's input gradient, the seed and the guided shift)
+GUIDE_MODE_MAX, GUIDE_MODE_MIN, GUIDE_MODE_TARGET = 0, 1, 2   # include/matinvent_hip_inputgrad.h
+
+INPUT_GRAD_SIGNATURES = {
+    "mi_scalar_input_grad": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "mi_guide_seed": (_I, [_P, _I, _I, _I, _I, C.c_float, _P, _P]),
+    "mi_guide_shift": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, STEER_SIGNATURES, PRETRAIN_SIGNATURES)
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, PRETRAIN_SIGNATURES)
 
 _lib = None
 

@@ -908,8 +908,13 @@ int net_wgrad_flush(mi_net* net, mi_batch* b, float* grad, hipStream_t s) {
 static inline dim3 g1(int64_t n) { return dim3((unsigned)cdiv(n, 256)); }
 
 int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_coord, const float* d_type, float* grad, hipStream_t s,
-                 const float* dgf_seed) {
+                 const float* dgf_seed, const InputGradOut* ig) {
     MI_CHECK(b->tape.allocated && b->tape.valid, MI_ESTATE, "mi_cspnet_backward without a preceding training forward on this batch");
+    // (ig -- input_grad.hip, DESIGN 44: the data-only form.  `grad` is NULL: every launch that contracts or reduces into it is skipped -- `wg`
+    //  below -- and the pass hands the pair operands, d G and the embedding's dXa to input_grad.hip's launches)
+    MI_CHECK(!ig || (dgf_seed && !grad && b->tape.wslots == 0), MI_ESTATE, "the input-gradient form is seeded from the graph features and takes no gradient buffer");
+    MI_CHECK(ig || grad, MI_EINVAL, "null argument");
+    const bool wg = ig == nullptr;
     // (dgf_seed -- scalar_head.hip: the pass starts from d gf alone, the three heads are not part of it; its entry refuses a deferred window)
     MI_CHECK(!dgf_seed || b->tape.wslots == 0, MI_ESTATE, "a backward seeded from the graph features runs without a weight-gradient window");
     const int H = net->H, L = net->L, N = b->N, B = b->B, TD = net->TD, F = net->F;
@@ -957,7 +962,7 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
         hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nblk), dim3(256), 8 * H * sizeof(float), s, dy, ld_dy, x, stats, net->p(wname + ".weight"),
                            dx, accumulate, sc, N, H, rows_per_block);
         // part[blk][0:H] -> dw, [H:2H] -> db ; weight and bias are adjacent in theta (weight first)
-        hipLaunchKernelGGL(part_reduce_kernel<>, dim3(cdiv(2 * H, PART_REDUCE_COLS)), dim3(256), 0, s, sc, nblk, 2 * H, G(wname + ".weight"), 2 * H);
+        if (wg) hipLaunchKernelGGL(part_reduce_kernel<>, dim3(cdiv(2 * H, PART_REDUCE_COLS)), dim3(256), 0, s, sc, nblk, 2 * H, G(wname + ".weight"), 2 * H);
         MI_KERNEL_CHECK();
         return MI_OK;
     };
@@ -971,6 +976,7 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
     // Fourier features are the same for every layer; in pair mode one row per unordered atom pair
     const bool pairs = g_edge_pairs && !b->knn && H % 4 == 0;
     const int64_t Np = b->Np;
+    MI_CHECK(!ig || pairs, MI_EINVAL, "the input-gradient form runs in the fully connected pair mode only");
     // (built by the first product that reads the fp32 rows: the plane-set form of the Fourier block's weight gradient -- the default at the benchmark size --
     //  reads the forward's pair-mode operand planes instead and never asks for them: one launch and 37 MB of writes fewer per micro-step)
     bool ff_built = false;
@@ -1025,7 +1031,7 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
         const float* Ypre = t.Ypre + (size_t)l * NH;
         // node MLP (cspnet.py:80-82)
         if (nb) {   // (dY, Xa, dXa of this layer and d cat were written by the chain launch above this layer's edge stage)
-            if (!defer) {
+            if (!defer && wg) {
                 MI_TRY(gemm_tn_auto(dYl, H, Xa, H, G(p + "node_mlp.2.weight"), H, N, H, H, sc, scf, s));
                 MI_TRY(colsum_acc(dYl, H, G(p + "node_mlp.2.bias"), N, H, sc, scf, s));
                 MI_TRY(gemm_tn_auto(dXa, H, cat, 2 * H, G(p + "node_mlp.0.weight"), 2 * H, N, H, 2 * H, sc, scf, s));
@@ -1035,7 +1041,7 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
         hipLaunchKernelGGL(silu_bwd_kernel, g1(NH), dim3(256), 0, s, dh, Ypre, dYl, (int64_t)NH);
         hipLaunchKernelGGL(silu_fwd_kernel, g1(NH), dim3(256), 0, s, Xpre, Xa, (int64_t)NH);
         MI_KERNEL_CHECK();
-        if (!defer) {
+        if (!defer && wg) {
             MI_TRY(gemm_tn_auto(dYl, H, Xa, H, G(p + "node_mlp.2.weight"), H, N, H, H, sc, scf, s));
             MI_TRY(colsum_acc(dYl, H, G(p + "node_mlp.2.bias"), N, H, sc, scf, s));
         }
@@ -1044,7 +1050,7 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
         // layout a lane owns one column of 16 rows, so the pre-activation comes in as 16 four-byte loads per tile)
         hipLaunchKernelGGL(silu_bwd_kernel, g1(NH), dim3(256), 0, s, dXa, Xpre, dXa, (int64_t)NH);
         MI_KERNEL_CHECK();
-        if (!defer) {
+        if (!defer && wg) {
             MI_TRY(gemm_tn_auto(dXa, H, cat, 2 * H, G(p + "node_mlp.0.weight"), 2 * H, N, H, 2 * H, sc, scf, s));
             MI_TRY(colsum_acc(dXa, H, G(p + "node_mlp.0.bias"), N, H, sc, scf, s));
         }
@@ -1075,15 +1081,17 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
             bool w2_planes = false;
 #if MI_PLANES_FP16
             const Planes m1l = t.M1pl_l ? make_planes(t.M1pl_l + (size_t)l * t.m1pl_stride, H, 1.f, t.dsc_layers + (size_t)l * 8) : Planes();
-            w2_planes = dz2_planes && t.dsc_layers_valid && g_bwd_wgrad_f16 && g_bwd_wgrad_planes && t.M1pl_l && g_tn_xsilu && gemm_tn_planes_ok(dzp, 0, m1l, 0, E, H, H);
+            w2_planes = wg && dz2_planes && t.dsc_layers_valid && g_bwd_wgrad_f16 && g_bwd_wgrad_planes && t.M1pl_l && g_tn_xsilu && gemm_tn_planes_ok(dzp, 0, m1l, 0, E, H, H);
 #endif
             if (dz2_sums) {
                 hipLaunchKernelGGL(edge_dz2_colsum_kernel, dim3(1, nchunk), dim3(256), 0, s, t.dcat, b->src, b->rowptr, Z2, sc, E, H, crows, dzp,
                                    am, b->dsc + 6, w2_planes ? 0 : 1);
-                hipLaunchKernelGGL(part_reduce_kernel<>, dim3(cdiv(H, PART_REDUCE_COLS)), dim3(256), 0, s, sc, nchunk, H, G(p + "edge_mlp.2.bias"), H);
+                if (wg) hipLaunchKernelGGL(part_reduce_kernel<>, dim3(cdiv(H, PART_REDUCE_COLS)), dim3(256), 0, s, sc, nchunk, H, G(p + "edge_mlp.2.bias"), H);
             } else {
                 hipLaunchKernelGGL(edge_dz2_kernel, g1(E * H), dim3(256), 0, s, t.dcat, b->src, b->rowptr, Z2, E, H);
             }
+            if (!wg) {   // (data-only form: edge_mlp.2's weight and bias gradients are not formed)
+            } else
 #if MI_PLANES_FP16
             if (w2_planes) {   // (both operands exist as plane sets: dZ2 just written above, M1 kept by this layer's training forward)
                 MI_TRY(gemm_tn_planes(dzp, 0, m1l, 0, G(p + "edge_mlp.2.weight"), H, (int)E, H, H, b->dsc + 6, t.dsc_layers + (size_t)l * 8, sc, scf, s));
@@ -1099,7 +1107,7 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
                 MI_KERNEL_CHECK();
                 MI_TRY(gemm_tn_auto(Z2, H, t.M1, H, G(p + "edge_mlp.2.weight"), H, (int)E, H, H, sc, scf, s));
             }
-            if (!dz2_sums) MI_TRY(colsum_acc(Z2, H, G(p + "edge_mlp.2.bias"), (int)E, H, sc, scf, s));
+            if (!dz2_sums && wg) MI_TRY(colsum_acc(Z2, H, G(p + "edge_mlp.2.bias"), (int)E, H, sc, scf, s));
             if (dz2_planes) {
                 PlanesEpilogue pd;
                 pd.C = t.dM1;
@@ -1118,17 +1126,17 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
                 MI_KERNEL_CHECK();
             }
             if (pairs) {  // t.M1 is free again (its weight gradient is done): Dm | Dp live there
-                float* gWff = G(p + "edge_mlp.0.weight") + 2 * H + 9;
+                float* gWff = wg ? G(p + "edge_mlp.0.weight") + 2 * H + 9 : nullptr;
                 float *Dm = t.M1, *Dp = t.M1 + (size_t)Np * H;
                 float* dsum = sc + scf - H;  // the tail of the scratch: the reductions below use its head
                 // (the LDS-tile pair pass: its per-crystal partial sums of the self edges' dZ1 go into the cosine block in ONE launch -- no dsum, no memset)
                 const bool dsum_folded = fused_pairs && b->nmax_fc <= PAIRS_NMAX && g_bwd_pairs_tile;
-                if (!dsum_folded) MI_HIP(hipMemsetAsync(dsum, 0, H * sizeof(float), s));
+                if (!dsum_folded && wg) MI_HIP(hipMemsetAsync(dsum, 0, H * sizeof(float), s));
                 const bool wff_f16 = dz2_planes && fused_pairs && g_bwd_wgrad_f16;  // two-plane fp16 operands for the Fourier-block weight gradient
                 bool wff_planes = false;   // ... and from plane sets: the pass below writes Dm / Dp as such, the Fourier operand is the forward's pair-mode plane set
 #if MI_PLANES_FP16
                 Planes dmp, dpp, ffp;
-                if (wff_f16 && g_bwd_wgrad_planes && t.DmPl && b->nmax_fc <= PAIRS_NMAX && g_bwd_pairs_tile && g_edge_pairs && b->FFpl) {
+                if (wg && wff_f16 && g_bwd_wgrad_planes && t.DmPl && b->nmax_fc <= PAIRS_NMAX && g_bwd_pairs_tile && g_edge_pairs && b->FFpl) {
                     dmp = make_planes(t.DmPl, H, 1.f, b->dsc + 8);
                     dpp = make_planes(t.DpPl, H, 1.f, b->dsc + 8);
                     ffp = make_planes(b->FFpl, 2 * net->Kh, PL_S_UNIT);
@@ -1145,23 +1153,34 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
 #endif
                     hipLaunchKernelGGL(edge_bwd_pairs_tile_kernel, dim3(B, cdiv(H, PAIRS_W)), dim3(256), sh, s, t.dM1, Z1, b->node_off, b->rowptr, b->pair_off, Dm,
                                        Dp, dPQ, dGl, sc, H, wff_f16 ? am + 1 : nullptr, wff_f16 ? b->dsc + 8 : nullptr);
-                    hipLaunchKernelGGL(part_reduce_bcast_kernel, dim3(cdiv(H, 32), 12), dim3(256), 0, s, sc, B, H, gWff + 3 * F, net->edge_in, H, 3 * F);
+                    if (wg) hipLaunchKernelGGL(part_reduce_bcast_kernel, dim3(cdiv(H, 32), 12), dim3(256), 0, s, sc, B, H, gWff + 3 * F, net->edge_in, H, 3 * F);
                     MI_KERNEL_CHECK();
                 } else if (fused_pairs) {
                     hipLaunchKernelGGL(edge_bwd_pairs_kernel, dim3(B, cdiv(H, 128)), dim3(128), (size_t)2 * b->nmax_fc * 128 * sizeof(float), s, t.dM1,
                                        Z1, b->node_off, b->rowptr, b->pair_off, Dm, Dp, dPQ, dGl, sc, H,
                                        wff_f16 ? am + 1 : nullptr, wff_f16 ? b->dsc + 8 : nullptr);
-                    hipLaunchKernelGGL(part_reduce_kernel<>, dim3(cdiv(H, PART_REDUCE_COLS)), dim3(256), 0, s, sc, B, H, dsum, H);
+                    if (wg) hipLaunchKernelGGL(part_reduce_kernel<>, dim3(cdiv(H, PART_REDUCE_COLS)), dim3(256), 0, s, sc, B, H, dsum, H);
                     MI_KERNEL_CHECK();
                 } else {
                     if (Np > 0) {
                         hipLaunchKernelGGL(pair_combine_kernel, g1(Np * (H / 4)), dim3(256), 0, s, t.dM1, b->pair_e1, b->pair_e2, Dm, Dp, Np, H);
                         MI_KERNEL_CHECK();
                     }
-                    MI_TRY(colsum_acc(t.dM1, H, dsum, N, H, sc, scf - H, s, b->e_diag));
+                    if (wg) MI_TRY(colsum_acc(t.dM1, H, dsum, N, H, sc, scf - H, s, b->e_diag));
                 }
-                if (!dsum_folded) hipLaunchKernelGGL(row_broadcast_add_kernel, g1((int64_t)H * 3 * F), dim3(256), 0, s, dsum, gWff + 3 * F, net->edge_in, H, 3 * F);
+                if (!dsum_folded && wg) hipLaunchKernelGGL(row_broadcast_add_kernel, g1((int64_t)H * 3 * F), dim3(256), 0, s, dsum, gWff + 3 * F, net->edge_in, H, 3 * F);
                 MI_KERNEL_CHECK();
+                if (ig) {
+                    // d u / d(sin | cos features) of the pairs, [Np][6F] into t.FF (free in this form: nothing builds the features' fp32 rows): Dm Wsin | Dp Wcos
+                    // with the fp32 rows the pass above wrote (the plane-set form of Dm / Dp belongs to the weight gradient and is not taken here), then
+                    // the chain rule through sin / cos into the pairs' d Delta -- layers L - 1 ... 0, the first one assigning
+                    if (Np > 0) {
+                        const float* wT = b->ig_wT + (size_t)l * 6 * F * H;
+                        MI_TRY(gemm_nt(Dm, H, wT, H, t.FF, 6 * F, (int)Np, 3 * F, H, GemmEpilogue(), s));
+                        MI_TRY(gemm_nt(Dp, H, wT + (size_t)3 * F * H, H, t.FF + 3 * F, 6 * F, (int)Np, 3 * F, H, GemmEpilogue(), s));
+                        MI_TRY(input_grad_pairs(net, b, t.in_frac, t.FF, l == L - 1, s));
+                    }
+                } else
 #if MI_PLANES_FP16
                 if (Np > 0 && wff_planes) {
                     MI_TRY(gemm_tn_planes(dmp, 0, ffp, 0, gWff, net->edge_in, (int)Np, H, 3 * F, b->dsc + 8, b->dsc + 12, sc, scf - H, s));
@@ -1189,10 +1208,10 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
             MI_HIP(hipMemsetAsync(dPQ, 0, NH * 2 * 4, s));
         }
         if (!edge_sums_done) hipLaunchKernelGGL(graph_sum_kernel, g1((int64_t)B * H), dim3(256), 0, s, dPQ, 2 * H, b->node_off, dGl, B, H);
-        if (!gram_batched) hipLaunchKernelGGL(gram_bwd_kernel, dim3(cdiv(H, 32)), dim3(256), 0, s, dGl, t.in_lat, G(p + "edge_mlp.0.weight"), net->edge_in,
+        if (!gram_batched && wg) hipLaunchKernelGGL(gram_bwd_kernel, dim3(cdiv(H, 32)), dim3(256), 0, s, dGl, t.in_lat, G(p + "edge_mlp.0.weight"), net->edge_in,
                                               G(p + "edge_mlp.0.bias"), B, H, (size_t)0, (size_t)0);
         MI_KERNEL_CHECK();
-        if (!defer) {
+        if (!defer && wg) {
             MI_TRY(gemm_tn_auto(dPQ, 2 * H, cat, 2 * H, G(p + "edge_mlp.0.weight"), net->edge_in, N, H, H, sc, scf, s));
             MI_TRY(gemm_tn_auto(dPQ + H, 2 * H, cat, 2 * H, G(p + "edge_mlp.0.weight") + H, net->edge_in, N, H, H, sc, scf, s));
         }
@@ -1201,7 +1220,7 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
             float *dY1 = nullptr, *Xa1 = nullptr, *dXa1 = nullptr;
             if (l > 0) w_rows(l - 1, &dY1, &Xa1, &dXa1);
             MI_TRY(node_bwd(net, b, l, dPQ, dh, dY1, dXa1, Xa1, ln_batched ? ln_tail + (size_t)l * ln_slot : sc, l > 0 ? b->absmax + 2 * L + 2 + 2 * (l - 1) : nullptr, s));
-            if (!ln_batched) hipLaunchKernelGGL(part_reduce_kernel<>, dim3(cdiv(2 * H, PART_REDUCE_COLS)), dim3(256), 0, s, sc, cdiv(N, 32), 2 * H, G(p + "layer_norm.weight"), 2 * H);
+            if (!ln_batched && wg) hipLaunchKernelGGL(part_reduce_kernel<>, dim3(cdiv(2 * H, PART_REDUCE_COLS)), dim3(256), 0, s, sc, cdiv(N, 32), 2 * H, G(p + "layer_norm.weight"), 2 * H);
             MI_KERNEL_CHECK();
             continue;
         }
@@ -1219,13 +1238,13 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
         }
     }
 
-    if (gram_batched) {   // the lattice term's weight / bias gradient of every layer: one launch (gridDim.y = L) over the per-layer d G slots
+    if (gram_batched && wg) {   // the lattice term's weight / bias gradient of every layer: one launch (gridDim.y = L) over the per-layer d G slots
         const size_t stride = net->off("csp_layer_1.edge_mlp.0.weight") - net->off("csp_layer_0.edge_mlp.0.weight");
         hipLaunchKernelGGL(gram_bwd_kernel, dim3(cdiv(H, 32), L), dim3(256), 0, s, t.dG, t.in_lat, G("csp_layer_0.edge_mlp.0.weight"), net->edge_in,
                            G("csp_layer_0.edge_mlp.0.bias"), B, H, (size_t)B * H, stride);
         MI_KERNEL_CHECK();
     }
-    if (ln_batched) {   // (every layer's parameter block has the same size: a constant stride between the layers' LayerNorm weights)
+    if (ln_batched && wg) {   // (every layer's parameter block has the same size: a constant stride between the layers' LayerNorm weights)
         const size_t stride = net->off("csp_layer_1.layer_norm.weight") - net->off("csp_layer_0.layer_norm.weight");
         hipLaunchKernelGGL(part_reduce_batched_kernel, dim3(cdiv(2 * H, 32), L), dim3(256), 0, s, ln_tail, ln_slot, cdiv(N, 32), 2 * H,
                            G("csp_layer_0.layer_norm.weight"), stride, 2 * H);
@@ -1233,6 +1252,10 @@ int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_co
     }
     // ---------------- embedding (cspnet.py:265-271) ----------------
     const int WA = H + TD;
+    if (ig) {   // the data path alone: the embedding's dXa (when the type rows' gradient is asked for), then input_grad.hip's three closing launches
+        if (ig->g_types) MI_TRY(gemm_nt(dh, H, net->WaT, H, t.dXa, H, N, H, H, GemmEpilogue(), s, &b->sk));
+        return input_grad_finish(net, b, ig, t.in_lat, t.dG, t.dXa, s);
+    }
     if (hw) {   // the data path only: d tproj and the embedding's dXa into the slot; the five contractions and three column sums run in net_wgrad_flush
         hipLaunchKernelGGL(graph_sum_kernel, g1((int64_t)B * H), dim3(256), 0, s, dh, H, b->node_off, t.w_dtproj + hs * B * H, B, H);
         MI_KERNEL_CHECK();

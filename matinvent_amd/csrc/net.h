@@ -266,6 +266,13 @@ struct mi_batch {
     // rows and -- forward-only form, which prepares no tape -- the noising's three by-products; the resampling's per-group flags and ESS
     float *st_sched = nullptr, *st_noise = nullptr;   // [B][4]; tar_x [N][3] | rnd_l [B][9] | rnd_t [N][100]
     float* st_parts = nullptr;                        // [B][2] = (flags, ESS) of group g in row g (B rows: room for K = 1)
+    // input gradient of the predictor (input_grad.hip, include/matinvent_hip_inputgrad.h; allocated on first use): the pairs'
+    // d u / d Delta summed over the layers, and the transposed Fourier columns of every layer's edge_mlp.0.weight (the W operand of gemm_nt)
+    // with the network and parameter version they were packed from
+    float* ig_dd = nullptr;                           // [Np][3]
+    float* ig_wT = nullptr;                           // [L][6F][H]
+    const void* ig_net = nullptr;
+    uint64_t ig_epoch = 0;
     mi_pool* pool = nullptr;
     std::vector<int> edge_off_h, pair_off_h;
     int* edge_off = nullptr;   // [B + 1] first edge of each crystal (pooled handles only)
@@ -284,8 +291,20 @@ int net_tape_prepare(mi_net* net, mi_batch* b);
 int net_pack_transposes(mi_net* net, hipStream_t s);
 // dgf_seed [B][H] (scalar_head.hip): the pass is seeded from d gf ALONE -- d hf[i] = dgf_seed[g(i)] / n_g, no head's backward, the lattice_out.* /
 // type_out.* / coord_out.* slices of `grad` untouched; d_lat / d_coord / d_type are not read.  NULL: the three heads' seeds, as ever.
+// ig (input_grad.hip): the DATA-ONLY, input-gradient form -- `grad` is NULL and never read: no weight-gradient contraction or
+// reduction is launched, and the pass additionally produces d / d(coordinates, lattices, type rows) of what seeded it.  Pair mode only (its
+// entry refuses everything else).  NULL: the pass of before, launch for launch.
+struct InputGradOut {
+    float *g_types, *g_frac, *g_lat;   // [N][100] or NULL, [N][3], [B][9]
+};
 int net_backward(mi_net* net, mi_batch* b, const float* d_lat, const float* d_coord, const float* d_type, float* grad, hipStream_t s,
-                 const float* dgf_seed = nullptr);
+                 const float* dgf_seed = nullptr, const InputGradOut* ig = nullptr);
+// input_grad.hip: the new launches of that form.  input_grad_pairs: d Delta (b->ig_dd) (=, when `first`, else +=) the chain rule through
+// sin / cos of dSC [Np][6F] = [Dm Wsin | Dp Wcos]; input_grad_finish: the scatter to the atoms, the lattice term's chain rule over t.dG
+// and (g_types) dXa node_embedding.weight.
+int input_grad_prepare(mi_net* net, mi_batch* b, hipStream_t s);   // the handle's buffers of this form and the transposed Fourier columns (once per parameter version)
+int input_grad_pairs(mi_net* net, mi_batch* b, const float* frac, const float* dSC, bool first, hipStream_t s);
+int input_grad_finish(mi_net* net, mi_batch* b, const InputGradOut* ig, const float* lattices, const float* dG, const float* dXa, hipStream_t s);
 // scalar_head.hip: that broadcast (one launch), and the trunk's forward alone -- net_forward(trunk_only) ends behind the final LayerNorm, b->hf
 int scalar_seed_hf(const mi_batch* b, const float* dgf, float* dhf, int H, hipStream_t s);
 // scalar_head.hip: the body of the predictor's entries with the INPUT STAGE passed in (steer.hip: the noised micro-step, the forward on a
@@ -303,7 +322,14 @@ int scalar_run(const char* what, mi_net* net, mi_batch* b, const float* lengths,
                const float* time_freqs, const int* times, int t_all, const float* W, const float* bias, int P, const float* yhat, const int* have,
                const int* have_host, const int* count_global, const int* count_global_host, int accum_steps, int loss_kind, float* grad_theta,
                float* grad_W, float* grad_bias, float* stats, float* out, void* stream, scalar_input_stage_fn stage = nullptr,
-               void* stage_ctx = nullptr, bool own_inputs = false);
+               void* stage_ctx = nullptr, bool own_inputs = false, const float* ig_dout = nullptr, const InputGradOut* ig = nullptr);
+// steer.hip: the input stage of a chain STATE (the caller's arrays are the network inputs; the stage fills the time embedding alone)
+struct ScalarStateCtx {
+    const float *atom_types, *frac, *lattices, *time_freqs;
+    const int* times;
+    int t_all;
+};
+int scalar_state_stage(mi_net* net, mi_batch* b, ScalarStageIO* io, void* ctx, hipStream_t s);
 // backward.hip: the fine-tune micro-step's sequence -- time fill and embedding, add_noise_kernel (draw ids 7-9 at call `noise_step`, or the
 // injected noise), the agent's training forward, the frozen prior's forward (forked onto aux_stream when given), the LOSS STAGE, net_backward
 // into grad_theta -- with the loss stage passed in: it reads both networks' predictions and the targets, writes the three gradient seeds

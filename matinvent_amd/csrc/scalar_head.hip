@@ -214,7 +214,9 @@ static int scalar_buffers(mi_batch* b, int P, bool forward_only) {
 int scalar_run(const char* what, mi_net* net, mi_batch* b, const float* lengths, const float* angles, const float* frac0, const int* atom_types,
                const float* time_freqs, const int* times, int t_all, const float* W, const float* bias, int P, const float* yhat, const int* have,
                const int* have_host, const int* count_global, const int* count_global_host, int accum_steps, int loss_kind, float* grad_theta,
-               float* grad_W, float* grad_bias, float* stats, float* out, void* stream, scalar_input_stage_fn stage, void* stage_ctx, bool own_inputs) {
+               float* grad_W, float* grad_bias, float* stats, float* out, void* stream, scalar_input_stage_fn stage, void* stage_ctx, bool own_inputs,
+               const float* ig_dout, const InputGradOut* ig) {
+    // (ig -- input_grad.hip: the taped forward, dgf = ig_dout W, and the trunk's data-only backward down to the inputs: no loss, no gradient buffer)
     MI_CHECK(!b || !b->pool || pool_stream(b->pool) == (hipStream_t)stream, MI_EINVAL, "%s: a pooled batch handle is used on its pool's stream only", what);
     MI_CHECK(net && b, MI_EINVAL, "null handle");
     MI_CHECK(b->H == net->H && b->L == net->L, MI_EINVAL, "batch was created for a different network");
@@ -223,7 +225,7 @@ int scalar_run(const char* what, mi_net* net, mi_batch* b, const float* lengths,
     MI_CHECK(!b->cond_on && !b->lik_on, MI_EINVAL, "%s: the handle carries a condition or a likelihood mask", what);
     MI_CHECK(!b->gd_on, MI_EINVAL, "%s: the handle carries guidance (mi_batch_clear_guidance first)", what);
     MI_CHECK(b->tape.wcur == 0, MI_EINVAL, "%s: the handle has pending deferred weight gradients (mi_cspnet_wgrad_flush first)", what);
-    MI_CHECK(!grad_theta || b->tape.wslots == 0, MI_EINVAL, "%s: the handle has an open weight-gradient window (mi_batch_set_wgrad_window(.., 0) first)", what);
+    MI_CHECK(!(grad_theta || ig) || b->tape.wslots == 0, MI_EINVAL, "%s: the handle has an open weight-gradient window (mi_batch_set_wgrad_window(.., 0) first)", what);
     MI_CHECK(P >= 1, MI_EINVAL, "%s: P = %d properties: at least 1", what, P);
     MI_CHECK(accum_steps >= 1, MI_EINVAL, "%s: accum_steps = %d must be >= 1", what, accum_steps);
     MI_CHECK(loss_kind == MI_SCALAR_LOSS_MSE || loss_kind == MI_SCALAR_LOSS_L1, MI_EINVAL, "%s: unknown loss_kind %d", what, loss_kind);
@@ -244,11 +246,12 @@ int scalar_run(const char* what, mi_net* net, mi_batch* b, const float* lengths,
         }
     if (B == 0 || N == 0) return MI_OK;
     MI_CHECK((stage || (lengths && angles && frac0 && atom_types)) && time_freqs && W && bias, MI_EINVAL, "null argument");
-    MI_CHECK(!grad_theta || net->W2T != nullptr, MI_ESTATE, "mi_net_set_params must run before backward");
+    MI_CHECK(!(grad_theta || ig) || net->W2T != nullptr, MI_ESTATE, "mi_net_set_params must run before backward");
     TraceRange range(what);
     hipStream_t s = (hipStream_t)stream;
-    const bool train = grad_theta != nullptr;
+    const bool train = grad_theta != nullptr || ig != nullptr;
     if (train) MI_TRY(net_tape_prepare(net, b));
+    if (ig) MI_TRY(input_grad_prepare(net, b, s));
     MI_TRY(scalar_buffers(b, P, !train && !own_inputs));
     Tape& tp = b->tape;
     ScalarStageIO io{};
@@ -282,6 +285,11 @@ int scalar_run(const char* what, mi_net* net, mi_batch* b, const float* lengths,
     if (yhat && stats) hipLaunchKernelGGL(scalar_stats_kernel, dim3(1), dim3(256), 0, s, b->sc_parts, count_global, B, P, loss_kind, stats);
     MI_KERNEL_CHECK();
     if (!train) return MI_OK;
+    if (ig) {
+        hipLaunchKernelGGL(scalar_dgf_kernel, dim3((unsigned)cdiv((int64_t)B * H, 256)), dim3(256), 0, s, ig_dout, W, tp.dgf, B, H, P);
+        MI_KERNEL_CHECK();
+        return net_backward(net, b, nullptr, nullptr, nullptr, nullptr, s, tp.dgf, ig);
+    }
     hipLaunchKernelGGL(scalar_dgf_kernel, dim3((unsigned)cdiv((int64_t)B * H, 256)), dim3(256), 0, s, b->sc_dout, W, tp.dgf, B, H, P);
     hipLaunchKernelGGL(scalar_wgrad_kernel, dim3((unsigned)cdiv((int64_t)P * H + P, 256)), dim3(256), 0, s, b->sc_dout, b->sc_gf, grad_W, grad_bias, B, H, P);
     MI_KERNEL_CHECK();

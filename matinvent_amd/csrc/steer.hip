@@ -173,13 +173,8 @@ static int noised_stage(mi_net* net, mi_batch* b, ScalarStageIO* io, void* ctx, 
                                     io->w_lat, io->w_frac, io->w_types, tar_x, rnd_l, rnd_t, c.stream);
 }
 
-struct StateCtx {
-    const float *atom_types, *frac, *lattices, *time_freqs;
-    const int* times;
-    int t_all;
-};
-static int state_stage(mi_net* net, mi_batch* b, ScalarStageIO* io, void* ctx, hipStream_t s) {
-    const StateCtx& c = *static_cast<const StateCtx*>(ctx);
+int scalar_state_stage(mi_net* net, mi_batch* b, ScalarStageIO* io, void* ctx, hipStream_t s) {   // (net.h: mi_scalar_input_grad's stage too)
+    const ScalarStateCtx& c = *static_cast<const ScalarStateCtx*>(ctx);
     hipLaunchKernelGGL(steer_temb_kernel, dim3(b->B), dim3(256), 0, s, c.time_freqs, c.times, c.t_all, net->TD, b->temb);
     MI_KERNEL_CHECK();
     io->in_lat = c.lattices;
@@ -224,9 +219,9 @@ int mi_scalar_forward_state(mi_net* net, mi_batch* b, const float* atom_types, c
     MI_NO_LATENT(net, "mi_scalar_forward_state");
     MI_CHECK(out, MI_EINVAL, "%s: null argument", what);
     MI_CHECK(!b || b->B == 0 || b->N == 0 || (atom_types && frac && lattices), MI_EINVAL, "%s: null argument", what);
-    StateCtx ctx{atom_types, frac, lattices, time_freqs, times, t_all};
+    ScalarStateCtx ctx{atom_types, frac, lattices, time_freqs, times, t_all};
     return scalar_run(what, net, b, nullptr, nullptr, nullptr, nullptr, time_freqs, times, t_all, W, bias, P, nullptr, nullptr, nullptr, nullptr,
-                      nullptr, 1, MI_SCALAR_LOSS_MSE, nullptr, nullptr, nullptr, nullptr, out, stream, state_stage, &ctx, true);
+                      nullptr, 1, MI_SCALAR_LOSS_MSE, nullptr, nullptr, nullptr, nullptr, out, stream, scalar_state_stage, &ctx, true);
 }
 
 int mi_steer_resample(mi_batch* b, int K, const float* out, int P, int p, int mode, float target_hat, float lambda, float ess_frac, uint64_t seed,

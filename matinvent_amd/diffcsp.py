@@ -466,7 +466,7 @@ class DiffCSPModule(nn.Module):
     @torch.no_grad()
     def sample(self, batch, diff_ratio=1.0, step_lr=1e-5, seed=0, noise=None, init=None, record=False, t_start=None,
                t_stop=0, node_offset=0, graph_offset=0, streams=None, rec_sink=None, condition=None, likelihood=None, resample=None,
-               guidance=None, steer=None):
+               guidance=None, steer=None, classifier=None):
         """DiffCSPModule.sample (diffusion.py:273-399).
 
         `rec_sink` (a list; with record=True): receives one (first crystal, first atom, buffers) per chain, in crystal order -- the
@@ -514,7 +514,21 @@ class DiffCSPModule(nn.Module):
         levels are step indices and the predictor is given their trained times.  ValueError by name before any device work: a predictor
         that is not noised or of another T / schedule, atom counts that are not K-replicated, streams > 1, `record`, `noise`,
         `condition`, `likelihood`, `resample`, `guidance`, CSP mode.
+
+        `classifier` = classifier.ClassifierGuidance(predictor, task, ...): classifier guidance from the noise-aware predictor's
+        input gradient.  Every step t -> t - 1 of the guided window is the gradient at x_t (at the trained time of t on a view), one
+        single-step segment, and the shift of the new state by scale * Sigma_t * gradient -- one chain on one stream, nothing read inside
+        it.  Returns (final, traj, info): info = dict(levels, times, out [E][B]) from one read at the end.  ValueError by name before any
+        device work: a predictor that is not noised, of another T / schedule or knn-style, streams > 1, `record`, `noise`, `condition`,
+        `likelihood`, `resample`, `guidance`, `steer`, CSP mode, a property-conditioned prior.
         """
+        if classifier is not None:
+            from . import classifier as _classifier
+            _classifier.check_call(self, classifier, streams=streams, record=record, noise=noise, condition=condition, likelihood=likelihood,
+                                   resample=resample, guidance=guidance, steer=steer)
+            if self.__dict__.get("_knn_pending"):
+                self.check_graph()
+            return _classifier.run_chain(self, batch, classifier, step_lr, seed, init, t_start, t_stop, node_offset, graph_offset)
         if steer is not None:
             from . import steering
             steering.check_call(self, steer, streams=streams, record=record, noise=noise, condition=condition, likelihood=likelihood,

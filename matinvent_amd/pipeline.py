@@ -241,6 +241,8 @@ class MatInventPG(MatInvent):
         refuse("MatInventPG", **{f"sample_cfg.{k}": merged.get(k) for k in ("resample_times", "jump_length")})
         from .steering import refuse as refuse_steer
         refuse_steer("MatInventPG", **{"sample_cfg.steer": merged.get("steer")})   # 
+        from .classifier import refuse as refuse_classifier
+        refuse_classifier("MatInventPG", **{"sample_cfg.classifier": merged.get("classifier")})   # 
         if kwargs.get("div_filter"):
             raise ValueError("MatInventPG: div_filter=True is not built -- the diversity filter penalises the rewards that rank a top-k, and the "
                              "policy gradient has no top-k (use pipeline=mat_invent)")

@@ -427,6 +427,67 @@ def forward_state(model, state, handle, t, out=None):
     return out
 
 
+GUIDE_MODES = {"max": _lib.GUIDE_MODE_MAX, "min": _lib.GUIDE_MODE_MIN, "target": _lib.GUIDE_MODE_TARGET}
+
+
+def guide_seed(model, out, task, mode="max", target=None, d_out=None):
+    """d_out [B][P] (device) of log p(y | x_t) from the normalised predictions `out` (mi_guide_seed): column `task` = +1 ("max"), -1 ("min")
+    or -(out - target_hat) ("target": the raw value aimed at, normalised here), every other column 0, a row whose prediction is not finite
+    all zeros.  No host synchronisation."""
+    from .cspnet import _ptr, _stream
+    if task not in model.names:
+        raise ValueError(f"guide_seed: task = {task!r} is not a property of the predictor ({model.names})")
+    if mode not in GUIDE_MODES:
+        raise ValueError(f"guide_seed: mode = {mode!r}: it takes 'max', 'min' or 'target'")
+    if (mode == "target") != (target is not None):
+        raise ValueError("guide_seed: target = goes with mode = 'target', and only with it")
+    p = model.names.index(task)
+    that = 0.0 if target is None else (float(target) - float(model.normalizer.mean[p])) / float(model.normalizer.std[p])
+    B, P = out.shape
+    if d_out is None:
+        d_out = torch.empty(B, P, device=out.device)
+    _lib.check(_lib.load().mi_guide_seed(_ptr(out), int(B), int(P), p, GUIDE_MODES[mode], that, _ptr(d_out), _stream()), "mi_guide_seed")
+    return d_out
+
+
+def input_gradient(model, state, handle, t, d_out=None, task=None, mode="max", target=None, types=True, bufs=None):
+    """(out, g_frac, g_lat, g_types): the normalised predictions [B][P] of a chain STATE and, per crystal b, the gradient of
+    sum_p d_out[b][p] out[b][p] with respect to its coordinates [N][3], lattice [B][3][3] and type rows [N][100] (mi_scalar_input_grad: the
+    taped forward and the trunk's data-only backward; types = False: g_types is None and not computed).  d_out: [B][P] -- or None: the
+    seed of guide_seed(task, mode, target) from the predictions of forward_state at the same state (one more inference forward).  state,
+    handle and t are forward_state's; the state's arrays are left unchanged.  A noise-aware predictor only.  No host synchronisation."""
+    require_noised(model, "input_gradient")
+    lib = _lib.load()
+    from .cspnet import _ptr, _stream
+    dev = model.device
+    x, l, a = (state["frac_coords"], state["lattices"], state["atom_types"]) if isinstance(state, dict) else state
+    B, N, P = handle.num_graphs, handle.num_nodes, model.P
+    f = lambda v: v.to(dev, torch.float32).contiguous()
+    x, l, a = f(x), f(l), f(a)
+    if a.numel() != N * _lib.NUM_TYPES or x.numel() != N * 3 or l.numel() != B * 9:
+        raise ValueError(f"input_gradient: the state's shapes {tuple(a.shape)}, {tuple(x.shape)}, {tuple(l.shape)} are not the handle's {N} atoms in {B} crystals")
+    if d_out is None:
+        if task is None:
+            raise ValueError("input_gradient: give d_out [B][P], or task (with mode / target) for the seed of guide_seed")
+        d_out = guide_seed(model, forward_state(model, (x, l, a), handle, t), task, mode, target, d_out=None if bufs is None else bufs["d_out"])
+    else:
+        d_out = f(d_out)
+        if tuple(d_out.shape) != (B, P):
+            raise ValueError(f"input_gradient: d_out has shape {tuple(d_out.shape)}, not ({B}, {P})")
+    tm, t_all = (None, int(t)) if isinstance(t, (int, np.integer)) else (_times(t, B, dev), 0)
+    if bufs is None:
+        bufs = dict(out=torch.empty(B, P, device=dev), g_frac=torch.empty(N, 3, device=dev), g_lat=torch.empty(B, 3, 3, device=dev),
+                    g_types=torch.empty(N, _lib.NUM_TYPES, device=dev) if types else None)
+    out, g_frac, g_lat, g_types = bufs["out"], bufs["g_frac"], bufs["g_lat"], bufs["g_types"] if types else None
+    if B == 0:
+        return out, g_frac, g_lat, g_types
+    model.trunk.sync()
+    _, W, bias = model.head_slices()
+    _lib.check(lib.mi_scalar_input_grad(model.trunk._h, handle._h, _ptr(a), _ptr(x), _ptr(l), _ptr(model.time_freqs), _ptr(tm), t_all, _ptr(W), _ptr(bias),
+                                        P, _ptr(d_out), _ptr(out), _ptr(g_types), _ptr(g_frac), _ptr(g_lat), _stream()), "mi_scalar_input_grad")
+    return out, g_frac, g_lat, g_types
+
+
 def predict(model, records_or_batch, batch_size=64, pool=None):
     """De-normalised predictions, np.ndarray [n][P] float64, of a list of records (CrystalData, structures, read_extxyz frames) or of a
     CrystalBatchData.  A crystal that cannot be evaluated -- no atoms, an atomic number outside 1..100, a non-finite value, an atom count
