@@ -314,10 +314,26 @@ INPUT_GRAD_SIGNATURES = {
     "mi_guide_shift": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
 }
 
+# the relaxation extension, include/matinvent_hip_relax.h (FIRE on the forces of the predictor read as an energy)
+RELAX_ACTIVE, RELAX_CONVERGED, RELAX_FAILED, RELAX_EXHAUSTED = 0, 1, 2, 3   # include/matinvent_hip_relax.h
+RELAX_NF, RELAX_NI, RELAX_MAX_ROWS = 6, 3, 1500
+
+
+class RelaxParams(C.Structure):
+    _fields_ = ([(k, C.c_float) for k in ("dt", "dt_max", "maxstep", "f_inc", "f_dec", "a_start", "f_a", "fmax", "scale", "cell_factor", "det_min")] +
+                [(k, C.c_int) for k in ("n_min", "relax_cell", "per_atom")])
+
+
+RELAX_SIGNATURES = {
+    "mi_relax_init": (_I, [_P, C.POINTER(RelaxParams), _I, _I, _P, _P, _P, _P, _P, _P]),
+    "mi_relax_step": (_I, [_P, C.POINTER(RelaxParams), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mi_relax_run": (_I, [_P, _P, C.POINTER(RelaxParams), _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, PRETRAIN_SIGNATURES)
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, PRETRAIN_SIGNATURES)
 
 _lib = None
 
@@ -372,7 +388,11 @@ def saturation_events(reset: bool = True) -> int:
 def check_saturation(where: str):
     """Raise if any operand left the range of the two-plane fp16 format since the last check: such results are finite but wrong,
     and must never be handed on silently."""
-    n = saturation_events(reset=True)
+    check_saturation_count(saturation_events(reset=True), where)
+
+
+def check_saturation_count(n: int, where: str):
+    """check_saturation for a count the caller has read (and reset) itself."""
     if n:
         raise FloatingPointError(
             f"{where}: {n} operand conversions saturated the two-plane fp16 format (values beyond 65504 / scale, or NaN / inf "

@@ -163,6 +163,8 @@ def _set_path(cfg, path: str, value, create_missing: bool):
                 raise KeyError(f"override {path!r}: key {p!r} does not exist (prefix with + to add)")
             node[p] = Config()
         node = node[p]
+        if isinstance(node, str) and node.startswith("${") and node.endswith("}") and node.count("${") == 1:
+            node = _select(cfg, node[2:-1])   # (a key that only points elsewhere, `sample_cfg: ${sample_cfg}`: the path goes on at its target)
     if parts[-1] not in node and not create_missing:
         raise KeyError(f"override {path!r}: key does not exist (prefix with + to add)")
     node[parts[-1]] = _wrap(value)

@@ -1,7 +1,9 @@
 """RL pipelines with the reference's class names, constructor arguments and method surface
 (pipeline/base.py:27-136 ReinL, pipeline/mat_invent.py:17-290 MatInvent, pipeline/baseline.py Baseline).
 Sampling and fine-tuning run on the HIP path; scoring and filtering are the caller's plug-ins (rewards / filters are out of scope and
-optional here); the long-term memory and its diversity filter are memory.LongTimeMem, by formula as in the reference or by structure
+optional here); sample_cfg.mlip_opt, a callable (strucs, xyz_path) -> (strucs, energies) such as relax.Relaxer, relaxes the
+valid samples before the filter and the reward see them, where the reference does; the long-term memory and its diversity filter are
+memory.LongTimeMem, by formula as in the reference or by structure
 (DESIGN 32)."""
 import logging
 import os
@@ -40,6 +42,23 @@ class ReinL:
         os.makedirs(self.sample_dir, exist_ok=True)
         self.replay = ReplayBuffer(**(replay_args or {})) if replay else None
         self.ltm = LongTimeMem()   # base.py:64
+
+    def relax_step(self, strucs, xyz_path=None):
+        """mat_invent.py:88-91: sample_cfg.mlip_opt(strucs, xyz_path) -> (relaxed structures, energies), or (strucs, None, {}) without the
+        key.  `data` -- what the fine-tune set is drawn from -- is never relaxed, as in the reference.  The third value: the log keys
+        relax_converged, relax_failed, relax_steps_mean, relax_de_mean."""
+        opt = self.sample_cfg.get("mlip_opt")
+        if opt is None:
+            return strucs, None, {}
+        if not callable(opt):
+            raise ValueError(f"sample_cfg.mlip_opt takes a callable (strucs, xyz_path) -> (strucs, energies), e.g. relax.Relaxer, not {type(opt).__name__}")
+        from .relax import log_metrics
+        relaxed, energies = opt(strucs, xyz_path)
+        if len(relaxed) != len(strucs) or len(energies) != len(strucs):
+            raise ValueError(f"sample_cfg.mlip_opt returned {len(relaxed)} structures and {len(energies)} energies for {len(strucs)} samples")
+        log = log_metrics(opt, energies)
+        logging.info("relaxation: " + ", ".join(f"{k}: {v}" for k, v in log.items()))
+        return list(relaxed), energies, log
 
     def reward_step(self, sample_data, sample_struc, xyz_path=None, label="tmp"):
         """base.py:98-127: score, drop failed samples."""
@@ -84,7 +103,8 @@ class MatInvent(ReinL):
 
     def sample_step(self):
         """mat_invent.py:74-123: sample, geometric validity pre-filter (device-side quantities), save the valid set as
-        extxyz, optional filter callable, max_num.  MLIP relaxation / SUN metrics are out of scope.
+        extxyz, the optional relaxation (sample_cfg.mlip_opt: relax_step), the optional filter callable -- which receives the
+        relaxation's energies, None without one --, max_num.  The stability / synthesizability metrics of SUN are out of scope.
         sample_cfg.target_compositions_dict (a list of {symbol: count}) reaches the sampler with the other keys: the loop then samples
         crystals of those formulas only (replacement conditioning) and fine-tunes on them -- a fixed-formula RL loop.
         sample_cfg.resample_times / sample_cfg.jump_length reach it the same way: the conditioned chains make RePaint's jumps."""
@@ -97,12 +117,15 @@ class MatInvent(ReinL):
             n_all = len(data)
             data, strucs = invalid_filter(data, strucs)
             logging.info(f"geometric pre-filter kept {len(data)} of {n_all} samples")
+        xyz = None
         if rank == 0 and getattr(self, "sample_dir", None):
-            write_extxyz(strucs, os.path.join(self.sample_dir, f"step_{self.step:0>4d}_valid.extxyz"))
+            xyz = write_extxyz(strucs, os.path.join(self.sample_dir, f"step_{self.step:0>4d}_valid.extxyz"))
+        strucs, energies, relax_log = self.relax_step(strucs, xyz)
         flt = self.sample_cfg.get("filter")
         metrics = {}
         if callable(flt):
-            data, strucs, metrics = flt(data, strucs, None)
+            data, strucs, metrics = flt(data, strucs, energies)
+        metrics = dict(metrics, **relax_log)
         max_num = self.sample_cfg.get("max_num")
         if max_num and len(strucs) > max_num:
             data, strucs = data[:max_num], strucs[:max_num]
@@ -183,7 +206,7 @@ class MatInvent(ReinL):
 
 class Baseline(ReinL):
     """pipeline/baseline.py: sample + score only (no fine-tuning); with the reference's 2-of-3 unpack
-    bug (:78) fixed."""
+    bug (:78) fixed.  sample_cfg.mlip_opt relaxes the samples before they are scored (relax_step)."""
 
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
@@ -192,9 +215,10 @@ class Baseline(ReinL):
     def rl_step(self):
         kw = {k: v for k, v in self.sample_cfg.items() if k not in ("filter", "mlip_opt", "geometric_filter")}
         data, strucs = self.sampler.generate(model=self.agent, **kw)
+        strucs, _, relax_log = self.relax_step(strucs)
         data, strucs, rewards, props = self.reward_step(data, strucs, None, f"step_{self.step:0>4d}")
         if self.logger is not None:
-            self.logger.log({"reward mean": rewards.mean(), "reward std": rewards.std()}, step=self.step)
+            self.logger.log(dict({"reward mean": rewards.mean(), "reward std": rewards.std()}, **relax_log), step=self.step)
 
     def run_rl(self):
         for step in range(self.rl_epoch):
@@ -205,7 +229,8 @@ class Baseline(ReinL):
 class MatInventPG(MatInvent):
     """MatInvent with the PPO-clipped policy gradient on recorded trajectories (policy.pg_step, DDPO-style) in place of the
     reward-weighted denoising loss.  Each RL loop: rollout (sampling.sample_rollout: the kept crystals' chains stay on the device) ->
-    the validity pre-filter, the optional filter callable and max_num, as in MatInvent -> reward_step -> pg_step over EVERY kept
+    the validity pre-filter, the optional relaxation (sample_cfg.mlip_opt), the optional filter callable and max_num, as in MatInvent ->
+    reward_step -> pg_step over EVERY kept
     crystal.  On-policy: there is no top-k and no replay (a stored crystal's log-probabilities belong to weights that no longer exist),
     so replay=True is refused.  Single GPU, DiffCSP only (MatterGen has no log-probability path), one sampling batch per loop.
     finetune_cfg.kl_coef > 0 anchors the agent's transitions to the frozen prior's (policy.pg_step) and logs prior_kl.
@@ -276,13 +301,16 @@ class MatInventPG(MatInvent):
                                        **self._condition_kwargs())
         strucs = [data2struc(d) for d in data]
         logging.info(f"rollout kept {len(data)} samples" + (f" over {rollout.T} steps" if self.sample_steps is not None else ""))
+        xyz = None
         if getattr(self, "sample_dir", None):
-            write_extxyz(strucs, os.path.join(self.sample_dir, f"step_{self.step:0>4d}_valid.extxyz"))
+            xyz = write_extxyz(strucs, os.path.join(self.sample_dir, f"step_{self.step:0>4d}_valid.extxyz"))
+        strucs, energies, relax_log = self.relax_step(strucs, xyz)
         pos = {id(d): i for i, d in enumerate(data)}
         flt = self.sample_cfg.get("filter")
         metrics = {}
         if callable(flt):
-            data, strucs, metrics = flt(data, strucs, None)
+            data, strucs, metrics = flt(data, strucs, energies)
+        metrics = dict(metrics, **relax_log)
         max_num = self.sample_cfg.get("max_num")
         if max_num and len(strucs) > max_num:
             data, strucs = data[:max_num], strucs[:max_num]
