@@ -330,10 +330,28 @@ RELAX_SIGNATURES = {
     "mi_relax_run": (_I, [_P, _P, C.POINTER(RelaxParams), _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
 }
 
+# the convex-hull extension, include/matinvent_hip_hull.h (energy above the lower hull of a bank of reference phases)
+HULL_MAX_ELEMS, HULL_MAX_ITERS, HULL_EPS, HULL_LDS_DOUBLES = 8, 256, 1e-12, 4096   # include/matinvent_hip_hull.h
+HULL_OK, HULL_NO_TERMINAL, HULL_UNBOUNDED, HULL_ITER_CAP, HULL_BAD_QUERY = 0, 1, 2, 3, 4
+HULL_FLAG_SKIPPED = 1
+
+
+class HullArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("bank_nelem", "bank_Z", "bank_frac", "bank_energy", "grp_nelem", "grp_Z", "grp_q_off", "q_idx", "grp_c_off", "c_idx",
+                                           "query_c", "query_e", "workspace", "e_hull", "e_above", "chempot", "decomp_frac", "decomp_idx", "iters", "status",
+                                           "flags")] +
+                [(k, C.c_int) for k in ("M", "G", "Q", "nnz_q", "nnz_c", "max_elems", "no_lds")])
+
+
+HULL_SIGNATURES = {
+    "mi_hull_workspace": (_L, [_I, _I, _I]),
+    "mi_hull_above": (_I, [C.POINTER(HullArgs), _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, PRETRAIN_SIGNATURES)
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, PRETRAIN_SIGNATURES)
 
 _lib = None
 

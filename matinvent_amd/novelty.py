@@ -13,7 +13,8 @@ batch, the nearest bank row of its formula and the number of rows within the tol
     rule is [UPSTREAM-UNVERIFIED], and its matcher is pymatgen's StructureMatcher, which is not reproduced.
   * `UNFilter`: both behind the reference's filter call shape, for `sample_cfg.filter`.
 
-"stable" (a MatterSim relaxation against a downloaded convex hull) and "synthesizable" stay out of scope."""
+"stable" is stability.SUNFilter's (the energy above the convex hull of a phase bank), which owns a UNFilter for U and N; this
+class keeps refusing the name.  "synthesizable" stays out of scope."""
 import ctypes as C
 
 import numpy as np

@@ -104,7 +104,8 @@ class MatInvent(ReinL):
     def sample_step(self):
         """mat_invent.py:74-123: sample, geometric validity pre-filter (device-side quantities), save the valid set as
         extxyz, the optional relaxation (sample_cfg.mlip_opt: relax_step), the optional filter callable -- which receives the
-        relaxation's energies, None without one --, max_num.  The stability / synthesizability metrics of SUN are out of scope.
+        relaxation's energies, None without one --, max_num.  The stability metric of SUN is stability.SUNFilter, which reads those
+        energies; the synthesizability metric is out of scope.
         sample_cfg.target_compositions_dict (a list of {symbol: count}) reaches the sampler with the other keys: the loop then samples
         crystals of those formulas only (replacement conditioning) and fine-tunes on them -- a fixed-formula RL loop.
         sample_cfg.resample_times / sample_cfg.jump_length reach it the same way: the conditioned chains make RePaint's jumps."""

@@ -122,6 +122,33 @@ class Surrogate:
         return y[:, self.col].copy()
 
 
+class EAboveHull:
+    """The energy above the convex hull (stability.energy_above_hull) as a calculator of `Reward.prop_cfg`: `.calc(samples,
+    label)` returns e_above in eV/atom per structure, NaN where the solver did not end at an optimum or the structure has no energy (->
+    failed -> reward 0); target "descending" then optimises towards stability.  bank: a stability.PhaseBank, or phase_path: a .npz of
+    scripts/build_phase_bank.py, loaded on first use.  The energies are the second member of `samples` when it is a tuple (strucs,
+    energies); otherwise relaxer(strucs, None) -> (strucs, energies) supplies them (relax.Relaxer, whose energies the bank must match)."""
+
+    def __init__(self, bank=None, phase_path=None, relaxer=None, per_atom=True, root_dir="rewards", device="cuda", **kwargs):
+        if (bank is None) == (phase_path is None):
+            raise ValueError("EAboveHull: give exactly one of bank (a stability.PhaseBank) and phase_path (a .npz phase bank)")
+        self.bank, self.phase_path, self.relaxer, self.per_atom, self.root_dir, self.device = bank, phase_path, relaxer, bool(per_atom), root_dir, device
+
+    def calc(self, samples, label="tmp"):
+        from . import stability
+        strucs, energies = (samples[0], samples[1] if len(samples) > 1 else None) if isinstance(samples, tuple) else (samples, None)
+        if len(strucs) == 0:
+            return np.zeros(0, dtype=float)
+        if energies is None:
+            if self.relaxer is None:
+                raise ValueError("EAboveHull: no energies -- pass samples as (strucs, energies) or give relaxer (relax.Relaxer)")
+            strucs, energies = self.relaxer(list(strucs), None)
+        if self.bank is None:
+            self.bank = stability.PhaseBank.load(self.phase_path, device=self.device)
+        res = stability.energy_above_hull(list(strucs), energies, self.bank, self.per_atom)
+        return np.where(res["status"] == stability.OK, res["e_above"], np.nan).astype(float)
+
+
 class PyMatGen:
     """The composition / cell properties of rewards/calculators/pymatgen/calc.py:163-205 that need no external database:
     `density` (g/cm^3, :45-53).  `hhi` (:57-73) is the mass-fraction-weighted Herfindahl-Hirschman index of the elements'
