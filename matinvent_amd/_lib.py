@@ -348,10 +348,45 @@ HULL_SIGNATURES = {
     "mi_hull_above": (_I, [C.POINTER(HullArgs), _P]),
 }
 
+# the vibration extension, include/matinvent_hip_vib.h (Gamma-point modes and harmonic thermodynamics of the predictor read as an energy)
+VIB_OK, VIB_NO_CONVERGENCE, VIB_BAD_INPUT = 0, 1, 2   # include/matinvent_hip_vib.h
+VIB_MAX_ATOMS, VIB_MAX_TEMPS, EIG_MAX_SWEEPS, EIG_LDS_MAX_M, EIG_MAX_M = 256, 8, 30, 128, 768
+
+
+class VibChunkArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("src_types", "src_frac", "src_lat", "src_node_off")] + [("Bs", C.c_int)] +
+                [(k, C.c_void_p) for k in ("plan_src", "plan_copy", "types", "frac", "lat", "g_frac", "workspace", "ws_off")] +
+                [(k, C.c_double) for k in ("h", "scale", "det_min")] + [("per_atom", C.c_int)])
+
+
+class VibDynmatArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("workspace", "ws_off", "node_off", "mass", "asym", "status")] + [("h", C.c_double), ("B", C.c_int), ("max_atoms", C.c_int)])
+
+
+class SymEigArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("mats", "mat_off", "sizes", "work", "work_off", "evals", "ev_off", "sweeps", "status")] +
+                [(k, C.c_int) for k in ("B", "max_size", "no_lds")])
+
+
+class VibThermoArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("evals", "ev_off", "sizes", "eig_status", "dyn_status", "freqs", "c_v", "zpe", "n_imag", "n_zero", "status")] +
+                [("temps", C.c_double * 8), ("nu_cut", C.c_double), ("B", C.c_int), ("K", C.c_int)])
+
+
+VIB_SIGNATURES = {
+    "mi_vib_workspace": (_L, [C.POINTER(_I), _I, C.POINTER(_L)]),
+    "mi_vib_displace": (_I, [_P, C.POINTER(VibChunkArgs), _P]),
+    "mi_vib_collect": (_I, [_P, C.POINTER(VibChunkArgs), _P]),
+    "mi_vib_run_chunk": (_I, [_P, _P, C.POINTER(VibChunkArgs), _P, _P, _P, _I, _P, _P, _P, _P]),
+    "mi_vib_dynmat": (_I, [C.POINTER(VibDynmatArgs), _P]),
+    "mi_sym_eigvals": (_I, [C.POINTER(SymEigArgs), _P]),
+    "mi_vib_thermo": (_I, [C.POINTER(VibThermoArgs), _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, PRETRAIN_SIGNATURES)
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, VIB_SIGNATURES, PRETRAIN_SIGNATURES)
 
 _lib = None
 

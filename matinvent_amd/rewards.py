@@ -1,6 +1,10 @@
-"""Synthetic reward with the `Reward.scoring` return contract (rewards/reward.py:8-115 returns
-(rewards, prop_dict, failed_mask)).  The reference's property calculators (pymatgen HHI, ALIGNN,
-DFT, ...) are out of scope; benchmarks and smoke runs use this."""
+"""Rewards with the `Reward.scoring` return contract (rewards/reward.py:8-115 returns (rewards, prop_dict, failed_mask)): the synthetic
+reward that benchmarks and smoke runs use, the reference's scalarisation `Reward`, and the calculators that run on this library --
+`Surrogate` (a trained property predictor), `EAboveHull` (the energy above the convex hull), `HeatCapacity` (the
+harmonic heat capacity of a predictor read as an energy, the reference's rewards/calculators/fairchem/phonon.py) and
+`PyMatGen` (density, HHI).  The energies behind EAboveHull and HeatCapacity are a PropertyPredictor's, relaxed by relax.Relaxer (DESIGN
+45): the reference's MLIP calculators (MatterSim, fairchem) themselves, ALIGNN and DFT stay out of scope (SURVEY.md section 2 rows
+11-12)."""
 import numpy as np
 
 
@@ -147,6 +151,58 @@ class EAboveHull:
             self.bank = stability.PhaseBank.load(self.phase_path, device=self.device)
         res = stability.energy_above_hull(list(strucs), energies, self.bank, self.per_atom)
         return np.where(res["status"] == stability.OK, res["e_above"], np.nan).astype(float)
+
+
+class HeatCapacity:
+    """The harmonic heat capacity (vibrations.analyze_records) as a calculator of `Reward.prop_cfg`: `.calc(samples, label)`
+    returns c_v at `temperature` in J / K / g per structure -- the Gamma-point modes of property `task` of a predictor read as an energy
+    (eV; per atom with per_atom).  NaN (-> failed -> reward 0) on any status other than OK and, with require_stable, for a structure with
+    an imaginary mode.  predictor: a loaded PropertyPredictor, or model_path: a directory written by predictor.save_predictor, loaded on
+    first use.  relaxer (relax.Relaxer, or any strucs, path -> (strucs, energies)): the structures are relaxed first, as the reference
+    does.  The remaining keywords are vibrations.Vibrations' (delta, nu_cut, batch_size, supercell, det_min)."""
+
+    def __init__(self, root_dir="rewards", predictor=None, model_path=None, task=None, temperature=300.0, relaxer=None, require_stable=False,
+                 supercell=(1, 1, 1), per_atom=True, device=None, **kwargs):
+        if (model_path is None) == (predictor is None):
+            raise ValueError("HeatCapacity: give exactly one of model_path (a save_predictor directory) and predictor (a loaded model)")
+        if task is None:
+            raise ValueError("HeatCapacity: task (the name of the property read as the energy) is required")
+        if not (np.isfinite(float(temperature)) and float(temperature) > 0):
+            raise ValueError(f"HeatCapacity: temperature = {temperature}: must be finite and positive")
+        self.root_dir, self.model_path, self.predictor, self.task, self.device = root_dir, model_path, predictor, str(task), device
+        self.temperature, self.relaxer, self.require_stable = float(temperature), relaxer, bool(require_stable)
+        self.vib_kw = dict(kwargs, supercell=tuple(int(r) for r in supercell), per_atom=bool(per_atom))
+        self.vib, self.last = None, None
+        if predictor is not None:
+            self._analysis()
+        else:
+            from .predictor import read_hparams
+            names = [str(n) for n in read_hparams(model_path)["names"]]
+            if self.task not in names:
+                raise ValueError(f"HeatCapacity: unknown property name {self.task!r}: the predictor has {names}")
+
+    def _analysis(self):
+        if self.vib is None:
+            from .vibrations import Vibrations
+            if self.predictor is None:
+                from .predictor import load_predictor
+                self.predictor = load_predictor(self.model_path, device=self.device)
+            self.vib = Vibrations(self.predictor, self.task, temperatures=(self.temperature,), **self.vib_kw)
+        return self.vib
+
+    def calc(self, samples, label="tmp"):
+        from . import vibrations
+        strucs = samples[0] if isinstance(samples, tuple) else samples
+        if len(strucs) == 0:
+            return np.zeros(0, dtype=float)
+        if self.relaxer is not None:
+            strucs, _ = self.relaxer(list(strucs), None)
+        res = vibrations.analyze_records(self._analysis(), list(strucs))
+        self.last = res
+        out = np.where(res["status"] == 0, res["c_v_gram"][:, 0], np.nan).astype(float)
+        if self.require_stable:
+            out[res["n_imag"] > 0] = np.nan
+        return out
 
 
 class PyMatGen:

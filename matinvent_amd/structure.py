@@ -75,6 +75,19 @@ def density(species, lengths, angles_deg) -> float:
     return m * _AMU_PER_A3_TO_G_CM3 / volume(lengths, angles_deg)
 
 
+def make_supercell(structure, reps):
+    """The (a, b, c)-fold replica of a record as a data.SimpleStructure: lengths multiplied, angles kept, the atoms of image (i, j, k) at
+    (frac + (i, j, k)) / (a, b, c), images in lexicographic order with the cell's atoms in their own order inside each."""
+    from .data import SimpleStructure
+    reps = tuple(int(r) for r in reps)
+    if len(reps) != 3 or min(reps) < 1:
+        raise ValueError(f"make_supercell: reps = {reps}: three integers >= 1")
+    lengths, angles, species, frac = _fields(structure)
+    shifts = np.array([(i, j, k) for i in range(reps[0]) for j in range(reps[1]) for k in range(reps[2])], dtype=np.float64)
+    x = ((frac[None, :, :] + shifts[:, None, :]) / np.asarray(reps, dtype=np.float64)).reshape(-1, 3)
+    return SimpleStructure([l * r for l, r in zip(lengths, reps)], list(angles), species * len(shifts), x)
+
+
 def _fields(s):
     """(lengths, angles, species, frac) of a SimpleStructure / CrystalData-like record."""
     if hasattr(s, "species"):
