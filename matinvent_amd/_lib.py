@@ -383,10 +383,34 @@ VIB_SIGNATURES = {
     "mi_vib_thermo": (_I, [C.POINTER(VibThermoArgs), _P]),
 }
 
+# the elasticity extension, include/matinvent_hip_elastic.h (the elastic tensor and moduli of the predictor read as an energy)
+ELASTIC_OK, ELASTIC_BAD_INPUT, ELASTIC_SINGULAR = 0, 1, 2   # include/matinvent_hip_elastic.h
+ELASTIC_COPIES, ELASTIC_ROW = 13, 8
+
+
+class ElasticChunkArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("src_types", "src_frac", "src_lat", "src_node_off")] + [("Bs", C.c_int)] +
+                [(k, C.c_void_p) for k in ("plan_src", "plan_copy", "types", "frac", "lat", "g_frac", "g_lat", "istate", "workspace", "asym")] +
+                [(k, C.c_double) for k in ("h", "scale", "det_min")] + [("per_atom", C.c_int)])
+
+
+class ElasticFitArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("workspace", "C", "S", "stress0", "pressure", "asym", "asym_C", "moduli", "evals", "cond", "n_negative",
+                                           "n_unrelaxed", "status")] + [("h", C.c_double), ("B", C.c_int)])
+
+
+ELASTIC_SIGNATURES = {
+    "mi_elastic_strain": (_I, [_P, C.POINTER(ElasticChunkArgs), _P]),
+    "mi_elastic_collect": (_I, [_P, C.POINTER(ElasticChunkArgs), _P]),
+    "mi_elastic_run_chunk": (_I, [_P, _P, C.POINTER(ElasticChunkArgs), C.POINTER(RelaxParams), _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "mi_elastic_fit": (_I, [C.POINTER(ElasticFitArgs), _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, VIB_SIGNATURES, PRETRAIN_SIGNATURES)
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
+                        PRETRAIN_SIGNATURES)
 
 _lib = None
 

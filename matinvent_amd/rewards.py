@@ -1,9 +1,10 @@
 """Rewards with the `Reward.scoring` return contract (rewards/reward.py:8-115 returns (rewards, prop_dict, failed_mask)): the synthetic
 reward that benchmarks and smoke runs use, the reference's scalarisation `Reward`, and the calculators that run on this library --
 `Surrogate` (a trained property predictor), `EAboveHull` (the energy above the convex hull), `HeatCapacity` (the
-harmonic heat capacity of a predictor read as an energy, the reference's rewards/calculators/fairchem/phonon.py) and
-`PyMatGen` (density, HHI).  The energies behind EAboveHull and HeatCapacity are a PropertyPredictor's, relaxed by relax.Relaxer (DESIGN
-45): the reference's MLIP calculators (MatterSim, fairchem) themselves, ALIGNN and DFT stay out of scope (SURVEY.md section 2 rows
+harmonic heat capacity of a predictor read as an energy, the reference's rewards/calculators/fairchem/phonon.py), `Elastic`
+(the bulk, shear and Young's modulus, Poisson's ratio and the Pugh ratio from the elastic tensor of a predictor read as an energy, the
+reference's rewards/calculators/fairchem/elastic.py) and `PyMatGen` (density, HHI).  The energies behind EAboveHull,
+HeatCapacity and Elastic are a PropertyPredictor's, relaxed by relax.Relaxer: the reference's MLIP calculators (MatterSim, fairchem) themselves, ALIGNN and DFT stay out of scope (SURVEY.md section 2 rows
 11-12)."""
 import numpy as np
 
@@ -202,6 +203,76 @@ class HeatCapacity:
         out = np.where(res["status"] == 0, res["c_v_gram"][:, 0], np.nan).astype(float)
         if self.require_stable:
             out[res["n_imag"] > 0] = np.nan
+        return out
+
+
+class Elastic:
+    """An elastic modulus (elasticity.analyze_records) as a calculator of `Reward.prop_cfg`: `.calc(samples, label)` returns
+    `quantity` -- bulk_modulus, shear_modulus, young_modulus (GPa), poisson_ratio or pugh_ratio -- in the `average` voigt, reuss or hill
+    per structure, from the elastic tensor of property `task` of a predictor read as an energy (eV; per atom with per_atom).  "voigt" is
+    the default because the reference's script returns bulk_modulus.voigt.  NaN (-> failed -> reward 0) on BAD_INPUT; for the Reuss and Hill
+    averages also on SINGULAR and when cond > cond_max (1e12: a stated, untuned choice -- the device applies no threshold); with
+    require_stable also when C has a negative eigenvalue (Born stability).  predictor: a loaded PropertyPredictor, or model_path: a
+    directory written by predictor.save_predictor, loaded on first use.  relaxer (relax.Relaxer, or any strucs, path -> (strucs,
+    energies)): the structures are relaxed first, as the reference does.  The remaining keywords are elasticity.Elasticity's (delta,
+    ion_steps, relax, batch_size, det_min)."""
+    QUANTITIES = ("bulk_modulus", "shear_modulus", "young_modulus", "poisson_ratio", "pugh_ratio")
+    AVERAGES = ("voigt", "reuss", "hill")
+
+    def __init__(self, root_dir="rewards", predictor=None, model_path=None, task=None, quantity="bulk_modulus", average="voigt", relaxer=None,
+                 require_stable=False, cond_max=1e12, per_atom=True, device=None, **kwargs):
+        if (model_path is None) == (predictor is None):
+            raise ValueError("Elastic: give exactly one of model_path (a save_predictor directory) and predictor (a loaded model)")
+        if task is None:
+            raise ValueError("Elastic: task (the name of the property read as the energy) is required")
+        if quantity not in self.QUANTITIES:
+            raise ValueError(f"Elastic: quantity = {quantity!r}: one of {self.QUANTITIES}")
+        if average not in self.AVERAGES:
+            raise ValueError(f"Elastic: average = {average!r}: one of {self.AVERAGES}")
+        if not float(cond_max) > 0:
+            raise ValueError(f"Elastic: cond_max = {cond_max}: must be positive")
+        self.root_dir, self.model_path, self.predictor, self.task, self.device = root_dir, model_path, predictor, str(task), device
+        self.quantity, self.average, self.relaxer = str(quantity), str(average), relaxer
+        self.require_stable, self.cond_max = bool(require_stable), float(cond_max)
+        self.ela_kw = dict(kwargs, per_atom=bool(per_atom))
+        self.ela, self.last = None, None
+        if predictor is not None:
+            self._analysis()
+        else:
+            from .predictor import read_hparams
+            names = [str(n) for n in read_hparams(model_path)["names"]]
+            if self.task not in names:
+                raise ValueError(f"Elastic: unknown property name {self.task!r}: the predictor has {names}")
+
+    def _analysis(self):
+        if self.ela is None:
+            from .elasticity import Elasticity
+            if self.predictor is None:
+                from .predictor import load_predictor
+                self.predictor = load_predictor(self.model_path, device=self.device)
+            self.ela = Elasticity(self.predictor, self.task, **self.ela_kw)
+        return self.ela
+
+    def calc(self, samples, label="tmp"):
+        from . import elasticity
+        strucs = samples[0] if isinstance(samples, tuple) else samples
+        if len(strucs) == 0:
+            return np.zeros(0, dtype=float)
+        if self.relaxer is not None:
+            strucs, _ = self.relaxer(list(strucs), None)
+        res = elasticity.analyze_records(self._analysis(), list(strucs))
+        self.last = res
+        status = np.asarray(res["status"])
+        out = np.array(res[self.quantity][:, self.AVERAGES.index(self.average)], dtype=float)
+        fine = status == 0
+        if self.average == "voigt":
+            fine |= status == 2   # SINGULAR keeps the Voigt values
+        else:
+            with np.errstate(invalid="ignore"):
+                fine &= np.asarray(res["cond"]) <= self.cond_max
+        if self.require_stable:
+            fine &= np.asarray(res["n_negative"]) == 0
+        out[~fine] = np.nan
         return out
 
 
