@@ -406,10 +406,31 @@ ELASTIC_SIGNATURES = {
     "mi_elastic_fit": (_I, [C.POINTER(ElasticFitArgs), _P]),
 }
 
+# the structure matcher, include/matinvent_hip_smatch.h (lattice maps, species-constrained assignment, RMS distance)
+SM_MAX_ATOMS, SM_SMALL_ATOMS, SM_MAX_SPECIES, SM_MAX_MAPS = 64, 32, 16, 256   # include/matinvent_hip_smatch.h
+SM_PREP_OK, SM_PREP_BAD_INPUT, SM_PREP_TOO_MANY_ATOMS, SM_PREP_TOO_MANY_SPECIES, SM_PREP_DEGENERATE_CELL, SM_PREP_REDUCE_CAP = 0, 1, 2, 3, 4, 5
+SM_OK, SM_NO_LATTICE, SM_BOX_CAP, SM_MAP_CAP, SM_SPECIES_MISMATCH, SM_BAD_PAIR, SM_NOT_PREPARED = 0, 1, 2, 3, 4, 5, 6
+
+
+class SmPrepared(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("offsets", "lat", "inv", "frac", "types", "perm", "spec_Z", "spec_off", "info")] + [("B", C.c_int), ("N", C.c_int)])
+
+
+class SmMatchArgs(C.Structure):
+    _fields_ = ([("a", SmPrepared), ("b", SmPrepared)] +
+                [(k, C.c_void_p) for k in ("pair_q", "pair_c", "rms", "max_dist", "best_map", "best_trans", "n_maps", "n_items", "status", "perm", "maps")] +
+                [("ltol", C.c_double), ("cos_tol", C.c_double), ("P", C.c_int), ("large_tile", C.c_int)])
+
+
+SMATCH_SIGNATURES = {
+    "mi_sm_prepare": (_I, [_P, _P, _P, C.POINTER(SmPrepared), _P]),
+    "mi_sm_match": (_I, [C.POINTER(SmMatchArgs), _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
                         PRETRAIN_SIGNATURES)
 
 _lib = None

@@ -389,7 +389,11 @@ class UNFilter:
     NEEDS = {"stable": "a MatterSim relaxation and a convex-hull reference set downloaded from a hub",
              "synthesizable": "a synthesizability model and its downloaded weights"}
 
-    def __init__(self, metrics=("unique", "novel"), reference_path=None, remember=False, fp_tol=FP_TOL, fp_args=None, device="cuda", **ignored):
+    def __init__(self, metrics=("unique", "novel"), reference_path=None, remember=False, fp_tol=FP_TOL, fp_args=None, device="cuda",
+                 matcher="fingerprint", ltol=0.2, stol=0.3, angle_tol=5.0, **ignored):
+        if matcher not in ("fingerprint", "structure"):
+            raise ValueError(f"UNFilter: matcher {matcher!r} is neither 'fingerprint' nor 'structure'")
+        self.matcher, self.ltol, self.stol, self.angle_tol = matcher, float(ltol), float(stol), float(angle_tol)
         metrics = [str(m) for m in metrics]
         for m in metrics:
             if m in self.NEEDS:
@@ -402,17 +406,46 @@ class UNFilter:
 
     @property
     def bank(self):
+        if self._bank is None and self.matcher == "structure":   # a StructureBank (.npz of scripts/build_structure_bank.py)
+            from .matching import StructureBank
+            self._bank = StructureBank.load(self.reference_path, self.device) if self.reference_path else StructureBank(self.device)
         if self._bank is None:   # on first use: constructing the filter touches no device
             kw = dict(fp_tol=self.fp_tol, device=self.device, **self.fp_args)
             self._bank = FingerprintBank.load(self.reference_path, **kw) if self.reference_path else FingerprintBank(**kw)
         return self._bank
+
+    def structure_masks(self, records):
+        """(unique, novel, match_rms_mean) under the structure matcher (matching.unique_mask / novel_mask): the mean is taken
+        over the records that match a bank row, NaN when none does."""
+        from . import matching
+        uniq = matching.unique_mask(records, self.ltol, self.stol, self.angle_tol, self.device)
+        novel, rms = matching.novel_mask(records, self.bank, self.ltol, self.stol, self.angle_tol, return_rms=True)
+        hit = rms <= self.stol
+        return uniq, novel, float(rms[hit].mean()) if hit.any() else float("nan")
 
     def __call__(self, data_list, structures, energies=None):
         records = structures if structures is not None else data_list
         n = len(records)
         bank = self.bank
         if n == 0:
-            return data_list, structures, {"unique_frac": 0.0, "novel_frac": 0.0, "un_frac": 0.0, "bank_size": float(len(bank))}
+            m = {"unique_frac": 0.0, "novel_frac": 0.0, "un_frac": 0.0, "bank_size": float(len(bank))}
+            if self.matcher == "structure":
+                m["match_rms_mean"] = float("nan")
+            return data_list, structures, m
+        if self.matcher == "structure":
+            uniq, novel, rms_mean = self.structure_masks(records)
+            keep = np.ones(n, bool)
+            if "unique" in self.metrics:
+                keep &= uniq
+            if "novel" in self.metrics:
+                keep &= novel
+            idx = [i for i in range(n) if keep[i]]
+            if self.remember and idx:
+                bank.add([records[i] for i in idx])
+            metrics = {"unique_frac": float(uniq.mean()), "novel_frac": float(novel.mean()), "un_frac": float((uniq & novel).mean()),
+                       "bank_size": float(len(bank)), "match_rms_mean": rms_mean}
+            pick = lambda xs: [xs[i] for i in idx] if xs is not None else None
+            return pick(data_list), pick(structures), metrics
         fingerprints = _fingerprints_of(records, None, bank.fp_args)
         uniq = unique_mask(records, fingerprints, self.fp_tol, bank.fp_args, self.device)
         novel = novel_mask(records, bank, fingerprints)

@@ -289,7 +289,7 @@ class SUNFilter:
     subset of {"stable", "unique", "novel"}; "validity" is accepted and ignored.  "stable" needs the energies of sample_cfg.mlip_opt."""
 
     def __init__(self, metrics=("stable", "unique", "novel"), phase_path=None, reference_path=None, threshold=STABLE_THRESHOLD, per_atom=True,
-                 remember=False, fp_tol=None, fp_args=None, device="cuda", bank=None, **ignored):
+                 remember=False, fp_tol=None, fp_args=None, device="cuda", bank=None, matcher="fingerprint", ltol=0.2, stol=0.3, angle_tol=5.0, **ignored):
         from .novelty import UNFilter
         from .structure import FP_TOL
         metrics = [str(m) for m in metrics]
@@ -305,7 +305,8 @@ class SUNFilter:
             raise ValueError(f"SUNFilter: threshold = {threshold!r} is not finite")
         self.threshold, self.per_atom, self.phase_path, self.device = float(threshold), bool(per_atom), phase_path, device
         self.un = UNFilter(metrics=[m for m in self.metrics if m != "stable"], reference_path=reference_path, remember=remember,
-                           fp_tol=FP_TOL if fp_tol is None else fp_tol, fp_args=fp_args, device=device)
+                           fp_tol=FP_TOL if fp_tol is None else fp_tol, fp_args=fp_args, device=device, matcher=matcher, ltol=ltol, stol=stol,
+                           angle_tol=angle_tol)
         self._bank = bank
 
     @property
@@ -327,9 +328,13 @@ class SUNFilter:
             m = {"unique_frac": 0.0, "novel_frac": 0.0, "un_frac": 0.0, "bank_size": float(len(un.bank)), "stable_frac": 0.0,
                  "e_above_hull_mean": float("nan"), "no_terminal": 0.0, "sun_frac": 0.0, "phase_bank_size": float(len(self.bank)) if want_s else 0.0}
             return data_list, structures, m
-        fingerprints = novelty._fingerprints_of(records, None, un.bank.fp_args)
-        uniq = novelty.unique_mask(records, fingerprints, un.fp_tol, un.bank.fp_args, un.device)
-        novel = novelty.novel_mask(records, un.bank, fingerprints)
+        rms_mean = None
+        if un.matcher == "structure":   # the structure matcher's U and N
+            uniq, novel, rms_mean = un.structure_masks(records)
+        else:
+            fingerprints = novelty._fingerprints_of(records, None, un.bank.fp_args)
+            uniq = novelty.unique_mask(records, fingerprints, un.fp_tol, un.bank.fp_args, un.device)
+            novel = novelty.novel_mask(records, un.bank, fingerprints)
         if want_s:
             res = energy_above_hull(records, energies, self.bank, self.per_atom)
             stable = stable_mask(res, self.threshold)
@@ -344,11 +349,15 @@ class SUNFilter:
             if name in self.metrics:
                 keep &= mask
         idx = [i for i in range(n) if keep[i]]
-        if un.remember and idx:
+        if un.remember and idx and un.matcher == "structure":
+            un.bank.add([records[i] for i in idx])
+        elif un.remember and idx:
             un.bank.add([records[i] for i in idx], (fingerprints[0][idx], fingerprints[1][idx]))
         metrics = {"unique_frac": float(uniq.mean()), "novel_frac": float(novel.mean()), "un_frac": float((uniq & novel).mean()),
                    "bank_size": float(len(un.bank)), "stable_frac": float(stable.mean()) if want_s else float("nan"), "e_above_hull_mean": e_mean,
                    "no_terminal": no_term, "sun_frac": float((stable & uniq & novel).mean()),
                    "phase_bank_size": float(len(self.bank)) if want_s else 0.0}
+        if rms_mean is not None:
+            metrics["match_rms_mean"] = rms_mean
         pick = lambda xs: [xs[i] for i in idx] if xs is not None else None
         return pick(data_list), pick(structures), metrics
