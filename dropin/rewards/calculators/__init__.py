@@ -1,1 +1,1 @@
-from matinvent_amd.rewards import Elastic, HeatCapacity, PyMatGen, Surrogate  # noqa: F401
+from matinvent_amd.rewards import Elastic, HeatCapacity, PyMatGen, Surrogate, Symmetry  # noqa: F401

@@ -427,10 +427,30 @@ SMATCH_SIGNATURES = {
     "mi_sm_match": (_I, [C.POINTER(SmMatchArgs), _P]),
 }
 
+# the symmetry finder, include/matinvent_hip_sym.h (space-group operations, point group, primitive cell of a prepared set)
+SYM_MAX_OPS, SYM_MAX_TRANS, SYM_INFO, SYM_CLASSES = 192, 64, 8, 10   # include/matinvent_hip_sym.h
+SYM_OK, SYM_NOT_PREPARED, SYM_BOX_CAP, SYM_MAP_CAP, SYM_NO_LATTICE, SYM_AMBIGUOUS, SYM_OPS_CAP, SYM_NOT_A_GROUP, SYM_PRIM_FAIL, SYM_BAD_TOL = 0, 1, 2, 4, 8, 16, 32, 64, 128, 256
+
+
+class SymOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("info", "rot_hist", "rot", "trans", "dev", "ptrans")]
+
+
+class SymPrimArgs(C.Structure):
+    _fields_ = ([("set", SmPrepared)] +
+                [(k, C.c_void_p) for k in ("types", "frac", "lat", "sym_info", "ptrans", "ws_types", "ws_frac", "prim_count", "prim_status", "prim_det",
+                                           "prim_offsets", "out_types", "out_frac", "out_lat")])
+
+
+SYM_SIGNATURES = {
+    "mi_sym_find": (_I, [C.POINTER(SmPrepared), _P, C.c_double, C.POINTER(SymOut), _P]),
+    "mi_sym_primitive": (_I, [C.POINTER(SymPrimArgs), _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, SYM_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
                         PRETRAIN_SIGNATURES)
 
 _lib = None

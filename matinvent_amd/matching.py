@@ -1,10 +1,10 @@
 """The structure matcher on the device (include/matinvent_hip_smatch.h): is it the same structure, how far apart, and which
 atom is which.  Follows the algorithm of pymatgen's StructureMatcher step by step -- lattice maps within (ltol, angle_tol), candidate
 translations from the rarest species, a species-constrained optimal assignment, an RMS displacement normalised by (V / n)^(1/3) compared
-with stol -- and is not bit-compatible with it; the defaults ltol 0.2, stol 0.3, angle_tol 5 degrees are [UPSTREAM-UNVERIFIED].  Not
-built: primitive-cell reduction and supercells (two cells of one structure with different atom counts are not compared; the fingerprint
-relation of novelty.py is supercell-invariant and stays available), the disordered matcher's substitutions, the second acceptance
-criterion on max_dist."""
+with stol -- and is not bit-compatible with it; the defaults ltol 0.2, stol 0.3, angle_tol 5 degrees are [UPSTREAM-UNVERIFIED].  With
+primitive=True every crystal is reduced to its primitive cell first (symmetry.py, DESIGN 50: prepare -> mi_sym_find -> mi_sym_primitive
+-> prepare), so two cells of one structure with different atom counts are compared; the default False compares cells as given.  Not
+built: supercell search inside the matcher, the disordered matcher's substitutions, the second acceptance criterion on max_dist."""
 import ctypes as C
 import math
 
@@ -52,12 +52,30 @@ def prepare_arrays(offsets, types, frac, lat, fill=None):
     return out
 
 
-def prepare(records, device="cuda"):
-    """A prepared set from host records (SimpleStructure / CrystalData-like): one upload, one launch."""
+def prepare_primitive_arrays(offsets, types, frac, lat, tol):
+    """The prepared set of the primitive cells: prepare -> mi_sym_find -> mi_sym_primitive -> prepare, nothing read back.
+    tol: symmetry.tolerances of the crystals."""
+    from . import symmetry
+    prim, _ = symmetry.reduce_arrays(offsets, types, frac, lat, tol)
+    return prepare_arrays(prim.offsets, prim.types, prim.frac, prim.lat)
+
+
+def prepare(records, device="cuda", primitive=False, symprec=0.1):
+    """A prepared set from host records (SimpleStructure / CrystalData-like): one upload, one launch.  primitive: of their primitive
+    cells (symprec in A, symmetry.py's)."""
     na, types, frac, lat = record_arrays(records)
     offsets = torch.cat([torch.zeros(1, dtype=torch.long), na.cumsum(0)]).to(torch.int32)
     dev = torch.device(device)
+    if primitive and len(records):
+        from . import symmetry
+        return prepare_primitive_arrays(offsets.to(dev), types.to(dev), frac.to(dev), lat.reshape(-1, 9).to(dev),
+                                        symmetry.tolerances(na.numpy(), lat.numpy(), symprec))
     return prepare_arrays(offsets.to(dev), types.to(dev), frac.to(dev), lat.reshape(-1, 9).to(dev))
+
+
+def _counts(prepared):
+    """The atom counts of a prepared set on the host: one read."""
+    return np.diff(prepared.offsets.cpu().numpy().astype(np.int64))
 
 
 def match_pairs(set_a, set_b, pairs, ltol=LTOL, stol=STOL, angle_tol=ANGLE_TOL, permutation=False, maps=False, large_tile=False, fill=None):
@@ -86,17 +104,17 @@ def match_pairs(set_a, set_b, pairs, ltol=LTOL, stol=STOL, angle_tol=ANGLE_TOL, 
     return out
 
 
-def rms_dist(record_a, record_b, ltol=LTOL, stol=STOL, angle_tol=ANGLE_TOL, device="cuda"):
+def rms_dist(record_a, record_b, ltol=LTOL, stol=STOL, angle_tol=ANGLE_TOL, device="cuda", primitive=False, symprec=0.1):
     """(rms, max_dist) of the best map, translation and assignment, or None when the two are not comparable or have no lattice map."""
-    s = prepare([record_a, record_b], device)
+    s = prepare([record_a, record_b], device, primitive, symprec)
     r = match_pairs(s, s, [(0, 1)], ltol, stol, angle_tol)
     rms, md, st = float(r["rms"][0]), float(r["max_dist"][0]), int(r["status"][0])
     return (rms, md) if st == _lib.SM_OK and np.isfinite(rms) else None
 
 
-def fit(record_a, record_b, ltol=LTOL, stol=STOL, angle_tol=ANGLE_TOL, device="cuda"):
+def fit(record_a, record_b, ltol=LTOL, stol=STOL, angle_tol=ANGLE_TOL, device="cuda", primitive=False, symprec=0.1):
     """rms <= stol.  pymatgen's second criterion on max_dist is not reproduced."""
-    d = rms_dist(record_a, record_b, ltol, stol, angle_tol, device)
+    d = rms_dist(record_a, record_b, ltol, stol, angle_tol, device, primitive, symprec)
     return d is not None and d[0] <= stol
 
 
@@ -108,10 +126,12 @@ def _key(record):
 class StructureBank:
     """An append-only reference set for the structure matcher.  The records' arrays (atom counts, atomic numbers, float32 coordinates and
     cells) are kept on the host, the prepared set on the device; it is prepared again, in one launch, at the first use after an append.
-    A host index (reduced formula, atom count) -> rows selects a query's candidates.  save / load: an .npz of those arrays only."""
+    A host index (reduced formula, atom count) -> rows selects a query's candidates.  save / load: an .npz of those arrays only.
+    primitive=True: every record is reduced to its primitive cell as it is added (one read of the reduced arrays per append, none per
+    match) and the index keys on the primitive atom count; queries are then reduced the same way."""
 
-    def __init__(self, device="cuda"):
-        self.device = torch.device(device)
+    def __init__(self, device="cuda", primitive=False, symprec=0.1):
+        self.device, self.primitive, self.symprec = torch.device(device), bool(primitive), float(symprec)
         self.na, self.types, self.frac, self.lat, self.keys = [], [], [], [], []
         self.index, self.formulas, self._set = {}, set(), None
 
@@ -122,7 +142,17 @@ class StructureBank:
         if len(records) == 0:
             return
         na, types, frac, lat = record_arrays(records)
-        self._add_arrays(na.numpy(), types.numpy(), frac.numpy(), lat.reshape(-1, 9).numpy(), [_key(r) for r in records])
+        keys = [_key(r) for r in records]
+        if self.primitive:
+            from . import symmetry
+            off = torch.cat([torch.zeros(1, dtype=torch.long), na.cumsum(0)]).to(torch.int32)
+            prim, _ = symmetry.reduce_arrays(off.to(self.device), types.to(self.device), frac.to(self.device), lat.reshape(-1, 9).to(self.device),
+                                             symmetry.tolerances(na.numpy(), lat.numpy(), self.symprec))
+            poff = prim.offsets.cpu().numpy().astype(np.int64)
+            n = int(poff[-1])
+            na, types, frac, lat = torch.from_numpy(np.diff(poff)), prim.types[:n].cpu(), prim.frac[:n].cpu(), prim.lat.cpu()
+            keys = [(k[0], int(c)) for k, c in zip(keys, na.tolist())]
+        self._add_arrays(na.numpy(), types.numpy(), frac.numpy(), lat.reshape(-1, 9).numpy(), keys)
 
     def _add_arrays(self, na, types, frac, lat, keys):
         for k in keys:
@@ -156,8 +186,9 @@ class StructureBank:
         return path
 
     @classmethod
-    def load(cls, path, device="cuda"):
-        bank = cls(device)
+    def load(cls, path, device="cuda", primitive=False, symprec=0.1):
+        """primitive: the file's cells are taken as primitive already (a bank that was saved from a primitive=True bank)."""
+        bank = cls(device, primitive, symprec)
         with np.load(path, allow_pickle=False) as z:
             na = z["num_atoms"]
             if len(na):
@@ -165,8 +196,8 @@ class StructureBank:
         return bank
 
     @classmethod
-    def from_records(cls, records, device="cuda"):
-        bank = cls(device)
+    def from_records(cls, records, device="cuda", primitive=False, symprec=0.1):
+        bank = cls(device, primitive, symprec)
         bank.add(records)
         return bank
 
@@ -180,7 +211,9 @@ def novel_mask(records, bank, ltol=LTOL, stol=STOL, angle_tol=ANGLE_TOL, return_
     if n == 0:
         return (np.zeros(0, bool), best) if return_rms else np.zeros(0, bool)
     keys = [_key(r) for r in records]
-    q = prepare(records, bank.device)
+    q = prepare(records, bank.device, bank.primitive, bank.symprec)
+    if bank.primitive:
+        keys = [(k[0], int(c)) for k, c in zip(keys, _counts(q))]
     flagged = q.status.cpu().numpy() != _lib.SM_PREP_OK
     novel = np.ones(n, bool)
     pairs = [(i, row) for i in range(n) if not flagged[i] for row in bank.rows(keys[i])]
@@ -195,17 +228,20 @@ def novel_mask(records, bank, ltol=LTOL, stol=STOL, angle_tol=ANGLE_TOL, return_
     return (novel, best) if return_rms else novel
 
 
-def unique_mask(records, ltol=LTOL, stol=STOL, angle_tol=ANGLE_TOL, device="cuda"):
+def unique_mask(records, ltol=LTOL, stol=STOL, angle_tol=ANGLE_TOL, device="cuda", primitive=False, symprec=0.1):
     """Leader clustering in list order within each (reduced formula, atom count): record i is kept iff no earlier KEPT record fits it, the
     rule novelty.unique_mask documents; the pair matrix of every group comes from one mi_sm_match call and novelty.resolve_leaders reads
-    it.  Records whose prepare status is not OK match by formula alone, among themselves: the first of a formula is kept."""
+    it.  Records whose prepare status is not OK match by formula alone, among themselves: the first of a formula is kept.  primitive: the
+    records are reduced to their primitive cells first and the groups key on the primitive atom count."""
     from .novelty import resolve_leaders
     n = len(records)
     mask = np.zeros(n, bool)
     if n == 0:
         return mask
     keys = [_key(r) for r in records]
-    s = prepare(records, device)
+    s = prepare(records, device, primitive, symprec)
+    if primitive:   # the groups key on the primitive atom count
+        keys = [(k[0], int(c)) for k, c in zip(keys, _counts(s))]
     flagged = s.status.cpu().numpy() != _lib.SM_PREP_OK
     groups, seen_flagged = {}, set()
     for i, k in enumerate(keys):

@@ -390,10 +390,11 @@ class UNFilter:
              "synthesizable": "a synthesizability model and its downloaded weights"}
 
     def __init__(self, metrics=("unique", "novel"), reference_path=None, remember=False, fp_tol=FP_TOL, fp_args=None, device="cuda",
-                 matcher="fingerprint", ltol=0.2, stol=0.3, angle_tol=5.0, **ignored):
+                 matcher="fingerprint", ltol=0.2, stol=0.3, angle_tol=5.0, primitive=False, symprec=0.1, **ignored):
         if matcher not in ("fingerprint", "structure"):
             raise ValueError(f"UNFilter: matcher {matcher!r} is neither 'fingerprint' nor 'structure'")
         self.matcher, self.ltol, self.stol, self.angle_tol = matcher, float(ltol), float(stol), float(angle_tol)
+        self.primitive, self.symprec = bool(primitive), float(symprec)   # the structure matcher on primitive cells
         metrics = [str(m) for m in metrics]
         for m in metrics:
             if m in self.NEEDS:
@@ -408,7 +409,8 @@ class UNFilter:
     def bank(self):
         if self._bank is None and self.matcher == "structure":   # a StructureBank (.npz of scripts/build_structure_bank.py)
             from .matching import StructureBank
-            self._bank = StructureBank.load(self.reference_path, self.device) if self.reference_path else StructureBank(self.device)
+            self._bank = (StructureBank.load(self.reference_path, self.device, self.primitive, self.symprec) if self.reference_path else
+                          StructureBank(self.device, self.primitive, self.symprec))
         if self._bank is None:   # on first use: constructing the filter touches no device
             kw = dict(fp_tol=self.fp_tol, device=self.device, **self.fp_args)
             self._bank = FingerprintBank.load(self.reference_path, **kw) if self.reference_path else FingerprintBank(**kw)
@@ -418,7 +420,7 @@ class UNFilter:
         """(unique, novel, match_rms_mean) under the structure matcher (matching.unique_mask / novel_mask): the mean is taken
         over the records that match a bank row, NaN when none does."""
         from . import matching
-        uniq = matching.unique_mask(records, self.ltol, self.stol, self.angle_tol, self.device)
+        uniq = matching.unique_mask(records, self.ltol, self.stol, self.angle_tol, self.device, self.primitive, self.symprec)
         novel, rms = matching.novel_mask(records, self.bank, self.ltol, self.stol, self.angle_tol, return_rms=True)
         hit = rms <= self.stol
         return uniq, novel, float(rms[hit].mean()) if hit.any() else float("nan")

@@ -3,7 +3,8 @@ reward that benchmarks and smoke runs use, the reference's scalarisation `Reward
 `Surrogate` (a trained property predictor), `EAboveHull` (the energy above the convex hull), `HeatCapacity` (the
 harmonic heat capacity of a predictor read as an energy, the reference's rewards/calculators/fairchem/phonon.py), `Elastic`
 (the bulk, shear and Young's modulus, Poisson's ratio and the Pugh ratio from the elastic tensor of a predictor read as an energy, the
-reference's rewards/calculators/fairchem/elastic.py) and `PyMatGen` (density, HHI).  The energies behind EAboveHull,
+reference's rewards/calculators/fairchem/elastic.py), `Symmetry` (the operation count, point-group order or crystal system of
+the symmetry finder) and `PyMatGen` (density, HHI).  The energies behind EAboveHull,
 HeatCapacity and Elastic are a PropertyPredictor's, relaxed by relax.Relaxer: the reference's MLIP calculators (MatterSim, fairchem) themselves, ALIGNN and DFT stay out of scope (SURVEY.md section 2 rows
 11-12)."""
 import numpy as np
@@ -273,6 +274,36 @@ class Elastic:
         if self.require_stable:
             fine &= np.asarray(res["n_negative"]) == 0
         out[~fine] = np.nan
+        return out
+
+
+class Symmetry:
+    """A symmetry figure (symmetry.find_symmetry) as a calculator of `Reward.prop_cfg`: `.calc(samples, label)` returns
+    `quantity` per structure -- n_ops (operations of the cell as given, pure translations included), pg_order (the point group's order),
+    not_p1 (1.0 when there is any operation beyond the pure translations, else 0.0) or crystal_system (1 triclinic .. 7 cubic).  NaN (->
+    failed -> reward 0) on any status other than OK: a crystal the prepare guard flags, an ambiguous tolerance, more operations than the
+    cap, a set that is not a group.  symprec in A (0.1: the reference's SpacegroupAnalyzer value)."""
+
+    QUANTITIES = ("n_ops", "pg_order", "not_p1", "crystal_system")
+
+    def __init__(self, quantity="n_ops", symprec=0.1, angle_tol=5.0, root_dir="rewards", device="cuda", **kwargs):
+        if quantity not in self.QUANTITIES:
+            raise ValueError(f"Symmetry: quantity {quantity!r} is none of {self.QUANTITIES}")
+        if not (np.isfinite(symprec) and symprec > 0):
+            raise ValueError(f"Symmetry: symprec = {symprec!r} is not a positive length")
+        self.quantity, self.symprec, self.angle_tol, self.root_dir, self.device = quantity, float(symprec), float(angle_tol), root_dir, device
+
+    def calc(self, samples, label="tmp"):
+        from . import _lib, symmetry
+        strucs = samples[0] if isinstance(samples, tuple) else samples
+        if len(strucs) == 0:
+            return np.zeros(0, dtype=float)
+        res = symmetry.find_symmetry(list(strucs), self.symprec, self.angle_tol, self.device)
+        col = "pg_order" if self.quantity == "not_p1" else self.quantity
+        out = getattr(res, col).astype(float)
+        if self.quantity == "not_p1":
+            out = (out > 1).astype(float)
+        out[res.status != _lib.SYM_OK] = np.nan
         return out
 
 

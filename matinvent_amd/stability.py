@@ -289,7 +289,8 @@ class SUNFilter:
     subset of {"stable", "unique", "novel"}; "validity" is accepted and ignored.  "stable" needs the energies of sample_cfg.mlip_opt."""
 
     def __init__(self, metrics=("stable", "unique", "novel"), phase_path=None, reference_path=None, threshold=STABLE_THRESHOLD, per_atom=True,
-                 remember=False, fp_tol=None, fp_args=None, device="cuda", bank=None, matcher="fingerprint", ltol=0.2, stol=0.3, angle_tol=5.0, **ignored):
+                 remember=False, fp_tol=None, fp_args=None, device="cuda", bank=None, matcher="fingerprint", ltol=0.2, stol=0.3, angle_tol=5.0, primitive=False, symprec=0.1,
+                 **ignored):
         from .novelty import UNFilter
         from .structure import FP_TOL
         metrics = [str(m) for m in metrics]
@@ -306,7 +307,7 @@ class SUNFilter:
         self.threshold, self.per_atom, self.phase_path, self.device = float(threshold), bool(per_atom), phase_path, device
         self.un = UNFilter(metrics=[m for m in self.metrics if m != "stable"], reference_path=reference_path, remember=remember,
                            fp_tol=FP_TOL if fp_tol is None else fp_tol, fp_args=fp_args, device=device, matcher=matcher, ltol=ltol, stol=stol,
-                           angle_tol=angle_tol)
+                           angle_tol=angle_tol, primitive=primitive, symprec=symprec)
         self._bank = bank
 
     @property

@@ -1,0 +1,160 @@
+"""Space-group operations, point group and primitive cell on the device (include/matinvent_hip_sym.h): the structure matcher
+run on (b, b) with a rigid metric, a nearest-atom test and every accepted (map, translation) item kept.  symprec = 0.1 A is the
+reference's value (SpacegroupAnalyzer(symprec=0.1)); angle_tol = 5 degrees is the matcher's and is untuned -- spglib's own lattice rule is
+[UPSTREAM-UNVERIFIED] and is not reproduced, and agreement with spglib is unverified (it is absent here).  Not built: the space-group
+number or Hall symbol, refined or standardised conventional cells, Wyckoff positions, symmetry reduction of the vibration or elastic
+displacement sets, magnetic and disordered structures."""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import matching
+from .structure import record_arrays
+
+SYMPREC, ANGLE_TOL = 0.1, 5.0
+CLASSES = (-6, -4, -3, -2, -1, 1, 2, 3, 4, 6)
+POINT_GROUPS = ("", "1", "-1", "2", "m", "2/m", "222", "mm2", "mmm", "4", "-4", "4/m", "422", "4mm", "-42m", "4/mmm", "3", "-3", "32", "3m", "-3m", "6", "-6",
+                "6/m", "622", "6mm", "-6m2", "6/mmm", "23", "m-3", "432", "-43m", "m-3m")
+CRYSTAL_SYSTEMS = ("", "triclinic", "monoclinic", "orthorhombic", "tetragonal", "trigonal", "hexagonal", "cubic")
+INFO = ("n_ops", "n_trans", "n_maps", "pg_order", "pg_index", "crystal_system", "has_inversion", "status")
+
+
+def tolerances(num_atoms, lattices, symprec=SYMPREC):
+    """symprec / (V_b / n_b)^(1/3) per crystal as float64 numpy, V_b in float64 from the float32 cell (rows of the prepared set's units:
+    unit volume per atom).  On the host, so that the device and the restatement read the same number; 1 where the cell has no volume (the
+    prepare status flags such a crystal)."""
+    L = np.asarray(lattices, np.float32).reshape(-1, 9).astype(np.float64)
+    na = np.asarray(num_atoms, np.int64)
+    out = np.ones(len(L))
+    for b in range(len(L)):
+        l = [float(x) for x in L[b]]
+        v = abs((l[0] * (l[4] * l[8] - l[5] * l[7]) - l[1] * (l[3] * l[8] - l[5] * l[6])) + l[2] * (l[3] * l[7] - l[4] * l[6]))
+        if na[b] >= 1 and math.isfinite(v) and v > 0.0:
+            out[b] = float(symprec) / (v / int(na[b])) ** (1.0 / 3.0)
+    return out
+
+
+class SymmetryResult:
+    """The arrays of mi_sym_find on the device (info [B, 8], rot_hist [B, 10], rot [B, 192, 9], trans [B, 192, 3], dev [B, 192], ptrans
+    [B, 64, 3]) and, read once, the named columns of info as numpy."""
+
+    def __init__(self, info, rot_hist, rot, trans, dev, ptrans, tol):
+        self.info, self.rot_hist, self.rot, self.trans, self.dev, self.ptrans, self.tol = info, rot_hist, rot, trans, dev, ptrans, tol
+        self._host = None
+
+    def __len__(self):
+        return len(self.info)
+
+    def host(self):
+        if self._host is None:
+            self._host = self.info.cpu().numpy()
+        return self._host
+
+    def __getattr__(self, name):
+        if name in INFO:
+            return self.host()[:, INFO.index(name)].copy()
+        raise AttributeError(name)
+
+    @property
+    def point_group(self):
+        """Hermann-Mauguin symbols; "" where the classes are those of no point group or the crystal was not analysed."""
+        return [POINT_GROUPS[i] for i in self.host()[:, 4]]
+
+    @property
+    def crystal_system_name(self):
+        return [CRYSTAL_SYSTEMS[i] for i in self.host()[:, 5]]
+
+    def operations(self, i):
+        """(W [k, 3, 3] int, t [k, 3], dev [k]) of crystal i in the basis of its reduced cell: f' = wrap(f W^-1 + t); k = min(n_ops, 192)."""
+        k = min(int(self.host()[i, 0]), _lib.SYM_MAX_OPS)
+        return self.rot[i, :k].reshape(k, 3, 3).cpu().numpy(), self.trans[i, :k].cpu().numpy(), self.dev[i, :k].cpu().numpy()
+
+
+def find_symmetry_prepared(prepared, tol, angle_tol=ANGLE_TOL, fill=None):
+    """mi_sym_find on a prepared set (matching.Prepared) and its tolerances (float64 [B], the prepared set's units).  `fill` builds the
+    output tensors (tests poison them)."""
+    lib = _lib.load()
+    dev = prepared.lat.device
+    B = prepared.B
+    tol = torch.as_tensor(np.asarray(tol, np.float64) if not torch.is_tensor(tol) else tol, dtype=torch.float64, device=dev).contiguous()
+    z = (lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)) if fill is None else fill
+    res = SymmetryResult(z((B, _lib.SYM_INFO), torch.int32), z((B, _lib.SYM_CLASSES), torch.int32), z((B, _lib.SYM_MAX_OPS, 9), torch.int32),
+                         z((B, _lib.SYM_MAX_OPS, 3), torch.float64), z((B, _lib.SYM_MAX_OPS), torch.float64), z((B, _lib.SYM_MAX_TRANS, 3), torch.float64), tol)
+    if B:
+        if tol.numel() != B:
+            raise ValueError(f"find_symmetry_prepared: {tol.numel()} tolerances for {B} crystals")
+        st = prepared.struct()
+        out = _lib.SymOut(*(t.data_ptr() for t in (res.info, res.rot_hist, res.rot, res.trans, res.dev, res.ptrans)))
+        _lib.check(lib.mi_sym_find(C.byref(st), tol.data_ptr(), math.cos(math.radians(float(angle_tol))), C.byref(out), torch.cuda.current_stream().cuda_stream),
+                   "mi_sym_find")
+    return res
+
+
+class Primitive:
+    """The arrays of mi_sym_primitive on the device: offsets [B + 1], types, frac [N, 3] float32 (the first offsets[B] rows), lat [B, 9]
+    float32, count, status [B], det [B]."""
+
+    def __init__(self, offsets, types, frac, lat, count, status, det):
+        self.offsets, self.types, self.frac, self.lat, self.count, self.status, self.det = offsets, types, frac, lat, count, status, det
+
+
+def primitive_arrays(prepared, types, frac, lat, sym, fill=None):
+    """mi_sym_primitive on device tensors: the prepared set, the arrays it was prepared from and the SymmetryResult of it."""
+    lib = _lib.load()
+    dev = prepared.lat.device
+    B, N = prepared.B, prepared.N
+    types, frac, lat = types.to(torch.int32).contiguous(), frac.to(torch.float32).contiguous(), lat.to(torch.float32).reshape(-1, 9).contiguous()
+    z = (lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)) if fill is None else fill
+    M = max(N, 1)
+    ws_types, ws_frac = torch.zeros(M, dtype=torch.int32, device=dev), torch.zeros((M, 3), dtype=torch.float32, device=dev)
+    out = Primitive(z((B + 1,), torch.int32), z((M,), torch.int32), z((M, 3), torch.float32), z((B, 9), torch.float32), z((B,), torch.int32),
+                    z((B,), torch.int32), z((B,), torch.float64))
+    if B:
+        p = lambda t: t.data_ptr()
+        args = _lib.SymPrimArgs(prepared.struct(), p(types), p(frac), p(lat), p(sym.info), p(sym.ptrans), p(ws_types), p(ws_frac), p(out.count), p(out.status),
+                                p(out.det), p(out.offsets), p(out.types), p(out.frac), p(out.lat))
+        _lib.check(lib.mi_sym_primitive(C.byref(args), torch.cuda.current_stream().cuda_stream), "mi_sym_primitive")
+    return out
+
+
+def _upload(records, device, symprec):
+    na, types, frac, lat = record_arrays(records)
+    offsets = torch.cat([torch.zeros(1, dtype=torch.long), na.cumsum(0)]).to(torch.int32)
+    dev = torch.device(device)
+    return na, offsets.to(dev), types.to(dev), frac.to(dev), lat.reshape(-1, 9).to(dev), tolerances(na.numpy(), lat.numpy(), symprec)
+
+
+def find_symmetry(records, symprec=SYMPREC, angle_tol=ANGLE_TOL, device="cuda"):
+    """The SymmetryResult of host records (SimpleStructure / CrystalData-like): one upload, two launches.  Never drops or reorders; a
+    record the prepare guard flags has status NOT_PREPARED and zero counts."""
+    na, offsets, types, frac, lat, tol = _upload(records, device, symprec)
+    prepared = matching.prepare_arrays(offsets, types, frac, lat)
+    return find_symmetry_prepared(prepared, tol, angle_tol)
+
+
+def reduce_arrays(offsets, types, frac, lat, tol, angle_tol=ANGLE_TOL):
+    """prepare -> mi_sym_find -> mi_sym_primitive on device tensors: (Primitive, SymmetryResult)."""
+    prepared = matching.prepare_arrays(offsets, types, frac, lat)
+    sym = find_symmetry_prepared(prepared, tol, angle_tol)
+    return primitive_arrays(prepared, types, frac, lat, sym), sym
+
+
+def primitive_records(records, symprec=SYMPREC, angle_tol=ANGLE_TOL, device="cuda"):
+    """(records, n_trans): every record in its primitive cell as a SimpleStructure (a record with one pure translation, or whose analysis
+    is not OK, keeps its cell and coordinates), and the number of pure translations found per record."""
+    from .data import SimpleStructure
+    if len(records) == 0:
+        return [], np.zeros(0, np.int64)
+    na, offsets, types, frac, lat, tol = _upload(records, device, symprec)
+    prim, sym = reduce_arrays(offsets, types, frac, lat, tol, angle_tol)
+    off, z, f, L = prim.offsets.cpu().numpy(), prim.types.cpu().numpy(), prim.frac.cpu().numpy(), prim.lat.cpu().numpy().reshape(-1, 3, 3).astype(np.float64)
+    out = []
+    for b in range(len(records)):
+        lengths = np.linalg.norm(L[b], axis=1)
+        cos = [float(np.dot(L[b][i], L[b][j]) / (lengths[i] * lengths[j])) for i, j in ((1, 2), (0, 2), (0, 1))]
+        angles = [math.degrees(math.acos(max(-1.0, min(1.0, c)))) for c in cos]
+        out.append(SimpleStructure([float(x) for x in lengths], angles, [int(v) for v in z[off[b]:off[b + 1]]], f[off[b]:off[b + 1]].astype(np.float64)))
+    return out, sym.n_trans.astype(np.int64)
