@@ -383,6 +383,33 @@ VIB_SIGNATURES = {
     "mi_vib_thermo": (_I, [C.POINTER(VibThermoArgs), _P]),
 }
 
+# the phonon extension, include/matinvent_hip_phonon.h (force constants from home-cell displacements in a supercell, dynamical matrices on a q-mesh)
+PHONON_MAX_PRIM, PHONON_IMAGES = 128, 27   # include/matinvent_hip_phonon.h
+
+
+class PhononFcArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("workspace", "ws_off", "node_off", "mass", "frac", "lat", "asym", "status")] +
+                [(k, C.c_double) for k in ("h", "tie_tol", "det_min")] + [("reps", C.c_int * 3), ("B", C.c_int), ("max_atoms", C.c_int)])
+
+
+class PhononDynmatArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("workspace", "ws_off", "node_off", "mass", "fc_status", "table", "item_crystal", "item_q", "mats", "mat_off", "sizes",
+                                           "herm")] + [("table_len", C.c_int64), ("reps", C.c_int * 3)] + [(k, C.c_int) for k in ("B", "Q", "T")])
+
+
+class PhononThermoArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("evals", "ev_off", "sizes", "eig_status", "sweeps", "herm_item", "fc_status", "item_off", "item_q", "weight", "lam",
+                                           "freqs", "c_v", "zpe", "n_imag", "n_zero", "min_freq", "min_q", "herm", "pair_gap", "sweeps_max", "status")] +
+                [("temps", C.c_double * 8), ("nu_cut", C.c_double)] + [(k, C.c_int) for k in ("B", "K", "Q")])
+
+
+PHONON_SIGNATURES = {
+    "mi_phonon_workspace": (_L, [C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_L)]),
+    "mi_phonon_fc": (_I, [C.POINTER(PhononFcArgs), _P]),
+    "mi_phonon_dynmat": (_I, [C.POINTER(PhononDynmatArgs), _P]),
+    "mi_phonon_thermo": (_I, [C.POINTER(PhononThermoArgs), _P]),
+}
+
 # the elasticity extension, include/matinvent_hip_elastic.h (the elastic tensor and moduli of the predictor read as an energy)
 ELASTIC_OK, ELASTIC_BAD_INPUT, ELASTIC_SINGULAR = 0, 1, 2   # include/matinvent_hip_elastic.h
 ELASTIC_COPIES, ELASTIC_ROW = 13, 8
@@ -450,7 +477,7 @@ SYM_SIGNATURES = {
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, SYM_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, SYM_SIGNATURES, PHONON_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
                         PRETRAIN_SIGNATURES)
 
 _lib = None

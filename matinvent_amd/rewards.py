@@ -1,7 +1,7 @@
 """Rewards with the `Reward.scoring` return contract (rewards/reward.py:8-115 returns (rewards, prop_dict, failed_mask)): the synthetic
 reward that benchmarks and smoke runs use, the reference's scalarisation `Reward`, and the calculators that run on this library --
 `Surrogate` (a trained property predictor), `EAboveHull` (the energy above the convex hull), `HeatCapacity` (the
-harmonic heat capacity of a predictor read as an energy, the reference's rewards/calculators/fairchem/phonon.py), `Elastic`
+harmonic heat capacity of a predictor read as an energy, the reference's rewards/calculators/fairchem/phonon.py; DESIGN 47, and from a q-mesh with method="mesh": DESIGN 51), `Elastic`
 (the bulk, shear and Young's modulus, Poisson's ratio and the Pugh ratio from the elastic tensor of a predictor read as an energy, the
 reference's rewards/calculators/fairchem/elastic.py), `Symmetry` (the operation count, point-group order or crystal system of
 the symmetry finder) and `PyMatGen` (density, HHI).  The energies behind EAboveHull,
@@ -161,10 +161,17 @@ class HeatCapacity:
     (eV; per atom with per_atom).  NaN (-> failed -> reward 0) on any status other than OK and, with require_stable, for a structure with
     an imaginary mode.  predictor: a loaded PropertyPredictor, or model_path: a directory written by predictor.save_predictor, loaded on
     first use.  relaxer (relax.Relaxer, or any strucs, path -> (strucs, energies)): the structures are relaxed first, as the reference
-    does.  The remaining keywords are vibrations.Vibrations' (delta, nu_cut, batch_size, supercell, det_min)."""
+    does.  The remaining keywords are vibrations.Vibrations' (delta, nu_cut, batch_size, supercell, det_min).
+    method = "mesh" (phonons.analyze_records) takes the heat capacity per primitive cell from a q-mesh instead: the supercell
+    ((a, b, c), or "auto" with min_length) is built around a displaced home cell, mesh = (m_a, m_b, m_c) is the Gamma-centred grid, the
+    remaining keywords are phonons.Phonons' (tie_tol and workspace_cap too), and require_stable fails a structure with an imaginary mode
+    anywhere on the mesh.  method = "gamma", the default, is the Gamma-point path above, unchanged."""
 
     def __init__(self, root_dir="rewards", predictor=None, model_path=None, task=None, temperature=300.0, relaxer=None, require_stable=False,
-                 supercell=(1, 1, 1), per_atom=True, device=None, **kwargs):
+                 supercell=(1, 1, 1), per_atom=True, device=None, method="gamma", mesh=(4, 4, 4), min_length=10.0, **kwargs):
+        if method not in ("gamma", "mesh"):
+            raise ValueError(f"HeatCapacity: method = {method!r}: \"gamma\" or \"mesh\"")
+        self.method = method
         if (model_path is None) == (predictor is None):
             raise ValueError("HeatCapacity: give exactly one of model_path (a save_predictor directory) and predictor (a loaded model)")
         if task is None:
@@ -173,7 +180,11 @@ class HeatCapacity:
             raise ValueError(f"HeatCapacity: temperature = {temperature}: must be finite and positive")
         self.root_dir, self.model_path, self.predictor, self.task, self.device = root_dir, model_path, predictor, str(task), device
         self.temperature, self.relaxer, self.require_stable = float(temperature), relaxer, bool(require_stable)
-        self.vib_kw = dict(kwargs, supercell=tuple(int(r) for r in supercell), per_atom=bool(per_atom))
+        if method == "mesh":
+            self.vib_kw = dict(kwargs, supercell=supercell if isinstance(supercell, str) else tuple(int(r) for r in supercell), per_atom=bool(per_atom),
+                               mesh=tuple(int(r) for r in mesh), min_length=float(min_length))
+        else:
+            self.vib_kw = dict(kwargs, supercell=tuple(int(r) for r in supercell), per_atom=bool(per_atom))
         self.vib, self.last = None, None
         if predictor is not None:
             self._analysis()
@@ -189,7 +200,11 @@ class HeatCapacity:
             if self.predictor is None:
                 from .predictor import load_predictor
                 self.predictor = load_predictor(self.model_path, device=self.device)
-            self.vib = Vibrations(self.predictor, self.task, temperatures=(self.temperature,), **self.vib_kw)
+            if self.method == "mesh":
+                from .phonons import Phonons
+                self.vib = Phonons(self.predictor, self.task, temperatures=(self.temperature,), **self.vib_kw)
+            else:
+                self.vib = Vibrations(self.predictor, self.task, temperatures=(self.temperature,), **self.vib_kw)
         return self.vib
 
     def calc(self, samples, label="tmp"):
@@ -199,7 +214,11 @@ class HeatCapacity:
             return np.zeros(0, dtype=float)
         if self.relaxer is not None:
             strucs, _ = self.relaxer(list(strucs), None)
-        res = vibrations.analyze_records(self._analysis(), list(strucs))
+        if self.method == "mesh":
+            from . import phonons
+            res = phonons.analyze_records(self._analysis(), list(strucs))
+        else:
+            res = vibrations.analyze_records(self._analysis(), list(strucs))
         self.last = res
         out = np.where(res["status"] == 0, res["c_v_gram"][:, 0], np.nan).astype(float)
         if self.require_stable:

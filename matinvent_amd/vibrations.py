@@ -12,7 +12,7 @@ THz, imaginary and zero counts, c_v(T), the zero-point energy).  Everything is e
 batch_size crystals) is read once, behind the next state's enqueue, so two workspaces are alive at most.
 
 supercell = (a, b, c) replicates a record on the host first: Gamma of the supercell samples the commensurate q-points of the cell.  The
-displaced set is NOT reduced by the supercell's translation symmetry (every atom of every image is displaced): out of scope here.
+displaced set is NOT reduced by the supercell's translation symmetry (every atom of every image is displaced): phonons.py does that.
 delta, nu_cut and det_min ship UNTUNED, and no weight of this repository is trained: nothing about the quality of a frequency or a heat
 capacity is claimed."""
 import ctypes as C
