@@ -474,10 +474,39 @@ SYM_SIGNATURES = {
     "mi_sym_primitive": (_I, [C.POINTER(SymPrimArgs), _P]),
 }
 
+# the substrate matcher, include/matinvent_hip_zsl.h (Zur-McGill superlattices, minimal coincident interface area)
+ZSL_MAX_MULT, ZSL_MAX_MILLER, ZSL_TABLE, ZSL_ROW_D, ZSL_ROW_I = 63, 8, 3276, 10, 20   # include/matinvent_hip_zsl.h
+ZSL_OK, ZSL_NO_MATCH, ZSL_MULT_CAP, ZSL_REDUCE_CAP, ZSL_BAD_CELL = 0, 1, 2, 3, 4
+
+
+class ZslPlanesArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("lat", "hkl", "cell_of")] + [("C", C.c_int), ("P", C.c_int), ("max_area", C.c_double)] +
+                [(k, C.c_void_p) for k in ("vec", "area", "mult", "status")])
+
+
+class ZslSearchArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("f_vec", "f_area", "f_mult", "f_status", "s_area", "s_mult", "s_status", "s_table")] +
+                [(k, C.c_int) for k in ("B", "Pf", "Ps", "count")] + [(k, C.c_double) for k in ("max_area_ratio_tol", "max_length_tol", "max_angle_tol")] +
+                [(k, C.c_void_p) for k in ("item_d", "item_i", "item_n")])
+
+
+class ZslReduceArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("item_d", "item_i", "item_n", "sub_off")] + [(k, C.c_int) for k in ("B", "Pf", "Ps", "S", "count")] +
+                [(k, C.c_void_p) for k in ("res_d", "res_i", "res_n", "mcia", "mcia_plane", "mcia_status")])
+
+
+ZSL_SIGNATURES = {
+    "mi_zsl_planes": (_I, [C.POINTER(ZslPlanesArgs), _P]),
+    "mi_zsl_workspace": (_L, [_I]),
+    "mi_zsl_tables": (_I, [_P, _P, _P, _I, _P, _P]),
+    "mi_zsl_search": (_I, [C.POINTER(ZslSearchArgs), _P]),
+    "mi_zsl_reduce": (_I, [C.POINTER(ZslReduceArgs), _P]),
+}
+
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, SYM_SIGNATURES, PHONON_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, SYM_SIGNATURES, ZSL_SIGNATURES, PHONON_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
                         PRETRAIN_SIGNATURES)
 
 _lib = None

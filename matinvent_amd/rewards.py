@@ -4,7 +4,7 @@ reward that benchmarks and smoke runs use, the reference's scalarisation `Reward
 harmonic heat capacity of a predictor read as an energy, the reference's rewards/calculators/fairchem/phonon.py; DESIGN 47, and from a q-mesh with method="mesh": DESIGN 51), `Elastic`
 (the bulk, shear and Young's modulus, Poisson's ratio and the Pugh ratio from the elastic tensor of a predictor read as an energy, the
 reference's rewards/calculators/fairchem/elastic.py), `Symmetry` (the operation count, point-group order or crystal system of
-the symmetry finder) and `PyMatGen` (density, HHI).  The energies behind EAboveHull,
+the symmetry finder) and `PyMatGen` (density, HHI, and the minimal coincident interface area on a substrate: DESIGN 52).  The energies behind EAboveHull,
 HeatCapacity and Elastic are a PropertyPredictor's, relaxed by relax.Relaxer: the reference's MLIP calculators (MatterSim, fairchem) themselves, ALIGNN and DFT stay out of scope (SURVEY.md section 2 rows
 11-12)."""
 import numpy as np
@@ -331,12 +331,29 @@ class PyMatGen:
     `density` (g/cm^3, :45-53).  `hhi` (:57-73) is the mass-fraction-weighted Herfindahl-Hirschman index of the elements'
     geological reserves; pymatgen ships that table as data (hhi.csv), which is not available offline -- pass `hhi_table`
     (CSV: symbol, HHI production, HHI reserve) to use it; without the table the task fails per sample (NaN -> reward 0, as the
-    reference's calculators do on error, :84-89)."""
+    reference's calculators do on error, :84-89).  `mcia` (:115-160) is the minimal coincident interface area (A^2) between each
+    structure and `substrate` on the device (matinvent_amd.substrates): `substrate` is a substrates.Substrate, a cell (six
+    parameters or a 3 x 3 matrix) or a file structure.read_extxyz reads -- no table of named substrates is shipped; `substrate_millers`
+    lists the substrate's planes (the reference uses (1, 0, 0) for Si, GaAs and InP), `zsl` holds substrates.ZSL arguments; NaN on any
+    status other than OK, as the reference's `except` branch does."""
 
-    def __init__(self, root_dir="rewards", task="density", hhi_table=None, **kwargs):
-        assert task in ("density", "hhi"), f"task {task!r} needs pymatgen / SMACT data that this build does not carry"
+    def __init__(self, root_dir="rewards", task="density", hhi_table=None, substrate=None, substrate_millers=None, zsl=None, primitive=False, device="cuda", **kwargs):
+        assert task in ("density", "hhi", "mcia"), f"task {task!r} needs pymatgen / SMACT data that this build does not carry"
         self.root_dir, self.task = root_dir, task
         self.hhi = None
+        if task == "mcia":
+            import os
+            from . import substrates
+            if substrate is None or isinstance(substrate, str) and not os.path.exists(substrate):
+                raise ValueError(f"task 'mcia' needs substrate= as a Substrate, a cell or a file (got {substrate!r}): no table of named substrates is shipped")
+            self.zsl = substrates.ZSL(**dict(zsl or {}))
+            if isinstance(substrate, substrates.Substrate):
+                if substrate_millers is not None:
+                    raise ValueError("substrate_millers goes with a cell or a file: a Substrate carries its own planes")
+                self.substrate = substrate
+            else:
+                self.substrate = substrates.Substrate("substrate", substrate, substrate_millers)
+            self.primitive, self.device, self.bank = bool(primitive), device, None
         if hhi_table is not None:
             import csv
             with open(hhi_table) as f:
@@ -345,6 +362,12 @@ class PyMatGen:
     def calc(self, samples, label="tmp"):
         from .structure import MASSES, SYMBOLS, density
         strucs = samples[0] if isinstance(samples, tuple) else samples
+        if self.task == "mcia":
+            from . import substrates
+            if self.bank is None:   # the tables are built once, at the first call
+                self.bank = substrates.SubstrateBank([self.substrate], self.zsl, self.device)
+            area, status = substrates.mcia(list(strucs), self.bank, self.zsl, primitive=self.primitive, device=self.device)
+            return np.where(status == 0, area, np.nan).astype(float)
         out = []
         for s in strucs:
             try:
