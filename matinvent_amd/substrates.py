@@ -251,11 +251,25 @@ def record_cells(records):
     return out
 
 
-def match_records(zsl, records, bank, count=False, primitive=False, device=None):
+def _has_atoms(r):
+    return hasattr(r, "lengths") and (hasattr(r, "species") or hasattr(r, "atom_types"))
+
+
+def match_records(zsl, records, bank, count=False, primitive=False, device=None, conventional=False):
     """The MatchResult of host records against a bank: one upload, the launches, one read at the end (MatchResult.host).  Never drops or
-    reorders records.  primitive=True runs symmetry.primitive_records on the films first (a record it cannot analyse keeps its cell)."""
+    reorders records.  primitive=True runs symmetry.primitive_records on the films first (a record it cannot analyse keeps its cell);
+    conventional=True runs symmetry.conventional_records on them instead, so that the planes are indexed in the conventional
+    cell whatever cell the film arrived in.  The two exclude each other."""
+    if primitive and conventional:
+        raise ValueError("match_records: primitive=True and conventional=True exclude each other: the planes are indexed in one cell")
     dev = torch.device(device) if device is not None else bank.device
     records = list(records)
+    if conventional and records:
+        from . import symmetry
+        good = [k for k, r in enumerate(records) if _has_atoms(r)]
+        conv, _ = symmetry.conventional_records([records[k] for k in good], device=dev)
+        for k, s in zip(good, conv):
+            records[k] = s
     if primitive and records:
         from . import symmetry
         good = [k for k, r in enumerate(records) if hasattr(r, "lengths") and (hasattr(r, "species") or hasattr(r, "atom_types"))]
@@ -267,9 +281,16 @@ def match_records(zsl, records, bank, count=False, primitive=False, device=None)
     return res
 
 
-def mcia(records, substrate, zsl=None, primitive=False, device="cuda"):
-    """The one-substrate shortcut: (mcia [B] in A^2, +inf where nothing matches; status [B]) of the records on one substrate."""
+def mcia(records, substrate, zsl=None, primitive=False, device="cuda", conventional=False):
+    """The one-substrate shortcut: (mcia [B] in A^2, +inf where nothing matches; status [B]) of the records on one substrate.  With
+    conventional=True a substrate given as a record with atoms is put into its conventional cell like the films; a bare cell, a Substrate
+    or a bank is taken as given."""
+    if primitive and conventional:
+        raise ValueError("mcia: primitive=True and conventional=True exclude each other: the planes are indexed in one cell")
     zsl = zsl or ZSL()
+    if conventional and _has_atoms(substrate):
+        from . import symmetry
+        substrate = symmetry.conventional_records([substrate], device=device)[0][0]
     bank = substrate if isinstance(substrate, SubstrateBank) else SubstrateBank([substrate], zsl, device)
-    res = match_records(zsl, records, bank, primitive=primitive, device=device)
+    res = match_records(zsl, records, bank, primitive=primitive, device=device, conventional=conventional)
     return res.mcia[:, 0], res.mcia_status[:, 0]

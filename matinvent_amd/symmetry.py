@@ -2,8 +2,13 @@
 run on (b, b) with a rigid metric, a nearest-atom test and every accepted (map, translation) item kept.  symprec = 0.1 A is the
 reference's value (SpacegroupAnalyzer(symprec=0.1)); angle_tol = 5 degrees is the matcher's and is untuned -- spglib's own lattice rule is
 [UPSTREAM-UNVERIFIED] and is not reproduced, and agreement with spglib is unverified (it is absent here).  Not built: the space-group
-number or Hall symbol, refined or standardised conventional cells, Wyckoff positions, symmetry reduction of the vibration or elastic
-displacement sets, magnetic and disordered structures."""
+number or Hall symbol, Wyckoff positions, idealised cell parameters, symmetry reduction of the vibration or elastic displacement sets,
+magnetic and disordered structures.
+
+The conventional cell (include/matinvent_hip_sym_conv.h): conventional_arrays / conventional_records reduce every crystal to
+its primitive cell, analyse that again and build the conventional basis, the centring and the Bravais lattice from the rotation parts.
+The rules are this build's own; pymatgen's get_conventional_standard_structure and spglib's standardisation are [UPSTREAM-UNVERIFIED]
+(both are absent here) and are not claimed to be reproduced beyond them."""
 import ctypes as C
 import math
 
@@ -20,6 +25,9 @@ POINT_GROUPS = ("", "1", "-1", "2", "m", "2/m", "222", "mm2", "mmm", "4", "-4", 
                 "6/m", "622", "6mm", "-6m2", "6/mmm", "23", "m-3", "432", "-43m", "m-3m")
 CRYSTAL_SYSTEMS = ("", "triclinic", "monoclinic", "orthorhombic", "tetragonal", "trigonal", "hexagonal", "cubic")
 INFO = ("n_ops", "n_trans", "n_maps", "pg_order", "pg_index", "crystal_system", "has_inversion", "status")
+BRAVAIS = ("", "aP", "mP", "mS", "oP", "oS", "oI", "oF", "tP", "tI", "hR", "hP", "cP", "cI", "cF")
+CENTRINGS = ("", "P", "A", "B", "C", "I", "F", "R")
+CONV_INFO = ("bravais", "centring", "mult", "crystal_system", "n_axes", "max_m", "zero", "status")
 
 
 def tolerances(num_atoms, lattices, symprec=SYMPREC):
@@ -158,3 +166,90 @@ def primitive_records(records, symprec=SYMPREC, angle_tol=ANGLE_TOL, device="cud
         angles = [math.degrees(math.acos(max(-1.0, min(1.0, c)))) for c in cos]
         out.append(SimpleStructure([float(x) for x in lengths], angles, [int(v) for v in z[off[b]:off[b + 1]]], f[off[b]:off[b + 1]].astype(np.float64)))
     return out, sym.n_trans.astype(np.int64)
+
+
+# ---- the conventional cell ----------------------------------------------------------------------------------------------------------
+class Conventional:
+    """The arrays of mi_sym_conventional on the device: info [B, 8], M [B, 9], cvec [B, 4, 3], count [B], offsets [B + 1], types [4 N], frac
+    [4 N, 3] float32 (the first offsets[B] rows), lat [B, 9] float32."""
+
+    def __init__(self, info, M, cvec, count, offsets, types, frac, lat):
+        self.info, self.M, self.cvec, self.count, self.offsets, self.types, self.frac, self.lat = info, M, cvec, count, offsets, types, frac, lat
+
+
+def conventional_prepared(prepared, types, frac, lat, sym, fill=None):
+    """mi_sym_conventional on device tensors: the prepared set of the primitive crystals, the arrays it was prepared from and the
+    SymmetryResult of it.  `fill` builds the output tensors (tests poison them)."""
+    lib = _lib.load()
+    dev = prepared.lat.device
+    B, N = prepared.B, prepared.N
+    types, frac, lat = types.to(torch.int32).contiguous(), frac.to(torch.float32).contiguous(), lat.to(torch.float32).reshape(-1, 9).contiguous()
+    z = (lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)) if fill is None else fill
+    rows = max(4 * N, 1)
+    ws_adj = torch.zeros((B, 9), dtype=torch.int32, device=dev)
+    out = Conventional(z((B, _lib.SYM_CONV_INFO), torch.int32), z((B, 9), torch.int32), z((B, _lib.SYM_CONV_MAX_MULT, 3), torch.int32), z((B,), torch.int32),
+                       z((B + 1,), torch.int32), z((rows,), torch.int32), z((rows, 3), torch.float32), z((B, 9), torch.float32))
+    if B:
+        p = lambda t: t.data_ptr()
+        args = _lib.SymConvArgs(prepared.struct(), p(types), p(frac), p(lat), p(sym.info), p(sym.rot), p(ws_adj), p(out.info), p(out.M), p(out.cvec), p(out.count),
+                                p(out.offsets), p(out.types), p(out.frac), p(out.lat))
+        _lib.check(lib.mi_sym_conventional(C.byref(args), torch.cuda.current_stream().cuda_stream), "mi_sym_conventional")
+    return out
+
+
+def conventional_arrays(offsets, types, frac, lat, tol, angle_tol=ANGLE_TOL):
+    """prepare -> mi_sym_find -> mi_sym_primitive -> prepare -> mi_sym_find -> mi_sym_conventional on device tensors, nothing read back
+    between them: (Conventional, SymmetryResult of the primitive crystals).  The second analysis runs with the first one's tolerances: they
+    are in the prepared set's units (unit volume per atom), which the primitive cell keeps."""
+    prim, _ = reduce_arrays(offsets, types, frac, lat, tol, angle_tol)
+    prepared = matching.prepare_arrays(prim.offsets, prim.types, prim.frac, prim.lat)
+    sym = find_symmetry_prepared(prepared, tol, angle_tol)
+    return conventional_prepared(prepared, prim.types, prim.frac, prim.lat, sym), sym
+
+
+class ConventionalResult:
+    """Per record, as numpy: bravais (Pearson-style strings, "" where there is no conventional cell), bravais_index (1 .. 14, 0), centring
+    ("P", "A", "B", "C", "I", "F", "R", ""), mult, crystal_system, M [B, 3, 3] (the conventional vectors in the reduced primitive basis),
+    status (the find status of the primitive crystal, with SYM_CONV_FAIL = 512 where the record came back as it was) and cell_parameters
+    [B, 6] (a, b, c, alpha, beta, gamma of the returned records)."""
+
+    def __init__(self, info, M, cell_parameters):
+        self.info = info
+        self.bravais_index, self.mult, self.crystal_system, self.status = (info[:, k].copy() for k in (0, 2, 3, 7))
+        self.bravais = [BRAVAIS[i] for i in info[:, 0]]
+        self.centring = [CENTRINGS[i] for i in info[:, 1]]
+        self.M, self.cell_parameters = M, cell_parameters
+
+    def __len__(self):
+        return len(self.info)
+
+
+def _parameters(L):
+    lengths = np.linalg.norm(L, axis=1)
+    cos = [float(np.dot(L[i], L[j]) / (lengths[i] * lengths[j])) for i, j in ((1, 2), (0, 2), (0, 1))]
+    return [float(x) for x in lengths], [math.degrees(math.acos(max(-1.0, min(1.0, c)))) for c in cos]
+
+
+def conventional_records(records, symprec=SYMPREC, angle_tol=ANGLE_TOL, device="cuda"):
+    """(records, ConventionalResult): every record in its conventional cell as a SimpleStructure.  Never drops or reorders; a record
+    without a conventional cell (any status but OK) comes back as it was."""
+    from .data import SimpleStructure
+    if len(records) == 0:
+        return [], ConventionalResult(np.zeros((0, _lib.SYM_CONV_INFO), np.int32), np.zeros((0, 3, 3), np.int32), np.zeros((0, 6)))
+    na, offsets, types, frac, lat, tol = _upload(records, device, symprec)
+    conv, _ = conventional_arrays(offsets, types, frac, lat, tol, angle_tol)
+    info, M = conv.info.cpu().numpy(), conv.M.cpu().numpy().reshape(-1, 3, 3)
+    off, z, f, L = conv.offsets.cpu().numpy(), conv.types.cpu().numpy(), conv.frac.cpu().numpy(), conv.lat.cpu().numpy().reshape(-1, 3, 3).astype(np.float64)
+    out, params = [], np.full((len(records), 6), np.nan)
+    for b, rec in enumerate(records):
+        if info[b, 7] != _lib.SYM_OK or info[b, 0] == 0:
+            out.append(rec)
+            try:
+                params[b] = list(np.asarray(rec.lengths, np.float64).reshape(-1)) + list(np.asarray(rec.angles, np.float64).reshape(-1))
+            except Exception:
+                pass
+            continue
+        lengths, angles = _parameters(L[b])
+        params[b] = lengths + angles
+        out.append(SimpleStructure(lengths, angles, [int(v) for v in z[off[b]:off[b + 1]]], f[off[b]:off[b + 1]].astype(np.float64)))
+    return out, ConventionalResult(info, M, params)

@@ -14,7 +14,7 @@ B.build(verbose=False)   # the default objects
 vdir = os.path.join(B.HERE, "lib", "variants")
 os.makedirs(vdir, exist_ok=True)
 objs = []
-for src in B.SOURCES:
+for src in B.ALL_SOURCES:
     obj = os.path.join(B.OBJ, src.replace(".hip", ".o"))
     if src in units:
         obj = os.path.join(vdir, f"{name}_{src.replace('.hip', '.o')}")

@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from matinvent_amd.build import ARCH, CSRC, NO_PACKED_FP32, SOURCES  # noqa: E402
+from matinvent_amd.build import ARCH, CSRC, NO_PACKED_FP32, ALL_SOURCES as SOURCES  # noqa: E402
 
 want = sys.argv[1:]
 W = 12

@@ -10,7 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from matinvent_amd.build import ARCH, CSRC, NO_PACKED_FP32, SOURCES  # noqa: E402
+from matinvent_amd.build import ARCH, CSRC, NO_PACKED_FP32, ALL_SOURCES as SOURCES  # noqa: E402
 
 minlen = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 tmp = tempfile.mkdtemp()
