@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include <stdio.h>
 #include <string>
 #include <vector>
@@ -66,6 +67,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+static inline bool pos_finite(double v) { return std::isfinite(v) && v > 0.0; }   // (the entries' host-side checks of steps, scales and temperatures)
 
 // ---- device math ----------------------------------------------------------------------
 // torch.nn.functional.silu: x / (1 + exp(-x))

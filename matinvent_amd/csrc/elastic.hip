@@ -7,22 +7,21 @@
 // csrc/elastic_fit.h holds every formula, host and device.  mi_elastic_run_chunk enqueues strain, the ion relaxation (mi_relax_init and
 // mi_relax_run at a fixed cell) when it is asked for, mi_scalar_input_grad and collect on one stream.
 
+#include <climits>
 #include <cmath>
 
 #include "../../include/matinvent_hip_elastic.h"
 #include "elastic_fit.h"
+#include "energy_chunk.h"
 #include "net.h"
 
 namespace mi {
-
-extern int g_edge_pairs;   // cspnet.hip (mi_set_edge_pairs)
 
 static_assert(ELASTIC_OK == MI_ELASTIC_OK && ELASTIC_BAD_INPUT == MI_ELASTIC_BAD_INPUT && ELASTIC_SINGULAR == MI_ELASTIC_SINGULAR, "status codes");
 static_assert(ELASTIC_COPIES == MI_ELASTIC_COPIES && ELASTIC_ROW == MI_ELASTIC_ROW && RELAX_NI == MI_RELAX_NI, "sizes");
 static_assert(RELAX_CONVERGED == MI_RELAX_CONVERGED && RELAX_FAILED == MI_RELAX_FAILED && RELAX_EXHAUSTED == MI_RELAX_EXHAUSTED, "relaxation codes");
 
 constexpr int ELA_THREADS = 256;
-constexpr int ELA_TYPE_COLS = 100;   // the type rows' width (matinvent_hip_scalar.h): 25 float4
 
 struct ElasticChunk {
     mi_elastic_chunk_args a;
@@ -31,23 +30,16 @@ struct ElasticChunk {
     int relaxed;           // non-zero: a.istate is read
 };
 
-// the plan entry of copy k: its source crystal, copy index and atom count; false: the entry is not admissible
+// the plan entry of copy k (energy_chunk.h): ELASTIC_COPIES copies of a crystal of any size
 __device__ __forceinline__ bool ela_plan(const ElasticChunk& A, int k, int* src, int* c, int* n, int* s0, int* c0) {
-    *src = A.a.plan_src[k], *c = A.a.plan_copy[k];
-    if (*src < 0 || *src >= A.a.Bs) return false;
-    *s0 = A.a.src_node_off[*src];
-    *n = A.a.src_node_off[*src + 1] - *s0;
-    *c0 = A.node_off[k];
-    return *n >= 1 && A.node_off[k + 1] - *c0 == *n && *c >= 0 && *c < ELASTIC_COPIES;
+    return chunk_plan_entry(A.a.plan_src, A.a.plan_copy, A.a.Bs, A.a.src_node_off, A.node_off, k, 0, ELASTIC_COPIES, INT_MAX, src, c, n, s0, c0);
 }
 
 __global__ __launch_bounds__(ELA_THREADS) void elastic_strain_kernel(ElasticChunk A) {
     const int k = blockIdx.x, tid = threadIdx.x;
     int src, c, n, s0, c0;
     if (!ela_plan(A, k, &src, &c, &n, &s0, &c0)) return;   // (uniform)
-    const float4* ts = reinterpret_cast<const float4*>(A.a.src_types + (size_t)s0 * ELA_TYPE_COLS);
-    float4* td = reinterpret_cast<float4*>(A.a.types + (size_t)c0 * ELA_TYPE_COLS);
-    for (int i = tid; i < n * (ELA_TYPE_COLS / 4); i += ELA_THREADS) td[i] = ts[i];
+    chunk_copy_types(A.a.src_types, A.a.types, s0, c0, n, tid, ELA_THREADS);
     const float* xs = A.a.src_frac + (size_t)s0 * 3;
     float* xd = A.a.frac + (size_t)c0 * 3;
     for (int i = tid; i < n * 3; i += ELA_THREADS) xd[i] = xs[i];
@@ -84,21 +76,8 @@ __global__ __launch_bounds__(64) void elastic_fit_kernel(mi_elastic_fit_args a) 
     if (o.status == ELASTIC_BAD_INPUT) a.asym[b] = jac_nan();
 }
 
-static bool ela_pos_finite(double v) { return std::isfinite(v) && v > 0.0; }
-
 static int ela_chunk_check(const char* what, const mi_batch* b, const mi_elastic_chunk_args* q) {
-    MI_CHECK(b, MI_EINVAL, "%s: null handle", what);
-    MI_CHECK(q, MI_EINVAL, "%s: null argument block", what);
-    MI_NO_POOLED(b, "mi_elastic");
-    MI_CHECK(ela_pos_finite(q->h) && ela_pos_finite(q->scale) && ela_pos_finite(q->det_min), MI_EINVAL,
-             "%s: h = %g, scale = %g, det_min = %g: each must be finite and positive", what, q->h, q->scale, q->det_min);
-    MI_CHECK(q->Bs >= 0, MI_EINVAL, "%s: Bs = %d", what, q->Bs);
-    if (b->B == 0 || b->N == 0) return MI_OK;
-    MI_CHECK(q->src_types && q->src_frac && q->src_lat && q->src_node_off && q->plan_src && q->plan_copy && q->types && q->frac && q->lat && q->g_lat &&
-                 q->workspace && q->asym,
-             MI_EINVAL, "%s: null argument", what);
-    MI_CHECK((((uintptr_t)q->types | (uintptr_t)q->src_types) & 15) == 0, MI_EINVAL, "%s: the type rows must be 16-byte aligned", what);
-    return MI_OK;
+    return energy_chunk_check(what, "mi_elastic", b, q, q && q->g_lat && q->asym);
 }
 
 static int strain_launch(mi_batch* b, const mi_elastic_chunk_args* q, hipStream_t s) {
@@ -137,21 +116,13 @@ int mi_elastic_run_chunk(mi_net* net, mi_batch* b, const mi_elastic_chunk_args* 
                          const float* time_freqs, const float* W, const float* bias, int P, int p, float* d_out, float* out, float* vel_x,
                          float* fstate, void* stream) {
     const char* what = "mi_elastic_run_chunk";
-    // mi_scalar_input_grad's refusals, by name, here: the strain launch goes first, and nothing may be enqueued in front of a refusal
-    // (its hidden_dim cap alone stays its own: a refusal there leaves a written chunk state and nothing else behind)
+    // mi_scalar_input_grad's refusals, by name, here (input_grad_refusals): the strain launch goes first, and nothing may be enqueued in
+    // front of a refusal (its hidden_dim cap alone stays its own: a refusal there leaves a written chunk state and nothing else behind)
     MI_NO_LATENT(net, "mi_elastic_run_chunk");
     MI_NO_POOLED(b, "mi_elastic_run_chunk");
     MI_CHECK(net, MI_EINVAL, "%s: null network", what);
     MI_TRY(ela_chunk_check(what, b, args));
-    MI_CHECK(!b->knn, MI_EINVAL, "%s: a knn-style handle (the input gradient runs in the fully connected pair mode only)", what);
-    MI_CHECK(g_edge_pairs && net->H % 4 == 0, MI_EINVAL, "%s: pair mode is off or hidden_dim %% 4 != 0 (the input gradient runs in pair mode only)", what);
-    MI_CHECK(b->tape.wslots == 0, MI_EINVAL, "%s: the handle has an open weight-gradient window (mi_batch_set_wgrad_window(.., 0) first)", what);
-    MI_CHECK(b->H == net->H && b->L == net->L, MI_EINVAL, "%s: batch was created for a different network", what);
-    MI_CHECK(!b->time_map, MI_EINVAL, "%s: the handle carries a time map (the predictor runs on the trained grid)", what);
-    MI_CHECK(!b->cond_on && !b->lik_on, MI_EINVAL, "%s: the handle carries a condition or a likelihood mask", what);
-    MI_CHECK(!b->gd_on, MI_EINVAL, "%s: the handle carries guidance (mi_batch_clear_guidance first)", what);
-    MI_CHECK(b->tape.wcur == 0, MI_EINVAL, "%s: the handle has pending deferred weight gradients (mi_cspnet_wgrad_flush first)", what);
-    MI_CHECK(net->W2T != nullptr, MI_ESTATE, "%s: mi_net_set_params must run before backward", what);
+    MI_TRY(input_grad_refusals(what, net, b));
     MI_CHECK(P >= 1 && p >= 0 && p < P, MI_EINVAL, "%s: property p = %d of P = %d", what, p, P);
     MI_CHECK(ion_steps >= 0, MI_EINVAL, "%s: ion_steps = %d", what, ion_steps);
     mi_relax_params rp{};
@@ -187,7 +158,7 @@ int mi_elastic_fit(const mi_elastic_fit_args* args, void* stream) {
     MI_CHECK(args, MI_EINVAL, "mi_elastic_fit: null argument block");
     const mi_elastic_fit_args& a = *args;
     MI_CHECK(a.B >= 0, MI_EINVAL, "mi_elastic_fit: B = %d", a.B);
-    MI_CHECK(ela_pos_finite(a.h), MI_EINVAL, "mi_elastic_fit: h = %g: must be finite and positive", a.h);
+    MI_CHECK(pos_finite(a.h), MI_EINVAL, "mi_elastic_fit: h = %g: must be finite and positive", a.h);
     if (a.B == 0) return MI_OK;
     MI_CHECK(a.workspace && a.C && a.S && a.stress0 && a.pressure && a.asym && a.asym_C && a.moduli && a.evals && a.cond && a.n_negative && a.n_unrelaxed &&
                  a.status,

@@ -221,6 +221,22 @@ int input_grad_finish(mi_net* net, mi_batch* b, const InputGradOut* ig, const fl
     return MI_OK;
 }
 
+// the refusals below that need no launch, under a caller's name (net.h): mi_scalar_input_grad's knn, pair-mode and window lines, then
+// scalar_run's (scalar_head.hip) network / batch mismatch, time map, condition or likelihood mask, guidance, pending weight gradients and
+// W2T lines, in the order the two raise them.  Those stay the source of truth; a refusal added there belongs here too.
+int input_grad_refusals(const char* what, const mi_net* net, const mi_batch* b) {
+    MI_CHECK(!b->knn, MI_EINVAL, "%s: a knn-style handle (the input gradient runs in the fully connected pair mode only)", what);
+    MI_CHECK(g_edge_pairs && net->H % 4 == 0, MI_EINVAL, "%s: pair mode is off or hidden_dim %% 4 != 0 (the input gradient runs in pair mode only)", what);
+    MI_CHECK(b->tape.wslots == 0, MI_EINVAL, "%s: the handle has an open weight-gradient window (mi_batch_set_wgrad_window(.., 0) first)", what);
+    MI_CHECK(b->H == net->H && b->L == net->L, MI_EINVAL, "%s: batch was created for a different network", what);
+    MI_CHECK(!b->time_map, MI_EINVAL, "%s: the handle carries a time map (the predictor runs on the trained grid)", what);
+    MI_CHECK(!b->cond_on && !b->lik_on, MI_EINVAL, "%s: the handle carries a condition or a likelihood mask", what);
+    MI_CHECK(!b->gd_on, MI_EINVAL, "%s: the handle carries guidance (mi_batch_clear_guidance first)", what);
+    MI_CHECK(b->tape.wcur == 0, MI_EINVAL, "%s: the handle has pending deferred weight gradients (mi_cspnet_wgrad_flush first)", what);
+    MI_CHECK(net->W2T != nullptr, MI_ESTATE, "%s: mi_net_set_params must run before backward", what);
+    return MI_OK;
+}
+
 }  // namespace mi
 
 using namespace mi;

@@ -368,11 +368,31 @@ inline hipError_t batch_memset(const mi_batch* b, void* p, int v, size_t bytes) 
 }
 // the one-line checks of the entries: a pooled handle where none is taken; a pooled handle used on another stream than its pool's
 #define MI_NO_POOLED(b, what) \
-    MI_CHECK(!(b) || !(b)->pool, MI_EINVAL, what ": a pooled batch handle is not taken here (include/matinvent_hip_pool.h lists the entries that take one)")
+    MI_CHECK(!(b) || !(b)->pool, MI_EINVAL, "%s: a pooled batch handle is not taken here (include/matinvent_hip_pool.h lists the entries that take one)", what)
 #define MI_NO_LATENT(net, what) \
     MI_CHECK(!(net) || (net)->Z == 0, MI_EINVAL, what ": the network has a property-conditioned embedding (mi_net_set_latent), which this entry does not fill (include/matinvent_hip_guidance.h lists the entries that do)")
 #define MI_POOL_STREAM(b, stream, what) \
     MI_CHECK(!(b) || !(b)->pool || mi::pool_stream((b)->pool) == (hipStream_t)(stream), MI_EINVAL, what ": a pooled batch handle is used on its pool's stream only")
+// input_grad.hip: the host-side refusals of the input-gradient path that need no launch, under the caller's name (MI_EINVAL / MI_ESTATE with the
+// message set; net and b are not NULL): for an entry that enqueues work of its own in front of mi_scalar_input_grad (vib.hip, elastic.hip)
+int input_grad_refusals(const char* what, const mi_net* net, const mi_batch* b);
+// vib.hip, elastic.hip: the host-side check of a chunk's argument block over the fields mi_vib_chunk_args and mi_elastic_chunk_args share;
+// family names the unit in the pooled-handle refusal, own_pointers is the unit's own non-null condition (read only where pointers are)
+template <class Args>
+int energy_chunk_check(const char* what, const char* family, const mi_batch* b, const Args* q, bool own_pointers) {
+    MI_CHECK(b, MI_EINVAL, "%s: null handle", what);
+    MI_CHECK(q, MI_EINVAL, "%s: null argument block", what);
+    MI_NO_POOLED(b, family);
+    MI_CHECK(pos_finite(q->h) && pos_finite(q->scale) && pos_finite(q->det_min), MI_EINVAL, "%s: h = %g, scale = %g, det_min = %g: each must be finite and positive",
+             what, q->h, q->scale, q->det_min);
+    MI_CHECK(q->Bs >= 0, MI_EINVAL, "%s: Bs = %d", what, q->Bs);
+    if (b->B == 0 || b->N == 0) return MI_OK;
+    MI_CHECK(q->src_types && q->src_frac && q->src_lat && q->src_node_off && q->plan_src && q->plan_copy && q->types && q->frac && q->lat && q->workspace &&
+                 own_pointers,
+             MI_EINVAL, "%s: null argument", what);
+    MI_CHECK((((uintptr_t)q->types | (uintptr_t)q->src_types) & 15) == 0, MI_EINVAL, "%s: the type rows must be 16-byte aligned", what);
+    return MI_OK;
+}
 // pretrain.hip: the supervised micro-step's sequence -- time gather, the EMBEDDING STAGE, noising, the network, loss, statistics, backward --
 // with the embedding stage passed in: it fills b->temb [B][TD] from b->times on `s`.  mi_pretrain_micro_step's stage is the time embedding
 // (pretrain.hip), mi_pretrain_micro_step_cond's the crystal embedding with condition dropout (guidance.hip).

@@ -12,7 +12,7 @@
 #include <cmath>
 
 #include "../../include/matinvent_hip_phonon.h"
-#include "common.h"
+#include "energy_chunk.h"
 #include "phonon_fc.h"
 
 namespace mi {
@@ -21,22 +21,6 @@ static_assert(PH_MAX_PRIM == MI_PHONON_MAX_PRIM && PH_IMAGES == MI_PHONON_IMAGES
 static_assert(VIB_OK == MI_VIB_OK && VIB_BAD_INPUT == MI_VIB_BAD_INPUT && VIB_NO_CONVERGENCE == MI_VIB_NO_CONVERGENCE, "status codes");
 
 constexpr int PH_THREADS = 256;
-
-// the block's maximum of v (finite, >= 0): exact, so no order to fix
-__device__ __forceinline__ double ph_block_max(double v, double* red, int tid) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double o = __shfl_xor(v, m, 64);
-        v = o > v ? o : v;
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    v = red[0];
-#pragma unroll
-    for (int w = 1; w < PH_THREADS / 64; ++w) v = red[w] > v ? red[w] : v;
-    return v;
-}
 
 // the primitive cell's atom count of a supercell of Ns atoms; 0: not admissible
 __device__ __forceinline__ int ph_prim_atoms(int Ns, int N, int max_atoms) {
@@ -82,8 +66,8 @@ __global__ __launch_bounds__(PH_THREADS) void phonon_fc_kernel(mi_phonon_fc_args
         const double x = fabs(Phi[i]), y = fabs(Phi[i] - Phi[ph_partner(i, n, Ns, reps)]);
         mh = x > mh ? x : mh, md = y > md ? y : md;
     }
-    mh = ph_block_max(mh, red, tid);
-    md = ph_block_max(md, red, tid);   // (its first barrier also closes the reads of Phi above)
+    mh = block_max_f64<PH_THREADS>(mh, red, tid);
+    md = block_max_f64<PH_THREADS>(md, red, tid);   // (its first barrier also closes the reads of Phi above)
     if (tid == 0) a.asym[b] = mh > 0.0 ? md / mh : 0.0, a.status[b] = VIB_OK;
     for (size_t i = tid; i < total; i += T) {   // a pair is written by the thread of its lower index
         const size_t p = ph_partner(i, n, Ns, reps);
@@ -141,8 +125,8 @@ __global__ __launch_bounds__(PH_THREADS) void phonon_dynmat_kernel(mi_phonon_dyn
         const double xa = fabs(A), xb = fabs(B);
         mh = xa > mh ? xa : mh, mh = xb > mh ? xb : mh, md = da > md ? da : md, md = db > md ? db : md;
     }
-    mh = ph_block_max(mh, red, tid);
-    md = ph_block_max(md, red, tid);   // (its first barrier also closes the reads above)
+    mh = block_max_f64<PH_THREADS>(mh, red, tid);
+    md = block_max_f64<PH_THREADS>(md, red, tid);   // (its first barrier also closes the reads above)
     if (tid == 0) a.herm[t] = mh > 0.0 ? md / mh : 0.0;
     for (int i = tid; i < m * m; i += T) {   // the pair (x, y), x <= y, writes its eight elements of the embedding; no other pair reads them
         const int x = i / m, y = i % m;
@@ -206,8 +190,6 @@ __global__ __launch_bounds__(64) void phonon_thermo_kernel(mi_phonon_thermo_args
         a.min_freq[b] = lo, a.min_q[b] = at;
     }
 }
-
-static bool pos_finite(double v) { return std::isfinite(v) && v > 0.0; }
 
 }  // namespace mi
 

@@ -247,7 +247,8 @@ int mi_relax_run(mi_net* net, mi_batch* b, const mi_relax_params* params_host, c
                  const float* time_freqs, const float* W, const float* bias, int P, int p, const float* d_out, float* out, float* g_frac,
                  float* g_lat, float* vel_x, float* vel_l, float* fstate, int* istate, int steps, int finish, void* stream) {
     const char* what = "mi_relax_run";
-    // mi_scalar_input_grad's refusals that need no call of it (the others are its own, at the first iteration, before it enqueues anything)
+    // mi_scalar_input_grad's refusals that need no call of it (the others are its own, at the first iteration, before it enqueues anything,
+    // under its own name: input_grad_refusals (net.h) would rename them, so this prefix of its list stays written out)
     MI_NO_LATENT(net, "mi_relax_run");
     MI_NO_POOLED(b, "mi_relax_run");
     MI_CHECK(net, MI_EINVAL, "%s: null network", what);

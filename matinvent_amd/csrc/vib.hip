@@ -14,12 +14,11 @@
 #include <mutex>
 
 #include "../../include/matinvent_hip_vib.h"
+#include "energy_chunk.h"
 #include "net.h"
 #include "vib_dynmat.h"
 
 namespace mi {
-
-extern int g_edge_pairs;   // cspnet.hip (mi_set_edge_pairs)
 
 static_assert(VIB_OK == MI_VIB_OK && VIB_NO_CONVERGENCE == MI_VIB_NO_CONVERGENCE && VIB_BAD_INPUT == MI_VIB_BAD_INPUT && EIG_OK == MI_VIB_OK &&
                   EIG_NO_CONVERGENCE == MI_VIB_NO_CONVERGENCE && EIG_BAD_INPUT == MI_VIB_BAD_INPUT,
@@ -29,7 +28,6 @@ static_assert(VIB_MAX_ATOMS == MI_VIB_MAX_ATOMS && VIB_MAX_TEMPS == MI_VIB_MAX_T
               "sizes");
 
 constexpr int VIB_THREADS = 256;
-constexpr int TYPE_COLS = 100;   // the type rows' width (matinvent_hip_scalar.h): 25 float4
 
 struct VibChunk {
     mi_vib_chunk_args a;
@@ -37,23 +35,16 @@ struct VibChunk {
     int Bc;
 };
 
-// the plan entry of copy k: its source crystal, copy index and atom count; false: the entry is not admissible (uniform over the workgroup)
+// the plan entry of copy k (energy_chunk.h): 6 n copies of a crystal of n <= VIB_MAX_ATOMS atoms
 __device__ __forceinline__ bool vib_plan(const VibChunk& A, int k, int* src, int* c, int* n, int* s0, int* c0) {
-    *src = A.a.plan_src[k], *c = A.a.plan_copy[k];
-    if (*src < 0 || *src >= A.a.Bs) return false;
-    *s0 = A.a.src_node_off[*src];
-    *n = A.a.src_node_off[*src + 1] - *s0;
-    *c0 = A.node_off[k];
-    return *n >= 1 && *n <= VIB_MAX_ATOMS && A.node_off[k + 1] - *c0 == *n && *c >= 0 && *c < 6 * *n;
+    return chunk_plan_entry(A.a.plan_src, A.a.plan_copy, A.a.Bs, A.a.src_node_off, A.node_off, k, 6, 0, VIB_MAX_ATOMS, src, c, n, s0, c0);
 }
 
 __global__ __launch_bounds__(VIB_THREADS) void vib_displace_kernel(VibChunk A) {
     const int k = blockIdx.x, tid = threadIdx.x;
     int src, c, n, s0, c0;
     if (!vib_plan(A, k, &src, &c, &n, &s0, &c0)) return;
-    const float4* ts = reinterpret_cast<const float4*>(A.a.src_types + (size_t)s0 * TYPE_COLS);
-    float4* td = reinterpret_cast<float4*>(A.a.types + (size_t)c0 * TYPE_COLS);
-    for (int i = tid; i < n * (TYPE_COLS / 4); i += VIB_THREADS) td[i] = ts[i];
+    chunk_copy_types(A.a.src_types, A.a.types, s0, c0, n, tid, VIB_THREADS);
     const float* lat = A.a.src_lat + (size_t)src * 9;
     if (tid < 9) A.a.lat[(size_t)k * 9 + tid] = lat[tid];
     double Li[9];
@@ -74,22 +65,6 @@ __global__ __launch_bounds__(64) void vib_collect_kernel(VibChunk A) {
     const float* g = A.a.g_frac + (size_t)c0 * 3;
     double* row = A.a.workspace + A.a.ws_off[src] + (size_t)c * 3 * n;
     for (int i = tid; i < n * 3; i += 64) row[i] = ok ? vib_cart_grad(g + 3 * (i / 3), Li, s, i % 3) : jac_nan();
-}
-
-// the block's maximum of v (finite, >= 0): exact, so no order to fix
-__device__ __forceinline__ double vib_block_max(double v, double* red, int tid) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double o = __shfl_xor(v, m, 64);
-        v = o > v ? o : v;
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    v = red[0];
-#pragma unroll
-    for (int w = 1; w < VIB_THREADS / 64; ++w) v = red[w] > v ? red[w] : v;
-    return v;
 }
 
 __global__ __launch_bounds__(VIB_THREADS) void vib_dynmat_kernel(mi_vib_dynmat_args a) {
@@ -130,8 +105,8 @@ __global__ __launch_bounds__(VIB_THREADS) void vib_dynmat_kernel(mi_vib_dynmat_a
         const double x = fabs(W[i]), y = fabs(W[i] - W[c * N3 + r]);
         mh = x > mh ? x : mh, md = y > md ? y : md;
     }
-    mh = vib_block_max(mh, red, tid);
-    md = vib_block_max(md, red, tid);   // (its first barrier also closes the reads of W above)
+    mh = block_max_f64<VIB_THREADS>(mh, red, tid);
+    md = block_max_f64<VIB_THREADS>(md, red, tid);   // (its first barrier also closes the reads of W above)
     if (tid == 0) a.asym[b] = mh > 0.0 ? md / mh : 0.0, a.status[b] = VIB_OK;
     for (size_t i = tid; i < NN; i += T) {   // the pair (r, c), r < c, is written by the thread of its upper element
         const size_t r = i / N3, c = i % N3;
@@ -268,21 +243,8 @@ __global__ __launch_bounds__(64) void vib_thermo_kernel(mi_vib_thermo_args a) {
     }
 }
 
-static bool pos_finite(double v) { return std::isfinite(v) && v > 0.0; }
-
 static int chunk_check(const char* what, const mi_batch* b, const mi_vib_chunk_args* q) {
-    MI_CHECK(b, MI_EINVAL, "%s: null handle", what);
-    MI_CHECK(q, MI_EINVAL, "%s: null argument block", what);
-    MI_NO_POOLED(b, "mi_vib");
-    MI_CHECK(pos_finite(q->h) && pos_finite(q->scale) && pos_finite(q->det_min), MI_EINVAL, "%s: h = %g, scale = %g, det_min = %g: each must be finite and positive",
-             what, q->h, q->scale, q->det_min);
-    MI_CHECK(q->Bs >= 0, MI_EINVAL, "%s: Bs = %d", what, q->Bs);
-    if (b->B == 0 || b->N == 0) return MI_OK;
-    MI_CHECK(q->src_types && q->src_frac && q->src_lat && q->src_node_off && q->plan_src && q->plan_copy && q->types && q->frac && q->lat && q->g_frac &&
-                 q->workspace && q->ws_off,
-             MI_EINVAL, "%s: null argument", what);
-    MI_CHECK((((uintptr_t)q->types | (uintptr_t)q->src_types) & 15) == 0, MI_EINVAL, "%s: the type rows must be 16-byte aligned", what);
-    return MI_OK;
+    return energy_chunk_check(what, "mi_vib", b, q, q && q->g_frac && q->ws_off);
 }
 
 static int displace_launch(mi_batch* b, const mi_vib_chunk_args* q, hipStream_t s) {
@@ -333,21 +295,13 @@ int mi_vib_collect(mi_batch* b, const mi_vib_chunk_args* args, void* stream) {
 int mi_vib_run_chunk(mi_net* net, mi_batch* b, const mi_vib_chunk_args* args, const float* time_freqs, const float* W, const float* bias, int P,
                      const float* d_out, float* out, float* g_lat, void* stream) {
     const char* what = "mi_vib_run_chunk";
-    // mi_scalar_input_grad's refusals, by name, here: the displace launch goes first, and nothing may be enqueued in front of a refusal
-    // (its hidden_dim cap alone stays its own: a refusal there leaves a written chunk state and nothing else behind)
+    // mi_scalar_input_grad's refusals, by name, here (input_grad_refusals): the displace launch goes first, and nothing may be enqueued in
+    // front of a refusal (its hidden_dim cap alone stays its own: a refusal there leaves a written chunk state and nothing else behind)
     MI_NO_LATENT(net, "mi_vib_run_chunk");
     MI_NO_POOLED(b, "mi_vib_run_chunk");
     MI_CHECK(net, MI_EINVAL, "%s: null network", what);
     MI_TRY(chunk_check(what, b, args));
-    MI_CHECK(!b->knn, MI_EINVAL, "%s: a knn-style handle (the input gradient runs in the fully connected pair mode only)", what);
-    MI_CHECK(g_edge_pairs && net->H % 4 == 0, MI_EINVAL, "%s: pair mode is off or hidden_dim %% 4 != 0 (the input gradient runs in pair mode only)", what);
-    MI_CHECK(b->tape.wslots == 0, MI_EINVAL, "%s: the handle has an open weight-gradient window (mi_batch_set_wgrad_window(.., 0) first)", what);
-    MI_CHECK(b->H == net->H && b->L == net->L, MI_EINVAL, "%s: batch was created for a different network", what);
-    MI_CHECK(!b->time_map, MI_EINVAL, "%s: the handle carries a time map (the predictor runs on the trained grid)", what);
-    MI_CHECK(!b->cond_on && !b->lik_on, MI_EINVAL, "%s: the handle carries a condition or a likelihood mask", what);
-    MI_CHECK(!b->gd_on, MI_EINVAL, "%s: the handle carries guidance (mi_batch_clear_guidance first)", what);
-    MI_CHECK(b->tape.wcur == 0, MI_EINVAL, "%s: the handle has pending deferred weight gradients (mi_cspnet_wgrad_flush first)", what);
-    MI_CHECK(net->W2T != nullptr, MI_ESTATE, "%s: mi_net_set_params must run before backward", what);
+    MI_TRY(input_grad_refusals(what, net, b));
     MI_CHECK(P >= 1, MI_EINVAL, "%s: P = %d", what, P);
     if (b->B == 0 || b->N == 0) return MI_OK;
     MI_CHECK(time_freqs && W && bias && d_out && out && g_lat, MI_EINVAL, "%s: null argument", what);

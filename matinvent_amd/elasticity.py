@@ -15,14 +15,14 @@ C is the derivative of the Cauchy stress at the GIVEN structure: under a residua
 is why stress0 and pressure come back too (relax the structure first when that matters).  delta, det_min and the FIRE constants of the
 ion relaxation ship UNTUNED, and no weight of this repository is trained: nothing about the quality of a modulus is claimed."""
 import ctypes as C
-import logging
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import energy_analysis as EA
+from .energy_analysis import _at, release_handles   # noqa: F401  (release_handles follows the read of a state)
 from .relax import FIRE_DEFAULTS
-from .vibrations import _at
 
 STATUS = ("ok", "bad_input", "singular")
 AVERAGES = ("voigt", "reuss", "hill")
@@ -31,7 +31,7 @@ _FIT = (("C", 36), ("S", 36), ("stress0", 6), ("pressure", 1), ("asym", 1), ("as
 _COUNTS = ("n_negative", "n_unrelaxed", "status")
 
 
-class Elasticity:
+class Elasticity(EA.EnergyAnalysis):
     """What an analysis needs: predictor, a PropertyPredictor (fc edge style, clean or noise-aware; the time is 0); task: the property read
     as the energy (eV); delta: the strain h (untuned); per_atom: the property is an energy per atom (the stress is that of n times it);
     ion_steps: FIRE steps of the ions in every strained copy at its fixed cell (0: the ions are clamped at their fractional coordinates);
@@ -39,15 +39,7 @@ class Elasticity:
     source crystals per state; det_min: the |det L| below which a crystal is bad input."""
 
     def __init__(self, predictor, task, delta=0.005, per_atom=True, ion_steps=0, relax=None, batch_size=256, det_min=1e-3):
-        if predictor.hparams.get("edge_style", "fc") != "fc":
-            raise ValueError("Elasticity: a knn-style predictor has no input gradient (the fully connected pair mode only)")
-        if task not in predictor.names:
-            raise ValueError(f"Elasticity: task = {task!r} is not a property of the predictor ({predictor.names})")
-        for k, val in (("delta", delta), ("det_min", det_min)):
-            if not (np.isfinite(float(val)) and float(val) > 0):
-                raise ValueError(f"Elasticity: {k} = {val}: must be finite and positive")
-        if int(batch_size) < 1:
-            raise ValueError(f"Elasticity: batch_size = {batch_size}: must be >= 1")
+        super().__init__(predictor, task, per_atom=per_atom, batch_size=batch_size, det_min=det_min, delta=delta)
         if int(ion_steps) < 0:
             raise ValueError(f"Elasticity: ion_steps = {ion_steps}: must be >= 0")
         relax = dict(relax or {})
@@ -61,25 +53,14 @@ class Elasticity:
                     raise ValueError(f"Elasticity: n_min = {val}: must be >= 0")
             elif not (np.isfinite(float(val)) and float(val) > 0):
                 raise ValueError(f"Elasticity: {k} = {val}: must be finite and positive")
-        self.predictor, self.task, self.p = predictor, str(task), predictor.names.index(task)
-        self.delta, self.per_atom, self.ion_steps = float(delta), bool(per_atom), int(ion_steps)
+        self.ion_steps = int(ion_steps)
         self.fire = {k: (int(v) if k == "n_min" else float(v)) for k, v in fire.items()}
-        self.batch_size, self.det_min = int(batch_size), float(det_min)
-
-    def scale(self):
-        std = float(self.predictor.normalizer.std[self.p])
-        if not (np.isfinite(std) and std > 0):
-            raise ValueError(f"Elasticity: the normaliser's std of {self.task!r} is {std}: the predictor has no fitted normaliser")
-        return std
 
     def relax_params(self):
         """The C parameter block of the ion relaxation (relax_cell, scale, det_min and per_atom are the chunk's own: mi_elastic_run_chunk)."""
         f = self.fire
         return _lib.RelaxParams(f["dt"], f["dt_max"], f["maxstep"], f["f_inc"], f["f_dec"], f["a_start"], f["f_a"], f["fmax"], self.scale(), 0.0,
                                 self.det_min, f["n_min"], 0, int(self.per_atom))
-
-    def __deepcopy__(self, memo):
-        return self   # (a config that carries an analysis is merged by copy: the predictor's device handles are shared)
 
 
 def chunk_plan(num_crystals, batch_size):
@@ -111,12 +92,10 @@ def source_arrays(e, state, num_atoms):
 
 
 def chunk_buffers(e, Bc, Nc):
-    dev, P = e.predictor.device, e.predictor.P
+    """EA.gradient_buffers and the state of the ion relaxation."""
+    dev = e.predictor.device
     f = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-    d_out = torch.zeros(Bc, P, device=dev, dtype=torch.float32)
-    d_out[:, e.p] = 1.0
-    return dict(types=f(Nc, _lib.NUM_TYPES), frac=f(Nc, 3), lat=f(Bc, 3, 3), g_frac=f(Nc, 3), g_lat=f(Bc, 3, 3), out=f(Bc, P), d_out=d_out,
-                vel_x=f(Nc, 3), fstate=f(Bc, _lib.RELAX_NF), istate=torch.empty(Bc, _lib.RELAX_NI, device=dev, dtype=torch.int32))
+    return dict(EA.gradient_buffers(e, Bc, Nc), vel_x=f(Nc, 3), fstate=f(Bc, _lib.RELAX_NF), istate=torch.empty(Bc, _lib.RELAX_NI, device=dev, dtype=torch.int32))
 
 
 def chunk_args(e, src, plan_src, plan_copy, bufs, relaxed=None):
@@ -139,32 +118,10 @@ def run_chunk(e, handle, args, bufs):
 
 
 def enqueue_stresses(e, src):
-    """Every chunk's mi_elastic_run_chunk on the current stream: the workspace rows of every crystal of `src`.  A chunk whose atom-count
-    list equals the previous chunk's reuses its handle (and its buffers: the stream orders the reuse).  Returns the number of chunks."""
-    m = e.predictor
-    m.trunk.sync()
-    prev, cb, bufs, chunks = None, None, None, chunk_plan(src["B"], e.batch_size)
-    for ps, pc in chunks:
-        na = [src["na"][b] for b in ps]
-        if na != prev:
-            if cb is not None:   # the old handle goes once the stream has passed its work: a wait, not a read
-                torch.cuda.current_stream().synchronize()
-                src["handles"].remove(cb)
-                cb.release()
-            cb = m.make_batch(na)
-            src["handles"].append(cb)   # (the last one is released by release_handles, behind the stream's work)
-            bufs = chunk_buffers(e, len(na), sum(na))
-            prev = na
-        dev_s, dev_c = torch.from_numpy(ps.copy()).to(m.device), torch.from_numpy(pc.copy()).to(m.device)
-        src["keep"] += [dev_s, dev_c, bufs]   # (alive until the read)
-        run_chunk(e, cb, chunk_args(e, src, dev_s, dev_c, bufs), bufs)
-    return len(chunks)
-
-
-def release_handles(src):
-    for cb in src["handles"]:
-        cb.release()
-    src["handles"], src["keep"] = [], []
+    """Every chunk's mi_elastic_run_chunk on the current stream (EA.enqueue_chunks): the workspace rows of every crystal of `src`.
+    Returns the number of chunks."""
+    return EA.enqueue_chunks(e, src, chunk_plan(src["B"], e.batch_size), chunk_buffers,
+                             lambda cb, dev_s, dev_c, bufs: run_chunk(e, cb, chunk_args(e, src, dev_s, dev_c, bufs), bufs))
 
 
 def fit_args(e, src):
@@ -184,13 +141,9 @@ def analyze_state(e, state, num_atoms):
     src = source_arrays(e, state, num_atoms)
     if src["B"] == 0:
         return src
-    try:
+    with EA.releasing_on_error(src):
         enqueue_stresses(e, src)
         enqueue_fit(e, src)
-    except Exception:   # (a refused handle among them) the handles made so far go, behind the work that was enqueued on them
-        torch.cuda.current_stream().synchronize()
-        release_handles(src)
-        raise
     return src
 
 
@@ -216,7 +169,6 @@ def analyze_records(e, records):
     Voigt / Reuss / Hill.  A record the network cannot take and one whose handle is refused come back NaN with status -1; when a state's
     handle is refused its crystals are analysed one by one."""
     from .predictor import _valid_fields
-    from .structure import lattice_matrix
     dev = e.predictor.device
     records = list(records)
     n = len(records)
@@ -225,17 +177,12 @@ def analyze_records(e, records):
     ok = [i for i, f in enumerate(fields) if f is not None]
     widths = [w for _, w in _FIT]
 
-    def enqueue(rows):
-        na = [int(fields[i][0].size) for i in rows]
-        z = np.concatenate([fields[i][0] for i in rows])
-        types = np.zeros((z.size, _lib.NUM_TYPES), np.float32)
-        types[np.arange(z.size), z - 1] = 1.0
-        frac = np.concatenate([fields[i][1] for i in rows]) % 1.0
-        lat = np.stack([lattice_matrix(fields[i][2], fields[i][3]) for i in rows])
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
-        return rows, analyze_state(e, (up(frac), up(lat), up(types)), na)   # (MIError: a handle was refused; nothing is left behind)
+    def enqueue(_, rows):
+        na, state = EA.pack_records(fields, rows, dev)
+        return rows, analyze_state(e, state, na)   # (MIError: a handle was refused; nothing is left behind)
 
-    def read(rows, src):
+    def read(st):
+        rows, src = st
         B = src["B"]
         flat = torch.cat([src[k].reshape(B, -1) for k, _ in _FIT] + [src[k].to(torch.float64)[:, None] for k in _COUNTS], dim=1).cpu().numpy()
         release_handles(src)
@@ -246,36 +193,6 @@ def analyze_records(e, records):
         for j, k in enumerate(_COUNTS):
             res[k][rows] = flat[:, at + j].astype(np.int64)
 
-    pend, ran = [], False
-
-    def submit(rows):
-        nonlocal ran
-        pend.append(enqueue(rows))
-        ran = True
-        while len(pend) > 1:   # a state is read behind the next one's enqueue: the device stays busy, two workspaces are alive at most
-            read(*pend.pop(0))
-
-    try:
-        for s in range(0, len(ok), e.batch_size):   # source states of at most batch_size crystals
-            rows = ok[s:s + e.batch_size]
-            try:
-                submit(rows)
-            except _lib.MIError:
-                for i in rows:   # a handle of the state was refused: each crystal on its own, the refused one stays NaN with status -1
-                    try:
-                        submit([i])
-                    except _lib.MIError:
-                        pass
-        while pend:
-            read(*pend.pop(0))
-    finally:
-        for _, src in pend:   # (an error other than a refusal: nothing stays allocated)
-            torch.cuda.current_stream().synchronize()
-            release_handles(src)
-    if ran:   # operand conversions that left the fp16 plane format's range are counted process-wide: account for this call's own here
-        cnt = _lib.saturation_events(reset=True)
-        if cnt and (res["status"] == _lib.ELASTIC_BAD_INPUT).any():
-            logging.warning(f"analyze_records: {cnt} operand conversions saturated in chunks that hold bad-input crystals (their results are NaN)")
-        elif cnt:
-            _lib.check_saturation_count(cnt, "analyze_records")
+    ran = EA.run_pipelined([(None, ok)], e.batch_size, enqueue, read, EA.release_pending)   # source states of at most batch_size crystals
+    EA.settle_saturation(ran, (res["status"] == _lib.ELASTIC_BAD_INPUT).any(), "analyze_records")
     return add_shortcuts(res)

@@ -17,15 +17,16 @@ Departures and limits, stated: the supercell is DIAGONAL (the reference's transf
 q <-> -q only; the shortest-image search covers the 27 neighbouring supercells; mesh, tie_tol, delta and nu_cut ship UNTUNED, and no weight
 of this repository is trained: nothing about the quality of a frequency or a heat capacity is claimed."""
 import ctypes as C
-import logging
 from collections import namedtuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import energy_analysis as EA
 from . import vibrations as VB
-from .vibrations import KB_J_MOL, STATUS, _at, release_handles   # noqa: F401  (release_handles follows the read, as in vibrations.py)
+from .energy_analysis import _at, release_handles   # noqa: F401  (release_handles follows the read of a state)
+from .vibrations import KB_J_MOL, STATUS   # noqa: F401
 
 # the (crystal, q) matrices of one mi_phonon_dynmat / mi_sym_eigvals launch pair stay under this many bytes (the eigen-solver's work copies
 # included); an analysis of more items runs in several launch pairs on one buffer.  256 MiB: 1820 matrices of order 120 in the LDS path.
@@ -105,7 +106,7 @@ def auto_reps(lattice, min_length):
     return tuple(out)
 
 
-class Phonons:
+class Phonons(VB.HarmonicAnalysis):
     """What an analysis needs: predictor, task, delta, per_atom, temperatures, nu_cut, batch_size, det_min as vibrations.Vibrations';
     supercell: (a, b, c) or "auto" (auto_reps with min_length, per record); mesh: the Gamma-centred q-mesh of analyze_records; tie_tol: the
     distance (Angstrom) within which two images of a pair count as equally near (1e-5: phonopy's symprec from memory, unverified);
@@ -113,7 +114,7 @@ class Phonons:
 
     def __init__(self, predictor, task, supercell=(2, 2, 2), min_length=10.0, mesh=(4, 4, 4), delta=0.01, per_atom=True, temperatures=(300.0,), nu_cut=0.05,
                  batch_size=256, tie_tol=1e-5, det_min=1e-3, workspace_cap=WORKSPACE_CAP):
-        base = VB.Vibrations(predictor, task, delta=delta, per_atom=per_atom, temperatures=temperatures, nu_cut=nu_cut, batch_size=batch_size, det_min=det_min)
+        super().__init__(predictor, task, delta, per_atom, temperatures, nu_cut, batch_size, det_min)
         if isinstance(supercell, str):
             if supercell != "auto":
                 raise ValueError(f"Phonons: supercell = {supercell!r}: three integers >= 1 or \"auto\"")
@@ -129,14 +130,7 @@ class Phonons:
         if int(workspace_cap) < 1:
             raise ValueError(f"Phonons: workspace_cap = {workspace_cap}: must be >= 1")
         self.mesh = mesh_points(mesh).mesh
-        self.predictor, self.task, self.p = predictor, base.task, base.p
-        self.delta, self.per_atom, self.temperatures, self.nu_cut = base.delta, base.per_atom, base.temperatures, base.nu_cut
-        self.batch_size, self.det_min = base.batch_size, base.det_min
         self.supercell, self.min_length, self.tie_tol, self.workspace_cap = sc, float(min_length), float(tie_tol), int(workspace_cap)
-        self.scale = base.scale
-
-    def __deepcopy__(self, memo):
-        return self   # (a config that carries an analysis is merged by copy: the predictor's device handles are shared)
 
     def reps_for(self, lattice):
         return self.supercell if self.supercell != "auto" else auto_reps(lattice, self.min_length)
@@ -223,31 +217,8 @@ def source_arrays(p, state, num_atoms, masses, reps, table, weights, no_lds=0):
 
 def enqueue_gradients(p, src):
     """Every chunk's mi_vib_run_chunk on the current stream, the supercells as source and the home atoms' copies alone in the plan: the
-    workspace's 6 n rows Gc of every crystal of `src`.  A chunk whose atom-count list equals the previous chunk's reuses its handle.
-    Returns the number of chunks."""
-    from .cspnet import _stream
-    lib = _lib.load()
-    m = p.predictor
-    m.trunk.sync()
-    _, W, bias = m.head_slices()
-    prev, cb, bufs, chunks = None, None, None, chunk_plan(src["prim"], p.batch_size)
-    for ps, pc in chunks:
-        na = [src["na"][b] for b in ps]
-        if na != prev:
-            if cb is not None:   # the old handle goes once the stream has passed its work: a wait, not a read
-                torch.cuda.current_stream().synchronize()
-                src["handles"].remove(cb)
-                cb.release()
-            cb = m.make_batch(na)
-            src["handles"].append(cb)
-            bufs = VB.chunk_buffers(p, len(na), sum(na))
-            prev = na
-        dev_s, dev_c = torch.from_numpy(ps.copy()).to(m.device), torch.from_numpy(pc.copy()).to(m.device)
-        src["keep"] += [dev_s, dev_c, bufs]
-        args = VB.chunk_args(p, src, dev_s, dev_c, bufs)
-        _lib.check(lib.mi_vib_run_chunk(m.trunk._h, cb._h, C.byref(args), _at(m.time_freqs), _at(W), _at(bias), m.P, _at(bufs["d_out"]), _at(bufs["out"]),
-                                        _at(bufs["g_lat"]), _stream()), "mi_vib_run_chunk")
-    return len(chunks)
+    workspace's 6 n rows Gc of every crystal of `src` (vibrations.enqueue_gradients on this module's plan).  Returns the number of chunks."""
+    return VB.enqueue_gradients(p, src, chunk_plan(src["prim"], p.batch_size))
 
 
 def enqueue_fc(p, src):
@@ -308,22 +279,17 @@ def analyze_state(p, state, num_atoms, masses, reps, qpoints=None, weights=None,
     src = source_arrays(p, state, num_atoms, masses, reps, phase_table(qp, reps), weights, no_lds)
     if src["B"] == 0 or src["Q"] == 0:
         return src
-    try:
+    with EA.releasing_on_error(src):
         enqueue_gradients(p, src)
         enqueue_spectrum(p, src, no_lds)
-    except Exception:   # (a refused handle among them) the handles made so far go, behind the work that was enqueued on them
-        torch.cuda.current_stream().synchronize()
-        release_handles(src)
-        raise
     return src
 
 
 def _analyze(p, records, qpoints, weights):
     from .data import SimpleStructure
     from .predictor import _valid_fields
-    from .structure import MASSES, lattice_matrix, make_supercell
-    m = p.predictor
-    dev = m.device
+    from .structure import lattice_matrix, make_supercell
+    dev = p.predictor.device
     records = list(records)
     n, K, Q = len(records), len(p.temperatures), len(weights)
     res = dict(frequencies=[np.zeros((Q, 0)) for _ in range(n)], n_imag=np.full(n, -1, np.int64), n_zero=np.full(n, -1, np.int64), c_v=np.full((n, K), np.nan),
@@ -352,18 +318,12 @@ def _analyze(p, records, qpoints, weights):
         if fields[i] is not None:
             groups.setdefault(reps, []).append(i)
 
-    def enqueue(rows, reps):
-        na = [int(fields[i][0].size) for i in rows]
-        z = np.concatenate([fields[i][0] for i in rows])
-        types = np.zeros((z.size, _lib.NUM_TYPES), np.float32)
-        types[np.arange(z.size), z - 1] = 1.0
-        frac = np.concatenate([fields[i][1] for i in rows]) % 1.0
-        lat = np.stack([lattice_matrix(fields[i][2], fields[i][3]) for i in rows])
-        mass = np.asarray(MASSES, dtype=np.float64)[z]
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
-        return rows, na, mass, analyze_state(p, (up(frac), up(lat), up(types)), na, mass, reps, qpoints, weights)
+    def enqueue(reps, rows):
+        na, state, mass = EA.pack_records(fields, rows, dev, masses=True)
+        return rows, na, mass, analyze_state(p, state, na, mass, reps, qpoints, weights)
 
-    def read(rows, na, mass, src):
+    def read(st):
+        rows, na, mass, src = st
         cols = ("zpe", "min_freq", "asym", "herm", "pair_gap")
         ints = ("n_imag", "n_zero", "min_q", "sweeps_max", "status")
         small = torch.cat([src["c_v"]] + [src[k][:, None] for k in cols] + [src[k].to(torch.float64)[:, None] for k in ints], dim=1).cpu().numpy()
@@ -381,39 +341,8 @@ def _analyze(p, records, qpoints, weights):
                 res[c][i] = int(small[k, K + len(cols) + j])
             res["frequencies"][i] = freqs[eo[k * Q]:eo[(k + 1) * Q]].reshape(Q, 3 * prim).copy()
 
-    pend, ran = [], False
-
-    def submit(rows, reps):
-        nonlocal ran
-        pend.append(enqueue(rows, reps))
-        ran = True
-        while len(pend) > 1:   # a state is read behind the next one's enqueue
-            read(*pend.pop(0))
-
-    try:
-        for reps, ok in groups.items():
-            for s in range(0, len(ok), p.batch_size):   # source states of at most batch_size crystals of one reps
-                rows = ok[s:s + p.batch_size]
-                try:
-                    submit(rows, reps)
-                except _lib.MIError:
-                    for i in rows:   # a handle of the state was refused: each crystal on its own, the refused one stays NaN with status -1
-                        try:
-                            submit([i], reps)
-                        except _lib.MIError:
-                            pass
-        while pend:
-            read(*pend.pop(0))
-    finally:
-        for _, _, _, src in pend:   # (an error other than a refusal: nothing stays allocated)
-            torch.cuda.current_stream().synchronize()
-            release_handles(src)
-    if ran:   # operand conversions that left the fp16 plane format's range are counted process-wide: account for this call's own here
-        cnt = _lib.saturation_events(reset=True)
-        if cnt and (res["status"] == _lib.VIB_BAD_INPUT).any():
-            logging.warning(f"phonons: {cnt} operand conversions saturated in chunks that hold bad-input crystals (their results are NaN)")
-        elif cnt:
-            _lib.check_saturation_count(cnt, "phonons")
+    ran = EA.run_pipelined(groups.items(), p.batch_size, enqueue, read, EA.release_pending)   # source states of at most batch_size crystals of one reps
+    EA.settle_saturation(ran, (res["status"] == _lib.VIB_BAD_INPUT).any(), "phonons")
     return res
 
 

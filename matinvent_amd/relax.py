@@ -10,19 +10,19 @@ raw unit per Angstrom.  A clean or a noise-aware predictor is taken; the time is
 of this repository is trained: nothing about the quality of a relaxed structure is claimed.  A crystal that has converged or failed is
 frozen bit for bit but still rides through every gradient evaluation of its batch (no compaction)."""
 import ctypes as C
-import logging
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import energy_analysis as EA
 
 STATUS = ("active", "converged", "failed", "exhausted")
 FIRE_DEFAULTS = dict(dt=0.1, dt_max=1.0, maxstep=0.2, n_min=5, f_inc=1.1, f_dec=0.5, a_start=0.1, f_a=0.99)   # ASE's FIRE
-_POSITIVE = ("fmax", "dt", "dt_max", "maxstep", "f_inc", "f_dec", "a_start", "f_a", "det_min")
+_POSITIVE = ("fmax", "dt", "dt_max", "maxstep", "f_inc", "f_dec", "a_start", "f_a")
 
 
-class Relaxer:
+class Relaxer(EA.EnergyAnalysis):
     """What a relaxation needs: predictor, a PropertyPredictor (fc edge style, clean or noise-aware); task: the property read as the
     energy; steps: FIRE steps per crystal at most; fmax: the convergence threshold on the largest force row (raw unit per Angstrom);
     relax_cell: the lattice moves too (three more rows of force, -s g_lat / c); per_atom: the property is an energy per atom (the forces
@@ -33,14 +33,11 @@ class Relaxer:
 
     def __init__(self, predictor, task, steps=50, fmax=0.1, relax_cell=True, per_atom=True, cell_factor=None, check_every=0, batch_size=64,
                  det_min=1e-3, **fire):
-        if predictor.hparams.get("edge_style", "fc") != "fc":
-            raise ValueError("Relaxer: a knn-style predictor has no input gradient (the fully connected pair mode only)")
-        if task not in predictor.names:
-            raise ValueError(f"Relaxer: task = {task!r} is not a property of the predictor ({predictor.names})")
+        super().__init__(predictor, task, per_atom=per_atom, batch_size=batch_size, det_min=det_min)
         unknown = set(fire) - set(FIRE_DEFAULTS)
         if unknown:
             raise ValueError(f"Relaxer: unknown keywords {sorted(unknown)}")
-        v = dict(FIRE_DEFAULTS, **fire, fmax=fmax, det_min=det_min)
+        v = dict(FIRE_DEFAULTS, **fire, fmax=fmax, det_min=self.det_min)
         for k in _POSITIVE:
             if not (np.isfinite(float(v[k])) and float(v[k]) > 0):
                 raise ValueError(f"Relaxer: {k} = {v[k]}: must be finite and positive")
@@ -50,31 +47,21 @@ class Relaxer:
             raise ValueError(f"Relaxer: steps = {steps}: must be >= 0")
         if int(check_every) < 0:
             raise ValueError(f"Relaxer: check_every = {check_every}: 0 (never wait for the host) or a positive number of steps")
-        if int(batch_size) < 1:
-            raise ValueError(f"Relaxer: batch_size = {batch_size}: must be >= 1")
         if cell_factor is not None and not (np.isfinite(float(cell_factor)) and float(cell_factor) > 0):
             raise ValueError(f"Relaxer: cell_factor = {cell_factor}: None (the crystal's atom count) or a positive number")
-        self.predictor, self.task, self.p = predictor, str(task), predictor.names.index(task)
-        self.steps, self.check_every, self.batch_size = int(steps), int(check_every), int(batch_size)
-        self.relax_cell, self.per_atom = bool(relax_cell), bool(per_atom)
+        self.steps, self.check_every, self.relax_cell = int(steps), int(check_every), bool(relax_cell)
         self.cell_factor = None if cell_factor is None else float(cell_factor)
         self.fire = {k: (int(v[k]) if k == "n_min" else float(v[k])) for k in list(FIRE_DEFAULTS) + ["fmax", "det_min"]}
         self.last_info = None
 
     def params(self):
         """The C parameter block: the constants, and scale = the normaliser's std of the task."""
-        std = float(self.predictor.normalizer.std[self.p])
-        if not (np.isfinite(std) and std > 0):
-            raise ValueError(f"Relaxer: the normaliser's std of {self.task!r} is {std}: the predictor has no fitted normaliser")
         f = self.fire
-        return _lib.RelaxParams(f["dt"], f["dt_max"], f["maxstep"], f["f_inc"], f["f_dec"], f["a_start"], f["f_a"], f["fmax"], std,
+        return _lib.RelaxParams(f["dt"], f["dt_max"], f["maxstep"], f["f_inc"], f["f_dec"], f["a_start"], f["f_a"], f["fmax"], self.scale(),
                                 0.0 if self.cell_factor is None else self.cell_factor, f["det_min"], f["n_min"], int(self.relax_cell), int(self.per_atom))
 
     def __call__(self, strucs, xyz_path=None):
         return relax_records(self, strucs)
-
-    def __deepcopy__(self, memo):
-        return self   # (a config that carries a relaxer is merged by copy: the relaxer, with its predictor's device handles, is shared)
 
     @classmethod
     def from_config(cls, spec, device=None):
@@ -178,7 +165,6 @@ def relax_records(relaxer, records):
     relaxer.last_info: per record status (-1: never ran), steps, first energy."""
     from .data import SimpleStructure
     from .predictor import _valid_fields
-    from .structure import lattice_matrix
     m = relaxer.predictor
     dev = m.device
     records = list(records)
@@ -188,35 +174,18 @@ def relax_records(relaxer, records):
     fields = [_valid_fields(r) for r in records]
     ok = [i for i, f in enumerate(fields) if f is not None]
 
-    def enqueue(rows):
-        na = [int(fields[i][0].size) for i in rows]
-        cb = m.make_batch(na)   # (MIError: an atom count the handle refuses)
-        z = np.concatenate([fields[i][0] for i in rows])
-        types = np.zeros((z.size, _lib.NUM_TYPES), np.float32)
-        types[np.arange(z.size), z - 1] = 1.0
-        frac = np.concatenate([fields[i][1] for i in rows]) % 1.0
-        lat = np.stack([lattice_matrix(fields[i][2], fields[i][3]) for i in rows])
-        up = lambda v: torch.from_numpy(np.ascontiguousarray(v, np.float32)).to(dev)
-        st = (up(frac), up(lat), up(types))
+    def enqueue(_, rows):
+        cb = m.make_batch([int(fields[i][0].size) for i in rows])   # (MIError: an atom count the handle refuses)
         try:
+            na, st = EA.pack_records(fields, rows, dev)
             bufs = relax_enqueue(relaxer, st, cb)
         except Exception:
             cb.release()
             raise
         return rows, na, cb, st, bufs
 
-    pend = []
-    for s in range(0, len(ok), relaxer.batch_size):
-        rows = ok[s:s + relaxer.batch_size]
-        try:
-            pend.append(enqueue(rows))
-        except _lib.MIError:
-            for i in rows:   # one crystal of the batch is refused: each on its own, the refused one stays as it was
-                try:
-                    pend.append(enqueue([i]))
-                except _lib.MIError:
-                    pass
-    for rows, na, cb, st, bufs in pend:   # the reads, behind every batch's work
+    def read(state):
+        rows, na, cb, st, bufs = state
         info = read_info(relaxer, bufs, na)
         x, l = st[0].cpu().double().numpy(), st[1].cpu().double().numpy()
         cb.release()
@@ -228,12 +197,14 @@ def relax_records(relaxer, records):
             le, an = _lengths_angles(l[k])
             out[i] = SimpleStructure(le, an, [int(v) for v in fields[i][0]], x[off[k]:off[k + 1]].copy())
             energies[i] = info["e_last"][k]
-    if pend:   # operand conversions that left the fp16 plane format's range are counted process-wide: account for this call's own here
-        n = _lib.saturation_events(reset=True)
-        if n and (last["status"] == _lib.RELAX_FAILED).any():
-            logging.warning(f"relax_records: {n} operand conversions saturated in batches that hold failed crystals (their energies are NaN)")
-        elif n:
-            _lib.check_saturation_count(n, "relax_records")
+
+    def release(state):
+        torch.cuda.current_stream().synchronize()
+        state[2].release()
+
+    # every batch holds its own handle and nothing is read before the last enqueue (max_pending = None): the reads, behind every batch's work
+    ran = EA.run_pipelined([(None, ok)], relaxer.batch_size, enqueue, read, release, max_pending=None)
+    EA.settle_saturation(ran, (last["status"] == _lib.RELAX_FAILED).any(), "relax_records", "batches that hold failed crystals (their energies are NaN)")
     relaxer.last_info = last
     return out, energies
 

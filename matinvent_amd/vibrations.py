@@ -16,26 +16,34 @@ displaced set is NOT reduced by the supercell's translation symmetry (every atom
 delta, nu_cut and det_min ship UNTUNED, and no weight of this repository is trained: nothing about the quality of a frequency or a heat
 capacity is claimed."""
 import ctypes as C
-import logging
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import energy_analysis as EA
+from .energy_analysis import _at, release_handles   # noqa: F401  (release_handles follows the read of a state)
 
 STATUS = ("ok", "no_convergence", "bad_input")
 KB_J_MOL = 8.31446261815324   # k_B N_A in J / (K mol), CODATA 2018 (both exact)
 
 
-def _at(t):
-    """The device address of a contiguous tensor of any element type (the float64 and int64 arrays of this module included)."""
-    if t is None:
-        return None
-    assert t.is_cuda and t.is_contiguous(), (t.device, t.is_contiguous())
-    return C.c_void_p(t.data_ptr())
+class HarmonicAnalysis(EA.EnergyAnalysis):
+    """An analysis that ends in a thermo launch (Vibrations here, phonons.Phonons): the checked temperatures (a tuple) and nu_cut on top of
+    the shared configuration."""
+
+    def __init__(self, predictor, task, delta, per_atom, temperatures, nu_cut, batch_size, det_min):
+        super().__init__(predictor, task, per_atom=per_atom, batch_size=batch_size, det_min=det_min, delta=delta)
+        who = type(self).__name__
+        temps = tuple(float(t) for t in np.atleast_1d(np.asarray(temperatures, dtype=np.float64)))
+        if not 1 <= len(temps) <= _lib.VIB_MAX_TEMPS or not all(np.isfinite(t) and t > 0 for t in temps):
+            raise ValueError(f"{who}: temperatures = {temperatures}: 1 to {_lib.VIB_MAX_TEMPS} finite positive numbers")
+        if not (np.isfinite(float(nu_cut)) and float(nu_cut) >= 0):
+            raise ValueError(f"{who}: nu_cut = {nu_cut}: must be finite and >= 0")
+        self.temperatures, self.nu_cut = temps, float(nu_cut)
 
 
-class Vibrations:
+class Vibrations(HarmonicAnalysis):
     """What an analysis needs: predictor, a PropertyPredictor (fc edge style, clean or noise-aware; the time is 0); task: the property read
     as the energy (eV); delta: the displacement h in Angstrom; per_atom: the property is an energy per atom (the Hessian is that of n times
     it); temperatures: up to 8, in K; nu_cut: the |frequency| (THz) at or below which a mode counts as zero; batch_size: displaced copies per
@@ -43,35 +51,11 @@ class Vibrations:
     bad input."""
 
     def __init__(self, predictor, task, delta=0.01, per_atom=True, temperatures=(300.0,), nu_cut=0.05, batch_size=256, supercell=(1, 1, 1), det_min=1e-3):
-        if predictor.hparams.get("edge_style", "fc") != "fc":
-            raise ValueError("Vibrations: a knn-style predictor has no input gradient (the fully connected pair mode only)")
-        if task not in predictor.names:
-            raise ValueError(f"Vibrations: task = {task!r} is not a property of the predictor ({predictor.names})")
-        temps = tuple(float(t) for t in np.atleast_1d(np.asarray(temperatures, dtype=np.float64)))
-        if not 1 <= len(temps) <= _lib.VIB_MAX_TEMPS or not all(np.isfinite(t) and t > 0 for t in temps):
-            raise ValueError(f"Vibrations: temperatures = {temperatures}: 1 to {_lib.VIB_MAX_TEMPS} finite positive numbers")
-        for k, val in (("delta", delta), ("det_min", det_min)):
-            if not (np.isfinite(float(val)) and float(val) > 0):
-                raise ValueError(f"Vibrations: {k} = {val}: must be finite and positive")
-        if not (np.isfinite(float(nu_cut)) and float(nu_cut) >= 0):
-            raise ValueError(f"Vibrations: nu_cut = {nu_cut}: must be finite and >= 0")
-        if int(batch_size) < 1:
-            raise ValueError(f"Vibrations: batch_size = {batch_size}: must be >= 1")
+        super().__init__(predictor, task, delta, per_atom, temperatures, nu_cut, batch_size, det_min)
         sc = tuple(int(r) for r in supercell)
         if len(sc) != 3 or min(sc) < 1:
             raise ValueError(f"Vibrations: supercell = {supercell}: three integers >= 1")
-        self.predictor, self.task, self.p = predictor, str(task), predictor.names.index(task)
-        self.delta, self.per_atom, self.temperatures, self.nu_cut = float(delta), bool(per_atom), temps, float(nu_cut)
-        self.batch_size, self.supercell, self.det_min = int(batch_size), sc, float(det_min)
-
-    def scale(self):
-        std = float(self.predictor.normalizer.std[self.p])
-        if not (np.isfinite(std) and std > 0):
-            raise ValueError(f"Vibrations: the normaliser's std of {self.task!r} is {std}: the predictor has no fitted normaliser")
-        return std
-
-    def __deepcopy__(self, memo):
-        return self   # (a config that carries an analysis is merged by copy: the predictor's device handles are shared)
+        self.supercell = sc
 
 
 def chunk_plan(num_atoms, batch_size):
@@ -125,46 +109,23 @@ def chunk_args(v, src, plan_src, plan_copy, bufs):
                              v.delta, v.scale(), v.det_min, int(v.per_atom))
 
 
-def chunk_buffers(v, Bc, Nc):
-    dev, P = v.predictor.device, v.predictor.P
-    e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
-    d_out = torch.zeros(Bc, P, device=dev, dtype=torch.float32)
-    d_out[:, v.p] = 1.0
-    return dict(types=e(Nc, _lib.NUM_TYPES), frac=e(Nc, 3), lat=e(Bc, 3, 3), g_frac=e(Nc, 3), g_lat=e(Bc, 3, 3), out=e(Bc, P), d_out=d_out)
+chunk_buffers = EA.gradient_buffers
 
 
-def enqueue_gradients(v, src):
-    """Every chunk's mi_vib_run_chunk on the current stream: the workspace's Gc rows of every crystal of `src`.  A chunk whose atom-count
-    list equals the previous chunk's reuses its handle (and its buffers: the stream orders the reuse).  Returns the number of chunks."""
+def enqueue_gradients(v, src, chunks=None):
+    """Every chunk's mi_vib_run_chunk on the current stream (EA.enqueue_chunks): the workspace's Gc rows of every crystal of `src`.
+    chunks: the plan (default: chunk_plan of every atom; phonons.py passes the home atoms' copies alone).  Returns the number of chunks."""
     from .cspnet import _stream
-    lib = _lib.load()
-    m = v.predictor
-    m.trunk.sync()
-    _, W, bias = m.head_slices()
-    prev, cb, bufs, chunks = None, None, None, chunk_plan(src["na"], v.batch_size)
-    for ps, pc in chunks:
-        na = [src["na"][b] for b in ps]
-        if na != prev:
-            if cb is not None:   # the old handle goes once the stream has passed its work: a wait, not a read (its memory is not held to the end)
-                torch.cuda.current_stream().synchronize()
-                src["handles"].remove(cb)
-                cb.release()
-            cb = m.make_batch(na)
-            src["handles"].append(cb)   # (the last one is released by release_handles, behind the stream's work)
-            bufs = chunk_buffers(v, len(na), sum(na))
-            prev = na
-        dev_s, dev_c = torch.from_numpy(ps.copy()).to(m.device), torch.from_numpy(pc.copy()).to(m.device)
-        src["keep"] += [dev_s, dev_c, bufs]   # (alive until the read)
+    lib, m = _lib.load(), v.predictor
+
+    def run(cb, dev_s, dev_c, bufs):
+        _, W, bias = m.head_slices()
         args = chunk_args(v, src, dev_s, dev_c, bufs)
         _lib.check(lib.mi_vib_run_chunk(m.trunk._h, cb._h, C.byref(args), _at(m.time_freqs), _at(W), _at(bias), m.P, _at(bufs["d_out"]), _at(bufs["out"]),
                                         _at(bufs["g_lat"]), _stream()), "mi_vib_run_chunk")
-    return len(chunks)
 
-
-def release_handles(src):
-    for cb in src["handles"]:
-        cb.release()
-    src["handles"], src["keep"] = [], []
+    chunks = chunk_plan(src["na"], v.batch_size) if chunks is None else chunks
+    return EA.enqueue_chunks(v, src, chunks, chunk_buffers, run)
 
 
 def enqueue_dynmat(v, src):
@@ -195,15 +156,11 @@ def analyze_state(v, state, num_atoms, masses, no_lds=0):
     src = source_arrays(v, state, num_atoms, masses)
     if src["B"] == 0:
         return src
-    try:
+    with EA.releasing_on_error(src):
         enqueue_gradients(v, src)
         enqueue_dynmat(v, src)
         enqueue_eigvals(v, src, no_lds)
         enqueue_thermo(v, src)
-    except Exception:   # (a refused handle among them) the handles made so far go, behind the work that was enqueued on them
-        torch.cuda.current_stream().synchronize()
-        release_handles(src)
-        raise
     return src
 
 
@@ -214,9 +171,8 @@ def analyze_records(v, records):
     VIB_MAX_ATOMS atoms (after the supercell), one that cannot be replicated and one whose handle is refused come back NaN with status -1;
     when a state's handle is refused its crystals are analysed one by one."""
     from .predictor import _valid_fields
-    from .structure import MASSES, lattice_matrix, make_supercell
-    m = v.predictor
-    dev = m.device
+    from .structure import make_supercell
+    dev = v.predictor.device
     records = list(records)
     n, K = len(records), len(v.temperatures)
     if v.supercell != (1, 1, 1):
@@ -232,18 +188,12 @@ def analyze_records(v, records):
     fields = [None if r is None else _valid_fields(r) for r in records]
     ok = [i for i, f in enumerate(fields) if f is not None and f[0].size <= _lib.VIB_MAX_ATOMS]
 
-    def enqueue(rows):
-        na = [int(fields[i][0].size) for i in rows]
-        z = np.concatenate([fields[i][0] for i in rows])
-        types = np.zeros((z.size, _lib.NUM_TYPES), np.float32)
-        types[np.arange(z.size), z - 1] = 1.0
-        frac = np.concatenate([fields[i][1] for i in rows]) % 1.0
-        lat = np.stack([lattice_matrix(fields[i][2], fields[i][3]) for i in rows])
-        mass = np.asarray(MASSES, dtype=np.float64)[z]
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
-        return rows, na, mass, analyze_state(v, (up(frac), up(lat), up(types)), na, mass)   # (MIError: a handle was refused; nothing is left behind)
+    def enqueue(_, rows):
+        na, state, mass = EA.pack_records(fields, rows, dev, masses=True)
+        return rows, na, mass, analyze_state(v, state, na, mass)   # (MIError: a handle was refused; nothing is left behind)
 
-    def read(rows, na, mass, src):
+    def read(st):
+        rows, na, mass, src = st
         small = torch.cat([src["c_v"], src["zpe"][:, None], src["asym"][:, None]] +
                           [src[k].to(torch.float64)[:, None] for k in ("n_imag", "n_zero", "sweeps", "status")], dim=1).cpu().numpy()
         freqs = src["freqs"].cpu().numpy()
@@ -257,36 +207,6 @@ def analyze_records(v, records):
             res["n_imag"][i], res["n_zero"][i], res["sweeps"][i], res["status"][i] = (int(small[k, K + 2 + j]) for j in range(4))
             res["frequencies"][i] = freqs[eo[k]:eo[k + 1]].copy()
 
-    pend, ran = [], False
-
-    def submit(rows):
-        nonlocal ran
-        pend.append(enqueue(rows))
-        ran = True
-        while len(pend) > 1:   # a state is read behind the next one's enqueue: the device stays busy, two workspaces are alive at most
-            read(*pend.pop(0))
-
-    try:
-        for s in range(0, len(ok), v.batch_size):   # source states of at most batch_size crystals
-            rows = ok[s:s + v.batch_size]
-            try:
-                submit(rows)
-            except _lib.MIError:
-                for i in rows:   # a handle of the state was refused: each crystal on its own, the refused one stays NaN with status -1
-                    try:
-                        submit([i])
-                    except _lib.MIError:
-                        pass
-        while pend:
-            read(*pend.pop(0))
-    finally:
-        for _, _, _, src in pend:   # (an error other than a refusal: nothing stays allocated)
-            torch.cuda.current_stream().synchronize()
-            release_handles(src)
-    if ran:   # operand conversions that left the fp16 plane format's range are counted process-wide: account for this call's own here
-        cnt = _lib.saturation_events(reset=True)
-        if cnt and (res["status"] == _lib.VIB_BAD_INPUT).any():
-            logging.warning(f"analyze_records: {cnt} operand conversions saturated in chunks that hold bad-input crystals (their results are NaN)")
-        elif cnt:
-            _lib.check_saturation_count(cnt, "analyze_records")
+    ran = EA.run_pipelined([(None, ok)], v.batch_size, enqueue, read, EA.release_pending)   # source states of at most batch_size crystals
+    EA.settle_saturation(ran, (res["status"] == _lib.VIB_BAD_INPUT).any(), "analyze_records")
     return res
