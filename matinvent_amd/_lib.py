@@ -488,6 +488,20 @@ SYM_CONV_SIGNATURES = {
     "mi_sym_conventional": (_I, [C.POINTER(SymConvArgs), _P]),
 }
 
+# the refined structure, include/matinvent_hip_sym_refine.h (site maps, orbits, positions and cell projected onto the group)
+SYM_REFINE_FAIL, SYM_REFINE_INFO, SYM_REFINE_STAT = 1024, 8, 4   # include/matinvent_hip_sym_refine.h
+
+
+class SymRefineArgs(C.Structure):
+    _fields_ = ([("set", SmPrepared)] +
+                [(k, C.c_void_p) for k in ("types", "frac", "lat", "sym_info", "sym_rot", "sym_trans", "out_frac", "out_lat", "orbit", "mult", "site_order",
+                                           "trans_ref", "refine_info", "refine_stat")])
+
+
+SYM_REFINE_SIGNATURES = {
+    "mi_sym_refine": (_I, [C.POINTER(SymRefineArgs), _P]),
+}
+
 # the substrate matcher, include/matinvent_hip_zsl.h (Zur-McGill superlattices, minimal coincident interface area)
 ZSL_MAX_MULT, ZSL_MAX_MILLER, ZSL_TABLE, ZSL_ROW_D, ZSL_ROW_I = 63, 8, 3276, 10, 20   # include/matinvent_hip_zsl.h
 ZSL_OK, ZSL_NO_MATCH, ZSL_MULT_CAP, ZSL_REDUCE_CAP, ZSL_BAD_CELL = 0, 1, 2, 3, 4
@@ -520,7 +534,7 @@ ZSL_SIGNATURES = {
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, SYM_SIGNATURES, SYM_CONV_SIGNATURES, ZSL_SIGNATURES, PHONON_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, SYM_SIGNATURES, SYM_CONV_SIGNATURES, SYM_REFINE_SIGNATURES, ZSL_SIGNATURES, PHONON_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
                         PRETRAIN_SIGNATURES)
 
 _lib = None

@@ -301,11 +301,13 @@ class Symmetry:
     `quantity` per structure -- n_ops (operations of the cell as given, pure translations included), pg_order (the point group's order),
     not_p1 (1.0 when there is any operation beyond the pure translations, else 0.0), crystal_system (1 triclinic .. 7 cubic), or, through
     symmetry.conventional_records, bravais (1 .. 14 in the order aP mP mS oP oS oI oF tP tI hR hP cP cI cF) or centring_mult
-    (the lattice points per conventional cell: 1, 2, 3 or 4).  NaN (->
+    (the lattice points per conventional cell: 1, 2, 3 or 4), or, through symmetry.refined_records, n_orbits (the
+    symmetry-inequivalent sites of the cell as given) or distortion (the root mean square distance in A between the atoms and their
+    places in the structure projected onto the group found).  NaN (->
     failed -> reward 0) on any status other than OK: a crystal the prepare guard flags, an ambiguous tolerance, more operations than the
     cap, a set that is not a group.  symprec in A (0.1: the reference's SpacegroupAnalyzer value)."""
 
-    QUANTITIES = ("n_ops", "pg_order", "not_p1", "crystal_system", "bravais", "centring_mult")
+    QUANTITIES = ("n_ops", "pg_order", "not_p1", "crystal_system", "bravais", "centring_mult", "n_orbits", "distortion")
 
     def __init__(self, quantity="n_ops", symprec=0.1, angle_tol=5.0, root_dir="rewards", device="cuda", **kwargs):
         if quantity not in self.QUANTITIES:
@@ -323,6 +325,11 @@ class Symmetry:
             _, conv = symmetry.conventional_records(list(strucs), self.symprec, self.angle_tol, self.device)
             out = (conv.bravais_index if self.quantity == "bravais" else conv.mult).astype(float)
             out[conv.status != _lib.SYM_OK] = np.nan
+            return out
+        if self.quantity in ("n_orbits", "distortion"):
+            _, ref = symmetry.refined_records(list(strucs), self.symprec, self.angle_tol, self.device)
+            out = (ref.n_orbits if self.quantity == "n_orbits" else ref.rms_move).astype(float)
+            out[ref.status != _lib.SYM_OK] = np.nan
             return out
         res = symmetry.find_symmetry(list(strucs), self.symprec, self.angle_tol, self.device)
         col = "pg_order" if self.quantity == "not_p1" else self.quantity

@@ -2,13 +2,17 @@
 run on (b, b) with a rigid metric, a nearest-atom test and every accepted (map, translation) item kept.  symprec = 0.1 A is the
 reference's value (SpacegroupAnalyzer(symprec=0.1)); angle_tol = 5 degrees is the matcher's and is untuned -- spglib's own lattice rule is
 [UPSTREAM-UNVERIFIED] and is not reproduced, and agreement with spglib is unverified (it is absent here).  Not built: the space-group
-number or Hall symbol, Wyckoff positions, idealised cell parameters, symmetry reduction of the vibration or elastic displacement sets,
-magnetic and disordered structures.
+number or Hall symbol, Wyckoff letters, symmetry reduction of the vibration or elastic displacement sets, magnetic and disordered
+structures.
 
 The conventional cell (include/matinvent_hip_sym_conv.h): conventional_arrays / conventional_records reduce every crystal to
 its primitive cell, analyse that again and build the conventional basis, the centring and the Bravais lattice from the rotation parts.
 The rules are this build's own; pymatgen's get_conventional_standard_structure and spglib's standardisation are [UPSTREAM-UNVERIFIED]
-(both are absent here) and are not claimed to be reproduced beyond them."""
+(both are absent here) and are not claimed to be reproduced beyond them.
+
+The refined structure (include/matinvent_hip_sym_refine.h): refine_arrays / refined_records project the coordinates and the cell
+of every crystal onto the group found at symprec and return the site orbits, their multiplicities and the orders of the site-symmetry
+groups; symmetry_primitive_records stands where the reference's get_symmetry_primitive does."""
 import ctypes as C
 import math
 
@@ -253,3 +257,158 @@ def conventional_records(records, symprec=SYMPREC, angle_tol=ANGLE_TOL, device="
         params[b] = lengths + angles
         out.append(SimpleStructure(lengths, angles, [int(v) for v in z[off[b]:off[b + 1]]], f[off[b]:off[b + 1]].astype(np.float64)))
     return out, ConventionalResult(info, M, params)
+
+
+# ---- the refined structure ----------------------------------------------------------------------------------------------------------
+REFINE_INFO = ("n_orbits", "n_ops", "zero2", "zero3", "zero4", "zero5", "zero6", "status")
+REFINE_STAT = ("max_move", "rms_move", "cell_change", "max_residual")
+REFINE_CELLS = ("given", "primitive", "conventional")
+
+
+class Refined:
+    """The arrays of mi_sym_refine on the device, with the arrays it refined: offsets [B + 1], types [rows] (the first offsets[B] rows are
+    atoms), frac [rows, 3] and lat [B, 9] float32 (refined), orbit, mult, site_order [rows] (orbit: the lowest equivalent atom, an index
+    inside its crystal), trans_ref [B, 192, 3], info [B, 8] (n_orbits, n_ops, .., status), stat [B, 4] float64 (max move, rms move, cell
+    change, max residual in the prepared set's units) and tol [B], the tolerances the analysis ran with."""
+
+    def __init__(self, offsets, types, frac, lat, orbit, mult, site_order, trans_ref, info, stat, tol=None):
+        self.offsets, self.types, self.frac, self.lat, self.orbit, self.mult, self.site_order = offsets, types, frac, lat, orbit, mult, site_order
+        self.trans_ref, self.info, self.stat, self.tol = trans_ref, info, stat, tol
+
+
+def refine_prepared(prepared, types, frac, lat, sym, fill=None):
+    """mi_sym_refine on device tensors: the prepared set, the arrays it was prepared from and the SymmetryResult of it.  `fill` builds the
+    output tensors (tests poison them)."""
+    lib = _lib.load()
+    dev = prepared.lat.device
+    B, N = prepared.B, prepared.N
+    types, frac, lat = types.to(torch.int32).contiguous(), frac.to(torch.float32).contiguous(), lat.to(torch.float32).reshape(-1, 9).contiguous()
+    z = (lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)) if fill is None else fill
+    M = max(N, 1)
+    out = Refined(prepared.offsets, types, z((M, 3), torch.float32), z((B, 9), torch.float32), z((M,), torch.int32), z((M,), torch.int32), z((M,), torch.int32),
+                  z((B, _lib.SYM_MAX_OPS, 3), torch.float64), z((B, _lib.SYM_REFINE_INFO), torch.int32), z((B, _lib.SYM_REFINE_STAT), torch.float64), sym.tol)
+    if B:
+        p = lambda t: t.data_ptr()
+        args = _lib.SymRefineArgs(prepared.struct(), p(types), p(frac), p(lat), p(sym.info), p(sym.rot), p(sym.trans), p(out.frac), p(out.lat), p(out.orbit),
+                                  p(out.mult), p(out.site_order), p(out.trans_ref), p(out.info), p(out.stat))
+        _lib.check(lib.mi_sym_refine(C.byref(args), torch.cuda.current_stream().cuda_stream), "mi_sym_refine")
+    return out
+
+
+def _refine_stage(offsets, types, frac, lat, tol, angle_tol, earlier=None):
+    """prepare -> find -> refine of one stage's arrays.  A crystal the prepare guard rejects (a conventional cell of more than 64 atoms) has
+    nothing written by the entry: its rows come back as this stage received them, every atom an orbit of its own.  `earlier`: the fail bits
+    of the stages before ([B] int32), joined to the status."""
+    types, frac, lat = types.to(torch.int32).contiguous(), frac.to(torch.float32).contiguous(), lat.to(torch.float32).reshape(-1, 9).contiguous()
+    prepared = matching.prepare_arrays(offsets, types, frac, lat)
+    sym = find_symmetry_prepared(prepared, tol, angle_tol)
+    out = refine_prepared(prepared, types, frac, lat, sym)
+    B, rows = prepared.B, out.frac.shape[0]
+    if B:
+        off = offsets.to(torch.int64)
+        skipped = (out.info[:, -1] & _lib.SYM_NOT_PREPARED) != 0                                                 # [B]
+        atom = torch.arange(rows, device=off.device)
+        owner = torch.searchsorted(off[1:].contiguous(), atom, right=True).clamp_(max=B - 1)                  # the crystal of a row
+        mine = skipped[owner]
+        local, one = (atom - off[owner]).to(torch.int32), torch.ones_like(out.mult)
+        if prepared.N:
+            out.frac = torch.where(mine[:, None], frac[:rows], out.frac)
+            out.orbit, out.mult, out.site_order = torch.where(mine, local, out.orbit), torch.where(mine, one, out.mult), torch.where(mine, one, out.site_order)
+        out.lat = torch.where(skipped[:, None], lat, out.lat)
+        if earlier is not None:
+            out.info[:, -1] |= earlier.to(torch.int32)
+    return out
+
+
+def refine_arrays(offsets, types, frac, lat, tol, angle_tol=ANGLE_TOL, cell="given"):
+    """The refined crystals on device tensors, nothing read back in between: a Refined.  cell="given": prepare -> mi_sym_find ->
+    mi_sym_refine.  cell="primitive": reduce_arrays first, then the same on its output.  cell="conventional": conventional_arrays first,
+    then the same.  The later analyses run with the caller's tolerances: they are in the prepared set's units (unit volume per atom), which
+    both changes of cell keep.  A crystal a later stage cannot take comes back as the stage before produced it, with SYM_REFINE_FAIL; a
+    crystal an earlier stage left as it was (SYM_PRIM_FAIL, SYM_CONV_FAIL) is refined in the cell it has and carries that bit."""
+    if cell not in REFINE_CELLS:
+        raise ValueError(f"refine_arrays: cell {cell!r} is none of {REFINE_CELLS}")
+    if cell == "given":
+        return _refine_stage(offsets, types, frac, lat, tol, angle_tol)
+    if cell == "primitive":
+        prim, _ = reduce_arrays(offsets, types, frac, lat, tol, angle_tol)
+        return _refine_stage(prim.offsets, prim.types, prim.frac, prim.lat, tol, angle_tol, prim.status & _lib.SYM_PRIM_FAIL)
+    conv, _ = conventional_arrays(offsets, types, frac, lat, tol, angle_tol)
+    return _refine_stage(conv.offsets, conv.types, conv.frac, conv.lat, tol, angle_tol, conv.info[:, -1] & _lib.SYM_CONV_FAIL)
+
+
+class RefineResult:
+    """Per record, as numpy, from one read: status (the find status of the cell refined, with SYM_REFINE_FAIL = 1024 where the record came
+    back as it was), n_ops, n_orbits (symmetry-inequivalent sites), max_move, rms_move and max_residual in A (the prepared set's units
+    times (V / n)^(1/3) of the record), cell_change (max |Gbar - G| / max |G|), cell_parameters [B, 6] of the returned records, and per
+    record i orbits(i), multiplicity(i), site_symmetry_order(i) in the atom order of the returned record."""
+
+    def __init__(self, info, stat, scale, offsets, orbit, mult, site_order, cell_parameters):
+        self.info, self.offsets, self._orbit, self._mult, self._site = info, offsets, orbit, mult, site_order
+        self.status, self.n_orbits, self.n_ops = info[:, 7].copy(), info[:, 0].copy(), info[:, 1].copy()
+        self.max_move, self.rms_move, self.max_residual = stat[:, 0] * scale, stat[:, 1] * scale, stat[:, 3] * scale
+        self.cell_change, self.cell_parameters = stat[:, 2].copy(), cell_parameters
+
+    def __len__(self):
+        return len(self.info)
+
+    def _rows(self, arr, i):
+        return arr[int(self.offsets[i]):int(self.offsets[i + 1])].copy()
+
+    def orbits(self, i):
+        """Per atom of record i the lowest equivalent atom (an index into the record)."""
+        return self._rows(self._orbit, i)
+
+    def multiplicity(self, i):
+        return self._rows(self._mult, i)
+
+    def site_symmetry_order(self, i):
+        return self._rows(self._site, i)
+
+
+def refined_records(records, symprec=SYMPREC, angle_tol=ANGLE_TOL, device="cuda", cell="given"):
+    """(records, RefineResult): every record with its coordinates and its cell projected onto the group found at symprec, as a
+    SimpleStructure in the cell asked for ("given", "primitive", "conventional").  Never drops or reorders; a record whose status is not OK
+    is returned as the same object, with one orbit per atom."""
+    from .data import SimpleStructure
+    if cell not in REFINE_CELLS:
+        raise ValueError(f"refined_records: cell {cell!r} is none of {REFINE_CELLS}")
+    if len(records) == 0:
+        e = np.zeros(0, np.int32)
+        return [], RefineResult(np.zeros((0, _lib.SYM_REFINE_INFO), np.int32), np.zeros((0, _lib.SYM_REFINE_STAT)), np.zeros(0), np.zeros(1, np.int64), e, e, e,
+                                np.zeros((0, 6)))
+    na, offsets, types, frac, lat, tol = _upload(records, device, symprec)
+    ref = refine_arrays(offsets, types, frac, lat, tol, angle_tol, cell)
+    info, stat, off = ref.info.cpu().numpy(), ref.stat.cpu().numpy(), ref.offsets.cpu().numpy().astype(np.int64)
+    z, f, L = ref.types.cpu().numpy(), ref.frac.cpu().numpy(), ref.lat.cpu().numpy().reshape(-1, 3, 3).astype(np.float64)
+    orbit, mult, site = (t.cpu().numpy().copy() for t in (ref.orbit, ref.mult, ref.site_order))
+    scale = float(symprec) / np.asarray(tol, np.float64)   # (V / n)^(1/3) of every record: the changes of cell keep V / n
+    out, params, out_off = [], np.full((len(records), 6), np.nan), [0]
+    o2, m2, s2 = [], [], []
+    for b, rec in enumerate(records):
+        lo, hi = int(off[b]), int(off[b + 1])
+        if info[b, 7] != _lib.SYM_OK:
+            out.append(rec)
+            n = int(na[b])
+            o2.append(np.arange(n, dtype=np.int32)), m2.append(np.ones(n, np.int32)), s2.append(np.ones(n, np.int32))
+            info[b, 0] = n
+            stat[b] = 0.0
+            try:
+                params[b] = list(np.asarray(rec.lengths, np.float64).reshape(-1)) + list(np.asarray(rec.angles, np.float64).reshape(-1))
+            except Exception:
+                pass
+        else:
+            lengths, angles = _parameters(L[b])
+            params[b] = lengths + angles
+            out.append(SimpleStructure(lengths, angles, [int(v) for v in z[lo:hi]], f[lo:hi].astype(np.float64)))
+            o2.append(orbit[lo:hi]), m2.append(mult[lo:hi]), s2.append(site[lo:hi])
+        out_off.append(out_off[-1] + len(o2[-1]))
+    return out, RefineResult(info, stat, scale, np.asarray(out_off, np.int64), np.concatenate(o2), np.concatenate(m2), np.concatenate(s2), params)
+
+
+def symmetry_primitive_records(records, symprec=SYMPREC, angle_tol=ANGLE_TOL, device="cuda"):
+    """refined_records(..., cell="primitive"): the refined structure in its primitive cell, the place of the reference's
+    get_symmetry_primitive (SpacegroupAnalyzer(symprec=0.1).get_refined_structure().get_primitive_structure()).  The choice of cell is this
+    build's own (the first basis triple of the translation lattice); pymatgen's choice is [UPSTREAM-UNVERIFIED] (it is absent
+    here) and is not claimed to be reproduced."""
+    return refined_records(records, symprec, angle_tol, device, cell="primitive")
