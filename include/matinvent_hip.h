@@ -105,6 +105,8 @@ int mi_knn_graph(mi_batch* b, const float* frac, const float* lattices, void* st
  * and read the edge count on the device (the reference pays a host synchronisation per evaluation, models/diffcsp/cspnet.py:243-257 -> utils.py:335-514:
  * nonzero / masked_select).  A list over capacity cannot raise in the middle of an enqueued chain; it sets a sticky flag instead and contributes no edges.
  * This call synchronises `stream`, returns MI_ECAPACITY (and clears the flag) if any build since the last call exceeded the capacity, MI_OK otherwise.
+ * It also takes the last list's edge count from the device: until then the handle carries the capacity, afterwards mi_batch_num_edges and mi_knn_graph_read
+ * describe the list itself (no edges behind MI_ECAPACITY).
  * matinvent_amd.diffcsp asks it wherever a chain's results are about to be read. */
 int mi_knn_graph_status(mi_batch* b, void* stream);
 /* Copy out the current list: edges [2][E''] int32 (row 0 = aggregation/source node, row 1 = neighbour) and
@@ -384,7 +386,7 @@ void mi_gbatch_destroy(mi_gbatch* b);
  * synchronisation (the edge count sizes the later launches).  *num_edges = E. */
 int mi_gemnet_graph(mi_gemnet* net, mi_gbatch* b, const float* pos, const float* cell, void* stream, int64_t* num_edges);
 /* copy out the current graph (any pointer may be NULL): src/dst [E], img [E][3], swap [E] (index of the reverse edge),
- * rowptr [N+1] (edges are sorted by dst), D [E], V [E][3] (unit vector from dst to the periodic image of src) */
+ * rowptr [N+1] (edges are sorted by dst), D [E], V [E][3] (unit vector from dst to the periodic image of src); E = rowptr[N] */
 int mi_gemnet_graph_read(const mi_gbatch* b, int* src, int* dst, int* img, int* swap, int* rowptr, float* D, float* V, void* stream);
 /* The denoiser.  `train` is a bit set: 1 keeps the activations for mi_gemnet_backward (one pending backward per batch handle);
  * 2 (inference only) runs WITHOUT the host synchronisation that reads the graph's edge count: the edge-level launches are sized by the
@@ -400,7 +402,9 @@ int mi_gemnet_backward(mi_gemnet* net, mi_gbatch* b, const float* d_pos, const f
  * the periodic graph at some evaluation (1: more than max_neighbors kept pairs of one atom, 2: more than 512 atoms inside the cutoff
  * even after shrinking it, 4: an in-degree above 128) and ran without edges from then on: its sample is invalid, the others are
  * unaffected.  The counterpart of the reference's per-crystal invalid_filter (pipeline/filters/opt_filter.py:49-61), which drops
- * collapsed crystals one by one after sampling.  bad_host (B ints) and n_bad may be NULL.  Waits for the work queued on `stream`. */
+ * collapsed crystals one by one after sampling.  bad_host (B ints) and n_bad may be NULL.  Waits for the work queued on `stream`.
+ * Behind forwards without a host round trip it also takes the last graph's edge count from the device: until then the handle
+ * carries the capacity and mi_gemnet_graph_read refuses (MI_ESTATE); afterwards it copies the last graph, E = rowptr[N] rows. */
 int mi_gbatch_graph_status(mi_gbatch* b, int* bad_host, int* n_bad, void* stream);
 /* parity taps of the most recent forward: "h<i>" [N,emb_atom], "m<i>" [E,emb_edge] after block i (0 = embedding), "rbf" [E,num_radial] */
 int mi_gemnet_tap(mi_gbatch* b, const char* name, float* out, int64_t capacity, int64_t* numel, void* stream);

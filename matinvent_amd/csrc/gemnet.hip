@@ -2166,6 +2166,7 @@ static int graph_build(mi_gemnet* net, mi_gbatch* b, const float* pos, const flo
         return MI_OK;
     }
     int meta[4];
+    b->E = 0;   // (a build that fails below leaves no list on the handle)
     MI_HIP(hipMemcpyAsync(meta, b->meta, sizeof(meta), hipMemcpyDeviceToHost, s));
     MI_HIP(hipStreamSynchronize(s));
     MI_CHECK(meta[2] == 0, MI_ECAPACITY, "periodic graph: capacity exceeded (flags %d: 1 = more than max_neighbors kept pairs of one atom, 2 = more than %d atoms "
@@ -2754,6 +2755,8 @@ __global__ void code_to_img_kernel(const int* __restrict__ code, int* __restrict
 
 int mi_gemnet_graph_read(const mi_gbatch* b, int* src, int* dst, int* img, int* swap, int* rowptr, float* D, float* V, void* stream) {
     MI_CHECK(b, MI_EINVAL, "null handle");
+    // (behind a forward without a host round trip b->E is the capacity: E_cap rows, most of them stale, for a caller that sized its arrays by rowptr[N])
+    MI_CHECK(!b->nosync, MI_ESTATE, "the graph's edge count is still on the device (forwards without a host round trip): ask mi_gbatch_graph_status first");
     hipStream_t s = (hipStream_t)stream;
     const size_t E = (size_t)b->E;
     if (src) MI_HIP(hipMemcpyAsync(src, b->src, E * sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -2832,6 +2835,16 @@ int mi_gbatch_graph_status(mi_gbatch* b, int* bad_host, int* n_bad, void* stream
             nb += b->status_h[i] != 0;
         }
     }
+    if (b->nosync) {
+        // The chain's last forward left E = E_cap on the handle, with the count on the device.  The stream has just been drained: take the count, so that
+        // mi_gemnet_graph_read describes the list and not its capacity.  (Every forward rebuilds the graph and sets both again; the
+        // activations of that forward stay a compact arena, which is what mi_gemnet_tap refuses.)
+        int meta0 = 0;
+        MI_HIP(hipMemcpyAsync(&meta0, b->meta, sizeof(int), hipMemcpyDeviceToHost, s));
+        MI_HIP(hipStreamSynchronize(s));
+        b->E = std::min<int64_t>(std::max(meta0, 0), b->E_cap);
+        b->nosync = false;
+    }
     if (n_bad) *n_bad = nb;
     return MI_OK;
 }
@@ -2845,7 +2858,7 @@ int mi_gemnet_tap(mi_gbatch* b, const char* name, float* out, int64_t capacity, 
     MI_CHECK(b && name, MI_EINVAL, "null argument");
     auto it = b->taps.find(name);
     MI_CHECK(it != b->taps.end(), MI_EINVAL, "unknown tap %s", name);
-    MI_CHECK(!b->nosync, MI_ESTATE, "taps exist after a synchronising forward only (the sampler's forwards keep the edge count on the device)");
+    MI_CHECK(!b->nosync && !b->compact, MI_ESTATE, "taps exist after a synchronising forward only (the sampler's forwards keep the edge count on the device)");
     if (numel) *numel = it->second.second;
     if (out) {
         MI_CHECK(capacity >= it->second.second, MI_EINVAL, "tap %s needs %lld floats", name, (long long)it->second.second);

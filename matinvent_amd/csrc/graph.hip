@@ -199,11 +199,19 @@ __global__ __launch_bounds__(1024) void knn_scan_kernel(const int* __restrict__ 
         const bool over = meta[2] != 0 || (int64_t)E > E_cap || meta[1] > deg_cap;
         meta[0] = E;
         if (over) {
+            meta[2] = 1;          // (the emit kernel's test: a list over ANY capacity -- the degree's included -- is not emitted)
             meta[3] = 1;
             meta[4] = E;          // (what the host reports; the edge count the consumers see is zeroed below, after the emit kernel's own test)
             meta[5] = meta[1];
         }
+        part[0] = over;
     }
+    __syncthreads();
+    // A list over capacity leaves NO row spans behind.  The consumers of a build without a host round trip are launched whatever the verdict, and those that walk
+    // rowptr -- finalize_agg_kernel, node_chain.hip's phase A -- read one slot of mi_batch::part per 32-row block a span touches: `part` holds deg_cap / 32 + 2
+    // slots, a span longer than deg_cap can touch more.  With every span empty they read nothing, and the in-edge sums of a backward pass visit nothing.
+    if (part[0])
+        for (int k = tid; k <= N; k += 1024) rowptr[k] = 0;
 }
 // behind the emit kernel of a build without a host round trip: a list over capacity was not emitted -- its consumers (sized by capacity, row count from meta[0]) get none
 __global__ void knn_publish_kernel(int* __restrict__ meta, int64_t E_cap, int deg_cap) {
@@ -432,10 +440,16 @@ int mi_knn_graph_status(mi_batch* b, void* stream) {
     MI_HIP(hipStreamSynchronize(s));
     if (meta[3] != 0) {
         MI_HIP(hipMemsetAsync(b->kn_meta + 3, 0, 3 * sizeof(int), s));
+        b->E = 0;             // (nothing on the handle describes a list any more: mi_batch_num_edges and mi_knn_graph_read report none)
+        b->e_dev = nullptr;
         mi::set_error("a knn graph built inside the chain exceeded its capacity (edges %d of %lld, max degree %d of %d): the chain's results are invalid; raise edge_cap_per_node",
                       meta[4], (long long)b->E_cap, meta[5], b->deg_cap);
         return MI_ECAPACITY;
     }
+    // The host has now seen the count of the chain's last list: the handle describes that list, not its capacity (a build without a host round trip left
+    // E = E_cap and e_dev set; mi_batch_num_edges and mi_knn_graph_read go by E).  Every forward of a knn handle rebuilds the list and sets both again.
+    b->E = std::min<int64_t>(meta[0], b->E_cap);
+    b->e_dev = nullptr;
     b->e_hint = std::max<int64_t>(meta[0], 1);   // (the size of the chain's last list: the form hint of the next chain's launches)
     return MI_OK;
 }

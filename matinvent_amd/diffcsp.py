@@ -672,7 +672,9 @@ class DiffCSPModule(nn.Module):
         pending, self.__dict__["_knn_pending"] = self.__dict__.get("_knn_pending", []), []
         lib = _lib.load()
         for cb, stream in pending:
-            _lib.check(lib.mi_knn_graph_status(cb._h, C.c_void_p(stream.cuda_stream)), "mi_knn_graph_status")
+            rc = lib.mi_knn_graph_status(cb._h, C.c_void_p(stream.cuda_stream))
+            cb.num_edges = int(lib.mi_batch_num_edges(cb._h))   # (the chain's last list, now that the host has seen its count; none behind a capacity error)
+            _lib.check(rc, "mi_knn_graph_status")
 
     @contextlib.contextmanager
     def _conditioned(self, pairs, condition=True, likelihood=False, resample=None):

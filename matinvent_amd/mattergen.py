@@ -162,8 +162,17 @@ class GBatch:
         n = C.c_int64()
         self._net.sync()
         _lib.check(self._lib.mi_gemnet_graph(self._net._h, self._h, _ptr(pos), _ptr(cell), _stream(), C.byref(n)), "mi_gemnet_graph")
-        E = int(n.value)
+        return self.read_graph(int(n.value))
+
+    def read_graph(self, E=None):
+        """The graph the handle holds now, without building one: dict(src, dst, img, swap, rowptr, D, V); E = rowptr[N] unless given.  Behind a
+        sampler run without a host round trip the handle knows its edge count once `graph_status` has been asked; until then the library
+        refuses the read (MI_ESTATE)."""
         i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=self._dev)
+        if E is None:
+            rp = i32(self.num_nodes + 1)
+            _lib.check(self._lib.mi_gemnet_graph_read(self._h, None, None, None, None, _ptr(rp), None, None, _stream()), "mi_gemnet_graph_read")
+            E = int(rp[-1])
         out = dict(src=i32(E), dst=i32(E), img=i32(E, 3), swap=i32(E), rowptr=i32(self.num_nodes + 1), D=torch.empty(E, device=self._dev),
                    V=torch.empty(E, 3, device=self._dev))
         _lib.check(self._lib.mi_gemnet_graph_read(self._h, *(_ptr(out[k]) for k in ("src", "dst", "img", "swap", "rowptr", "D", "V")), _stream()),

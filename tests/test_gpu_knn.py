@@ -283,6 +283,28 @@ def test_knn_capacity_error_inside_a_chain_is_raised_behind_it():
         m.sample(box, step_lr=5e-6, seed=4)
         with pytest.raises(RuntimeError, match="capacity"):
             m.sample(box, step_lr=5e-6, seed=5)  # the next call reports the previous call's chains first
+        # with the error reported, the handle describes no list (it used to go on reporting the capacity, 2 x 4 x 40 rows of stale edges)
+        cb = m.crystal_batch(box)
+        assert int(lib.mi_batch_num_edges(cb._h)) == 0 and cb.num_edges == 0
+        assert cb.edges("reference")[0].shape == (2, 0) and cb.edges("csr")[1].shape == (0, 3)
+        # ... and is as good as new: one step from a geometry INSIDE the capacity (skewed N(0,1) cells, coordinates in the home cell as the chain
+        # keeps them: at most 2 edges per atom, checked with the oracle right here) is bit for bit the step on a fresh handle -- the over-capacity
+        # builds left no row span, degree or table behind
+        from tests import knn_cases as K
+        frac, lat = K.sparse([20, 20], 251)
+        frac = frac % 1.0
+        edges_ref, _ = O.knn_edges(frac, lat, box.num_atoms, 20)
+        assert 0 < K.max_degree(edges_ref, 40) <= 2 < m.decoder.edge_cap_per_node and K.margin(frac, lat, [20, 20]) > 1e-2
+        init = (frac, lat, torch.randn(40, 100, generator=torch.Generator().manual_seed(9)))
+        runs = []
+        for bx in (box, Box(torch.tensor([20, 20]))):
+            _, traj = m.sample(bx, step_lr=5e-6, seed=6, init=init, t_start=1, t_stop=0, record=True)
+            m.check_graph()                       # (inside the capacity on the device as well)
+            runs.append(traj)
+        assert m.crystal_batch(box) is cb and int(lib.mi_batch_num_edges(cb._h)) > 0
+        for t in runs[0]:
+            for k in ("atom_types", "frac_coords", "lattices"):
+                assert torch.equal(runs[0][t][k], runs[1][t][k]), (t, k)
     finally:
         lib.mi_debug_set_knn_nosync(was)
         m.__dict__["_knn_pending"] = []

@@ -309,6 +309,36 @@ def test_sampler_without_a_host_round_trip_equals_the_synchronising_form():
     assert _lib.saturation_events(reset=True) == 0
 
 
+def test_graph_read_after_a_sampler_run_without_a_host_round_trip_equals_the_synchronising_form():
+    """The chain's forwards leave the CAPACITY as the handle's edge count (the real count stays on the device).  Once graph_status() has
+    been asked -- last_sample_invalid() does -- the handle describes the last evaluation's graph: reading it returns the rows, and only
+    the rows, that the synchronising form leaves (it used to copy capacity-many rows, most of them stale)."""
+    from matinvent_amd import _lib
+    lib = _lib.load()
+    hpd = dict(M.TINY, emb_atom=128, emb_edge=128)
+    hp = M.GemNetHParams(**hpd)
+    m = _module(hpd, M.init_params(hp, seed=6, head_scale=20.0))
+    na = [20] * 40 + [7, 12, 1, 20]
+    graphs = []
+    try:
+        for mode in (0, 1):
+            lib.mi_debug_set_mg_nosync(mode)
+            m.sample(na, n_steps=1000, seed=9, i_stop=3)
+            (gb,) = m._last_chain_batches
+            if mode == 1:   # (the count is still on the device: no read of capacity-many rows)
+                with pytest.raises(RuntimeError, match="mi_gbatch_graph_status"):
+                    gb.read_graph()
+            assert not bool(m.last_sample_invalid().any())
+            graphs.append({k: v.clone() for k, v in gb.read_graph().items()})
+    finally:
+        lib.mi_debug_set_mg_nosync(1)
+    g0, g1 = graphs
+    E = g0["src"].shape[0]
+    assert 0 < E == int(g0["rowptr"][-1]) < sum(na) * 2 * hp.max_neighbors
+    for k in ("src", "dst", "img", "swap", "rowptr", "D", "V"):
+        assert g1[k].shape == g0[k].shape and torch.equal(g1[k], g0[k]), k
+
+
 def test_sampler_with_fitted_scale_factors_takes_the_synchronising_form():
     """GemNet's ScalingFactors with values other than one are elementwise passes on fp32 rows (op_scale), which the plane-only program of the
     no-round-trip forwards does not have: the chain then runs on the synchronising form whatever mi_debug_set_mg_nosync says (same samples both ways,
