@@ -502,6 +502,20 @@ SYM_REFINE_SIGNATURES = {
     "mi_sym_refine": (_I, [C.POINTER(SymRefineArgs), _P]),
 }
 
+# symmetry-constrained sampling, include/matinvent_hip_symc.h (a batch handle's group, orbits and affine maps; the per-step projection)
+SYMC_MAX_ATOMS, SYMC_MAX_OPS = 256, 192   # include/matinvent_hip_symc.h
+
+
+class SymmetryConstraint(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("op_off_host", "rot_host", "distinct_off_host", "distinct_host", "rep_host", "Q_host", "d_host")]
+
+
+SYMC_SIGNATURES = {
+    "mi_batch_set_symmetry": (_I, [_P, C.POINTER(SymmetryConstraint)]),
+    "mi_symmetry_apply": (_I, [_P, _P, _P, _P, _P]),
+    "mi_symmetry_failures": (_I, [_P, C.POINTER(_I)]),
+}
+
 # the substrate matcher, include/matinvent_hip_zsl.h (Zur-McGill superlattices, minimal coincident interface area)
 ZSL_MAX_MULT, ZSL_MAX_MILLER, ZSL_TABLE, ZSL_ROW_D, ZSL_ROW_I = 63, 8, 3276, 10, 20   # include/matinvent_hip_zsl.h
 ZSL_OK, ZSL_NO_MATCH, ZSL_MULT_CAP, ZSL_REDUCE_CAP, ZSL_BAD_CELL = 0, 1, 2, 3, 4
@@ -534,7 +548,7 @@ ZSL_SIGNATURES = {
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, SYM_SIGNATURES, SYM_CONV_SIGNATURES, SYM_REFINE_SIGNATURES, ZSL_SIGNATURES, PHONON_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, SYM_SIGNATURES, SYM_CONV_SIGNATURES, SYM_REFINE_SIGNATURES, SYMC_SIGNATURES, ZSL_SIGNATURES, PHONON_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
                         PRETRAIN_SIGNATURES)
 
 _lib = None

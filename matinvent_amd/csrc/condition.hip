@@ -254,7 +254,7 @@ int mi_batch_set_condition(mi_batch* b, const mi_condition* cond, const float* l
     MI_NO_POOLED(b, "mi_batch_set_condition");
     MI_CHECK(b, MI_EINVAL, "null handle");
     if (!cond) {
-        b->cond_on = b->cond_any = false;
+        b->cond_on = b->cond_any = b->cond_has_x = b->cond_has_l = false;
         b->cond_levels = 0;
         return MI_OK;
     }
@@ -277,7 +277,7 @@ int mi_batch_set_condition(mi_batch* b, const mi_condition* cond, const float* l
         for (int i = 0; i < 9 * B; ++i)
             MI_CHECK(!cond->known_lattice_host[i / 9] || std::isfinite(cond->lat0_host[i]), MI_EINVAL, "known lattice %d has a non-finite entry", i / 9);
 
-    b->cond_on = b->cond_any = false;   // (a failed copy below leaves no half-written condition attached)
+    b->cond_on = b->cond_any = b->cond_has_x = b->cond_has_l = false;   // (a failed copy below leaves no half-written condition attached)
     b->cond_levels = 0;
     // parts with nothing known keep a NULL-mask meaning for the kernel: their arrays are not uploaded and not read
     std::vector<int> zeros;
@@ -305,6 +305,7 @@ int mi_batch_set_condition(mi_batch* b, const mi_condition* cond, const float* l
     MI_HIP(hipMemcpy(b->cond_table, level_table_host, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice));
     b->cond_levels = n;
     b->cond_any = kt || kx || kl;
+    b->cond_has_x = kx, b->cond_has_l = kl;
     b->cond_on = true;
     return MI_OK;
 }

@@ -862,6 +862,7 @@ template int dev_alloc<float>(mi_batch*, float**, size_t);
 template int dev_alloc<int>(mi_batch*, int**, size_t);
 template int dev_alloc<unsigned short>(mi_batch*, unsigned short**, size_t);
 template int dev_alloc<unsigned>(mi_batch*, unsigned**, size_t);
+template int dev_alloc<double>(mi_batch*, double**, size_t);   // (sym_constraint.hip; its entries refuse a pooled handle)
 
 // bench.py's roofline hook: bracket the dominant stage (the per-edge MLP of one layer) with events
 struct ProfSlot {

@@ -221,6 +221,7 @@ struct mi_batch {
     int cond_table_cap = 0;
     int *cond_kt = nullptr, *cond_kx = nullptr, *cond_kl = nullptr, *cond_types0 = nullptr;   // [N], [N], [B], [N] (allocated on first use)
     float *cond_frac0 = nullptr, *cond_lat0 = nullptr, *cond_table = nullptr;                  // [N][3], [B][9], [cond_levels][3]
+    bool cond_has_x = false, cond_has_l = false;   // ... a coordinate / a lattice among the known (what a symmetry constraint refuses)
     // likelihood mask (condition.hip, mi_batch_set_likelihood_mask): the elements whose predictor terms leave the trajectory
     // likelihood -- state of its own, apart from the condition above (a policy-gradient handle carries the masks alone)
     bool lik_on = false;
@@ -273,6 +274,13 @@ struct mi_batch {
     float* ig_wT = nullptr;                           // [L][6F][H]
     const void* ig_net = nullptr;
     uint64_t ig_epoch = 0;
+    // symmetry constraint (sym_constraint.hip, mi_batch_set_symmetry): per crystal the operation count and the distinct rotation
+    // parts, per atom the orbit representative and the affine map from its coordinates; the failure counters of the cell projection
+    bool symc_on = false;          // a constraint is attached (mi_sampler_run imposes it; false: the chain's launches are those of before)
+    bool symc_any = false;         // ... and at least one crystal has more than the identity (none: no launch)
+    int symc_rot_cap = 0;
+    int *symc_K = nullptr, *symc_roff = nullptr, *symc_rot = nullptr, *symc_rep = nullptr, *symc_fail = nullptr;   // [B], [B + 1], [roff[B]][9], [N], [B]
+    double *symc_Q = nullptr, *symc_d = nullptr;                                                                    // [N][9], [N][3]
     mi_pool* pool = nullptr;
     std::vector<int> edge_off_h, pair_off_h;
     int* edge_off = nullptr;   // [B + 1] first edge of each crystal (pooled handles only)
@@ -441,6 +449,10 @@ int time_map_same(const mi_batch* p, const mi_batch* q, const char* what);
 int condition_check(const mi_batch* b, int T, const char* what);
 int condition_impose(const mi_batch* b, int level, uint64_t seed, float* atom_types, float* frac, float* lattices, float* rec_types, float* rec_frac,
                      float* rec_lat, hipStream_t s);
+// sym_constraint.hip: mi_sampler_run's host-side check of a handle with a symmetry constraint (MI_EINVAL with the message set) and the
+// projection of a state (one launch, none when every crystal has the identity alone)
+int symmetry_check(const mi_batch* b, bool has_noise, bool has_rec, const char* what);
+int symmetry_impose(const mi_batch* b, float* atom_types, float* frac, float* lattices, hipStream_t s);
 // ... and the entries' host-side check that two handles of one call carry the same likelihood mask, or none (MI_EINVAL with the message set)
 int likelihood_mask_same(const mi_batch* p, const mi_batch* q, const char* what);
 // ... and the masked form of the sampler's predictor launch (logprob.h: PredictorArgs), for a recording chain on a handle with a condition and a mask

@@ -249,6 +249,8 @@ static int sampler_step(mi_net* net, mi_batch* b, int t, uint64_t seed, const fl
     }
     // ... and at the level the step arrived at: the known elements of the state and of its record are overwritten (the corrector is left alone)
     if (b->cond_on) MI_TRY(condition_impose(b, t - 1, seed, atom_types, frac, lattices, a.rec_types, a.rec_frac, a.rec_lat, s));
+    // ... and the symmetry constraint (sym_constraint.hip): the state projected onto the template's group, behind the condition
+    if (b->symc_on) MI_TRY(symmetry_impose(b, atom_types, frac, lattices, s));
     return MI_OK;
 }
 
@@ -295,6 +297,7 @@ int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int 
     MI_TRY(condition_check(b, T, "the batch handle"));
     MI_TRY(resample_check(b, T, t_start, t_stop, noise != nullptr, rec != nullptr, "the batch handle"));
     MI_TRY(guidance_check(net, b, rec != nullptr, "the batch handle"));
+    MI_TRY(symmetry_check(b, noise != nullptr, rec != nullptr, "the batch handle"));
     hipStream_t s = (hipStream_t)stream;
     const int N = b->N, B = b->B;
     if (N == 0 || B == 0) return MI_OK;
@@ -316,6 +319,7 @@ int mi_sampler_run(mi_net* net, mi_batch* b, const float* coef_host, int T, int 
     hipLaunchKernelGGL(wrap_inplace_kernel, dim3(cdiv(n3, 256)), dim3(256), 0, s, frac, (int64_t)n3);
     // replacement conditioning (condition.hip): the known part of the state at the level the chain starts from, before it is recorded
     if (b->cond_on) MI_TRY(condition_impose(b, t_start, seed, atom_types, frac, lattices, nullptr, nullptr, nullptr, s));
+    if (b->symc_on) MI_TRY(symmetry_impose(b, atom_types, frac, lattices, s));   // (behind the condition, before the state is recorded)
     if (rec) {  // traj[t_start] = current state (diffusion.py:287-293)
         if (rec->atom_types) MI_HIP(hipMemcpyAsync(rec->atom_types + t_start * nA, atom_types, nA * 4, hipMemcpyDeviceToDevice, s));
         if (rec->lattices) MI_HIP(hipMemcpyAsync(rec->lattices + t_start * b9, lattices, b9 * 4, hipMemcpyDeviceToDevice, s));

@@ -466,7 +466,7 @@ class DiffCSPModule(nn.Module):
     @torch.no_grad()
     def sample(self, batch, diff_ratio=1.0, step_lr=1e-5, seed=0, noise=None, init=None, record=False, t_start=None,
                t_stop=0, node_offset=0, graph_offset=0, streams=None, rec_sink=None, condition=None, likelihood=None, resample=None,
-               guidance=None, steer=None, classifier=None):
+               guidance=None, steer=None, classifier=None, symmetry=None):
         """DiffCSPModule.sample (diffusion.py:273-399).
 
         `rec_sink` (a list; with record=True): receives one (first crystal, first atom, buffers) per chain, in crystal order -- the
@@ -521,7 +521,29 @@ class DiffCSPModule(nn.Module):
         it.  Returns (final, traj, info): info = dict(levels, times, out [E][B]) from one read at the end.  ValueError by name before any
         device work: a predictor that is not noised, of another T / schedule or knn-style, streams > 1, `record`, `noise`, `condition`,
         `likelihood`, `resample`, `guidance`, `steer`, CSP mode, a property-conditioned prior.
+
+        `symmetry` = symmetry_constraint.SymmetryConstraint for the crystals of `batch` (it may BE `batch`): the state is projected
+        onto each crystal's group -- coordinates pulled back from the orbit representatives, the cell's metric averaged over the rotation
+        parts, the type rows shared inside an orbit -- at the start and after the predictor of every step, behind any condition; the
+        corrector is left alone.  Every state of the chain carries the group to float32 rounding.  The constraint is attached to the chain's
+        batch handles for this call and cleared afterwards, each stream group its crystals' slice.  With `condition` as well: a condition
+        on atom types alone, whose known types agree inside every orbit (checked on the host).  Returns (final, traj, info): info =
+        dict(cell_failures [B]), the crystals' counts of cell projections skipped for a non-finite or non-positive metric, from one read at
+        the end.  ValueError by name before any device work: `record`, `noise`, `likelihood`, `resample`, `guidance`, `steer`,
+        `classifier`, CSP mode, atom counts that are not the batch's.
         """
+        if symmetry is not None:
+            for name, v in (("record=True", record), ("teacher-forced noise", noise is not None), ("likelihood", likelihood is not None),
+                            ("resample", resample is not None), ("guidance", guidance is not None), ("steer", steer is not None),
+                            ("classifier", classifier is not None), ("CSP mode", self.keep_lattice or self.keep_coords)):
+                if v:
+                    raise ValueError(f"sample: symmetry together with {name} is not supported -- a projected state has no likelihood under "
+                                     "the recorded proposal, and the projection moves what the other keyword holds fixed (DESIGN 57)")
+            counts = batch.num_atoms_list if isinstance(batch, CrystalBatch) else [int(v) for v in batch.num_atoms.tolist()]
+            if [int(v) for v in symmetry.num_atoms.tolist()] != counts:
+                raise ValueError("sample: the symmetry constraint's atom counts are not the batch's")
+            if condition is not None:
+                symmetry.check_condition(condition, "sample")
         if classifier is not None:
             from . import classifier as _classifier
             _classifier.check_call(self, classifier, streams=streams, record=record, noise=noise, condition=condition, likelihood=likelihood,
@@ -555,9 +577,16 @@ class DiffCSPModule(nn.Module):
             raise ValueError("sample: the condition's atom counts are not the batch's")
         if self.__dict__.get("_knn_pending"):
             self.check_graph()   # (the verdict of the previous call's chains: by now they have long finished)
+        sym = None if symmetry is None else (symmetry, [])   # (the constraint, the sink of its handles' failure counts)
+
+        def result(final, traj):   # with a constraint: (final, traj, info)
+            if sym is None:
+                return final, traj
+            import numpy as np
+            return final, traj, dict(cell_failures=np.concatenate(sym[1]) if sym[1] else np.zeros(0, np.int64))
         if isinstance(batch, CrystalBatch):
-            return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink,
-                                    condition=condition, likelihood=lik, resample=rj, guidance=gd)
+            return result(*self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink,
+                                            condition=condition, likelihood=lik, resample=rj, guidance=gd, symmetry=sym))
         if (self.keep_lattice or self.keep_coords) and init is None and condition is None:
             # CSP mode (diffusion.py:283-287): the known part of the structure replaces the drawn initial state and is never moved
             cb0 = self.crystal_batch(batch, node_offset, graph_offset)
@@ -579,8 +608,8 @@ class DiffCSPModule(nn.Module):
             streams = 4 if e_total >= 98304 else 3 if e_total >= 49152 else 2 if e_total >= 16384 else 1
         streams = max(1, min(int(streams), len(na)))
         if streams == 1:
-            return self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink,
-                                    condition=condition, likelihood=lik, resample=rj, guidance=gd)
+            return result(*self._sample_one(batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, rec_sink=rec_sink,
+                                            condition=condition, likelihood=lik, resample=rj, guidance=gd, symmetry=sym))
         key = ("split", streams, tuple(na))
         parts = getattr(batch, "_mi_split", {}).get(key)
         if parts is None:  # contiguous crystal groups, cached on the batch object like its CrystalBatch
@@ -631,7 +660,10 @@ class DiffCSPModule(nn.Module):
         # ... and so is guidance: every group's handle gets its crystals' rows and a partner handle of its own
         guided = [] if gd is None else [(self.crystal_batch(parts[k], node_offset + n0[k], graph_offset + g0[k]), (node_offset + n0[k], graph_offset + g0[k]),
                                          gd[1][g0[k]:g0[k + 1]], gd[2][g0[k]:g0[k + 1]]) for k in range(streams)]
-        with self._conditioned(conds, likelihood=lik, resample=rj), self._guided(guided, gd):
+        # ... and so is a symmetry constraint, inside the condition's scope
+        syms = [] if sym is None else [(self.crystal_batch(parts[k], node_offset + n0[k], graph_offset + g0[k]), sym[0].slice(g0[k], g0[k + 1]))
+                                       for k in range(streams)]
+        with self._conditioned(conds, likelihood=lik, resample=rj), self._guided(guided, gd), self._symmetric(syms, None if sym is None else sym[1]):
             out = workers.run(run, streams)
         if rec_sink is not None:
             for k, sk in enumerate(sinks):
@@ -663,7 +695,7 @@ class DiffCSPModule(nn.Module):
                     pass
             return dict(atom_types=state[2], frac_coords=state[0], lattices=state[1], num_atoms=idx[2], batch_idx=idx[1])
         traj = {t: (final_state() if t == t_stop else merge([o[1][t] for o in out])) for t in out[0][1]}
-        return traj[t_stop], traj
+        return result(traj[t_stop], traj)
 
     def check_graph(self):
         """knn edge style: wait for the chains enqueued by `sample` and raise (MI_ECAPACITY, as a RuntimeError) if a neighbour list built inside one of them
@@ -709,6 +741,25 @@ class DiffCSPModule(nn.Module):
                     resampling.clear(cb)
 
     @contextlib.contextmanager
+    def _symmetric(self, pairs, sink):
+        """Attach each (batch handle, SymmetryConstraint) of `pairs` for the duration of the block and clear the handles afterwards, whatever
+        happens inside (_conditioned's contract: one drain of the device first).  Behind the block the device is drained once more and the
+        handles' failure counters are read into `sink`, in the order of `pairs`."""
+        if not pairs:
+            yield
+            return
+        from . import symmetry_constraint as SC
+        torch.cuda.synchronize(self.device)
+        try:
+            for cb, c in pairs:
+                c.attach(cb)
+            yield
+            sink.extend(SC.failures(cb) for cb, _ in pairs)
+        finally:
+            for cb, _ in pairs:
+                SC.SymmetryConstraint.clear(cb)
+
+    @contextlib.contextmanager
     def _guided(self, handles, gd):
         """Attach guidance to each (batch handle, (node offset, graph offset), yhat rows, have rows) of `handles` for the duration of the block
         and clear the handles afterwards, whatever happens inside (_conditioned's contract: one drain of the device first).  gd =
@@ -734,7 +785,7 @@ class DiffCSPModule(nn.Module):
                 G.clear(cb)
 
     def _sample_one(self, batch, step_lr, seed, noise, init, record, t_start, t_stop, node_offset, graph_offset, inplace=None, drawn=False,
-                    rec_sink=None, condition=None, likelihood=False, resample=None, guidance=None):
+                    rec_sink=None, condition=None, likelihood=False, resample=None, guidance=None, symmetry=None):
         """One chain over one CrystalBatch on the current stream.
 
         Returns (traj[t_stop], traj) like the reference.  `traj` holds every step only when
@@ -778,7 +829,8 @@ class DiffCSPModule(nn.Module):
             rec = _lib.SamplerRecord(*(rec_t[k].data_ptr() for k in ("atom_types", "frac_coords", "lattices", "frac_coords_mid",
                                                                      "log_prob_l", "log_prob_t", "log_prob_x")))
         with self._conditioned([] if condition is None else [(cb, condition)], likelihood=likelihood, resample=resample), \
-                self._guided([] if guidance is None else [(cb, (node_offset, graph_offset), guidance[1], guidance[2])], guidance):
+                self._guided([] if guidance is None else [(cb, (node_offset, graph_offset), guidance[1], guidance[2])], guidance), \
+                self._symmetric([] if symmetry is None else [(cb, symmetry[0])], None if symmetry is None else symmetry[1]):
             _lib.check(lib.mi_sampler_run(self.decoder._h, cb._h, coef.numpy().ctypes.data_as(C.POINTER(C.c_float)), T, t_start, t_stop,
                                           _ptr(self.time_embedding.freqs), seed, C.byref(nz) if nz is not None else None,
                                           C.byref(rec) if rec is not None else None, _ptr(a), _ptr(x), _ptr(l), _stream()),

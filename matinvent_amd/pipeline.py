@@ -108,7 +108,8 @@ class MatInvent(ReinL):
         energies; the synthesizability metric is out of scope.
         sample_cfg.target_compositions_dict (a list of {symbol: count}) reaches the sampler with the other keys: the loop then samples
         crystals of those formulas only (replacement conditioning) and fine-tunes on them -- a fixed-formula RL loop.
-        sample_cfg.resample_times / sample_cfg.jump_length reach it the same way: the conditioned chains make RePaint's jumps."""
+        sample_cfg.resample_times / sample_cfg.jump_length reach it the same way: the conditioned chains make RePaint's jumps.
+        sample_cfg.symmetry_template / sample_cfg.symmetry_fix_types too: every crystal is sampled under the template's space group."""
         rank, world = rank_world()
         kw = {k: v for k, v in self.sample_cfg.items() if k not in ("filter", "mlip_opt", "geometric_filter")}
         if self.sample_steps is not None:   # (the sampler builds the agent's strided view; ft_step stays on the agent and its trained grid)
@@ -269,6 +270,8 @@ class MatInventPG(MatInvent):
         refuse_steer("MatInventPG", **{"sample_cfg.steer": merged.get("steer")})   # 
         from .classifier import refuse as refuse_classifier
         refuse_classifier("MatInventPG", **{"sample_cfg.classifier": merged.get("classifier")})   # 
+        from .symmetry_constraint import refuse as refuse_symmetry
+        refuse_symmetry("MatInventPG", **{f"sample_cfg.{k}": merged.get(k) for k in ("symmetry_template", "symmetry_fix_types")})   # 
         if kwargs.get("div_filter"):
             raise ValueError("MatInventPG: div_filter=True is not built -- the diversity filter penalises the rewards that rank a top-k, and the "
                              "policy gradient has no top-k (use pipeline=mat_invent)")

@@ -43,7 +43,7 @@ class DiffCSPSampler:
 
     def generate(self, model, batch_size=None, num_batches=None, sample_steps=None, condition=None, target_compositions_dict=None,
                  resample_times=None, jump_length=None, properties_to_condition_on=None, diffusion_guidance_factor=None, steer=None,
-                 classifier=None, **kwargs) -> Tuple[List[CrystalData], list]:
+                 classifier=None, symmetry_template=None, symmetry_fix_types=False, **kwargs) -> Tuple[List[CrystalData], list]:
         """sample.py:148-201.  Extra kwargs (`max_num`, `filter`, ...) are tolerated like the reference.
         `sample_steps` = S: the chains run on S of the model's T trained steps (model.respaced(S)); None: all of them.
         As in the reference, every batch is sampled but only the LAST batch's outputs are unpacked
@@ -65,7 +65,12 @@ class DiffCSPSampler:
         guidance, or more than one rank.
         `classifier` (DiffCSPModule.sample's `classifier`): a classifier.ClassifierGuidance, or the mapping of
         sample_cfg.classifier (ClassifierGuidance.from_config).  The guided steps and the predictor's outputs along the last batch's chain
-        are left in `self.last_classifier`.  ValueError: together with steer, a condition, resampling, guidance, or more than one rank."""
+        are left in `self.last_classifier`.  ValueError: together with steer, a condition, resampling, guidance, or more than one rank.
+        `symmetry_template` (DiffCSPModule.sample's `symmetry`): a crystal record, or the path of a JSON file holding one
+        (symmetry_constraint.load_template); every one of the batch_size x num_batches crystals is sampled under the template's space group
+        and Wyckoff multiplicities (SymmetryConstraint.template), with the template's atom count.  `symmetry_fix_types`: its species are
+        fixed too, by a condition on the atom types.  The cell-projection failure counts of the last batch are left in
+        `self.last_symmetry`.  ValueError: together with a condition, resampling, guidance, steer or classifier."""
         batch_size = batch_size or self.batch_size
         num_batches = num_batches or self.num_batches
         assert batch_size is not None and num_batches is not None
@@ -93,6 +98,19 @@ class DiffCSPSampler:
             guide = Guidance({k: float(v) for k, v in dict(properties_to_condition_on).items()}, diffusion_guidance_factor or 0.0)
         elif diffusion_guidance_factor:
             raise ValueError("DiffCSPSampler.generate: diffusion_guidance_factor needs properties_to_condition_on")
+        constraint = None
+        if symmetry_template is not None:
+            from .symmetry_constraint import SymmetryConstraint, load_template
+            for name, v in (("a condition", condition is not None), ("resample_times", resample is not None), ("properties_to_condition_on", guide is not None),
+                            ("steer", steer is not None), ("classifier", classifier is not None)):
+                if v:
+                    raise ValueError(f"DiffCSPSampler.generate: symmetry_template together with {name} is not supported")
+            record = load_template(symmetry_template) if isinstance(symmetry_template, (str, bytes)) or hasattr(symmetry_template, "__fspath__") else symmetry_template
+            constraint = SymmetryConstraint.template(record, batch_size, device=getattr(model, "device", "cuda"))
+            if symmetry_fix_types:
+                condition = constraint.condition(types=True)
+        elif symmetry_fix_types:
+            raise ValueError("DiffCSPSampler.generate: symmetry_fix_types needs symmetry_template")
         rank, world = int(kwargs.get("rank", 0)), int(kwargs.get("world_size", 1))
         if steer is not None:
             from .steering import Steering
@@ -111,12 +129,15 @@ class DiffCSPSampler:
         model = _strided(model, sample_steps)
         model.eval()
         from .dist import collectives_on
-        if condition is not None:   # the atom counts are the condition's: nothing is drawn, so every rank holds the same vector
+        if constraint is not None:   # the atom counts are the template's
+            from types import SimpleNamespace
+            dataset = SimpleNamespace(num_atoms=np.tile(constraint.num_atoms.numpy(), num_batches))
+        elif condition is not None:   # the atom counts are the condition's: nothing is drawn, so every rank holds the same vector
             from types import SimpleNamespace
             dataset = SimpleNamespace(num_atoms=np.tile(condition.num_atoms.numpy(), batch_size * num_batches // len(condition)))
         else:
             dataset = SampleDataset(total_num=batch_size * num_batches, dataset=self.num_atoms_distribution)
-        if condition is None and (world > 1 or collectives_on()):
+        if condition is None and constraint is None and (world > 1 or collectives_on()):
             # the atom counts come from numpy's unseeded GLOBAL generator (sample.py:123): every rank would draw a different
             # vector, while the shard ranges and the global noise offsets below assume ONE.  Rank 0's draw is the batch.
             from .dist import broadcast_object
@@ -141,6 +162,10 @@ class DiffCSPSampler:
             if condition is not None:
                 c0 = bi * batch_size % len(condition)
                 cond = condition.slice(c0 + lo, c0 + hi)
+            if constraint is not None:
+                outputs, _, self.last_symmetry = model.sample(counts, step_lr=step_lr, seed=self.seed, node_offset=node_off, graph_offset=lo, condition=cond,
+                                                              symmetry=constraint.slice(lo, hi))
+                continue
             outputs, _ = model.sample(counts, step_lr=step_lr, seed=self.seed, node_offset=node_off, graph_offset=lo, condition=cond,
                                       **({} if resample is None else {"resample": resample}), **({} if guide is None else {"guidance": guide}))
         data_list = _unpack(model, counts, outputs, node_off, lo, where="DiffCSPSampler.generate")
@@ -212,14 +237,15 @@ def _refuse_condition(where, condition):
                          "unconditioned proposal, not a trajectory likelihood (DESIGN 31)")
 
 
-def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_steps=None, condition=None, resample=None, steer=None, classifier=None):
+def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_steps=None, condition=None, resample=None, steer=None, classifier=None,
+               symmetry=None):
     """sample.py:249-309: sample with the trajectory recorded and return (sample_list, sample_traj), restricted to the crystals that
     pass invalid_filter.  sample_traj[k] is the step t = T - k (t = T .. 2) with the reference's keys (atom_types, lattices, frac_coords,
     frac_coords_mid, num_atoms, timesteps, log_prob_{t,x,l}; host tensors) plus next_frac_coords / next_lattices / next_atom_types --
     the state at t - 1 -- so that any element can go straight to DiffCSPModule.forward_logprb.  (The reference's own sample_mdp unpacks
     invalid_filter into the wrong values and never builds the next_* keys that forward_logprb reads.)
     A strided view (DiffCSPModule.respaced), or sample_steps = S which builds it: T is the view's S and `timesteps` are step indices --
-    what the VIEW's forward_logprb takes.  A `condition` is refused (ValueError), and so is `resample`."""
+    what the VIEW's forward_logprb takes.  A `condition` is refused (ValueError), and so are `resample` and `symmetry`."""
     from .filters import invalid_filter
     from .resampling import refuse
     refuse("sample_mdp", resample=resample)
@@ -227,6 +253,8 @@ def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_st
     refuse_steer("sample_mdp", steer=steer)   # (a resampled particle system has no per-chain trajectory likelihood)
     from .classifier import refuse as refuse_classifier
     refuse_classifier("sample_mdp", classifier=classifier)   # (the record would be the unshifted proposal's)
+    from .symmetry_constraint import refuse as refuse_symmetry
+    refuse_symmetry("sample_mdp", symmetry=symmetry)   # (a projected state has no likelihood under the recorded proposal)
     from .guidance import refuse_latent
     refuse_latent(model, "sample_mdp")
     _refuse_condition("sample_mdp", condition)
@@ -301,7 +329,7 @@ class Rollout:
 
 
 def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=True, sample_steps=None, condition=None, likelihood=None,
-                   resample=None, steer=None, classifier=None):
+                   resample=None, steer=None, classifier=None, symmetry=None):
     """Sample like sample_mdp (same atom-count draw, seed handling and invalid_filter; geometric_filter=False keeps every crystal) and
     keep the kept crystals' whole trajectories on the device as a Rollout -- compacted once per chain straight from the sampler's stacked
     record buffers, without the per-step dict or a host copy.  Returns (sample_list, rollout).  The policy gradient (policy.pg_step)
@@ -312,7 +340,7 @@ def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=T
     condition=c (for `sample_size` crystals), likelihood="free" (DESIGN 36): the chains are conditioned on c, whose atom counts replace the
     draw; rollout.lp_old is the masked record (the predictor terms of the known elements left out) and rollout.condition the kept
     crystals' part of c, which pg_step re-evaluates under.  CSP mode stays refused.  `resample` is refused (ValueError): a resampled chain
-    visits levels more than once and a rollout holds one visit."""
+    visits levels more than once and a rollout holds one visit.  `symmetry` is refused too."""
     from .conditioning import check_likelihood
     from .filters import invalid_filter
     from .resampling import refuse
@@ -321,6 +349,8 @@ def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=T
     refuse_steer("sample_rollout", steer=steer)   # 
     from .classifier import refuse as refuse_classifier
     refuse_classifier("sample_rollout", classifier=classifier)   # 
+    from .symmetry_constraint import refuse as refuse_symmetry
+    refuse_symmetry("sample_rollout", symmetry=symmetry)   # 
     from .guidance import refuse_latent
     refuse_latent(model, "sample_rollout")
     if not check_likelihood("sample_rollout", likelihood, condition):
