@@ -516,6 +516,23 @@ SYMC_SIGNATURES = {
     "mi_symmetry_failures": (_I, [_P, C.POINTER(_I)]),
 }
 
+# composition validity, include/matinvent_hip_chem.h (charge neutrality and the Pauling test over a user-supplied element table)
+CHEM_MAX_Z, CHEM_MAX_STATES, CHEM_MAX_ELEMS, CHEM_CHUNK, CHEM_MAX_GRID, CHEM_MAX_BATCH, CHEM_DEFAULT_MAX_COMBOS = 118, 32, 8, 65536, 2048, 4096, 10_000_000   # include/matinvent_hip_chem.h
+(CHEM_ENUMERATED, CHEM_ELEMENTAL, CHEM_ALLOY, CHEM_BAD_INPUT, CHEM_TOO_MANY_ELEMENTS, CHEM_UNKNOWN_ELEMENT, CHEM_NO_STATES,
+ CHEM_TOO_MANY_COMBOS) = range(8)
+
+
+class ChemArgs(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("present", "n_states", "ox", "eneg_rank", "is_metal", "node_off", "atom_types", "workspace", "valid", "status", "n_elems",
+                                           "elems", "counts", "n_combos", "n_neutral", "n_valid", "first", "first_ox", "atom_ox")] +
+                [("max_combos", C.c_int64)] + [(k, C.c_int) for k in ("B", "N", "use_pauling_test", "include_alloys")])
+
+
+CHEM_SIGNATURES = {
+    "mi_chem_workspace": (_L, [_I, _L]),
+    "mi_chem_validity": (_I, [C.POINTER(ChemArgs), _P]),
+}
+
 # the substrate matcher, include/matinvent_hip_zsl.h (Zur-McGill superlattices, minimal coincident interface area)
 ZSL_MAX_MULT, ZSL_MAX_MILLER, ZSL_TABLE, ZSL_ROW_D, ZSL_ROW_I = 63, 8, 3276, 10, 20   # include/matinvent_hip_zsl.h
 ZSL_OK, ZSL_NO_MATCH, ZSL_MULT_CAP, ZSL_REDUCE_CAP, ZSL_BAD_CELL = 0, 1, 2, 3, 4
@@ -548,7 +565,7 @@ ZSL_SIGNATURES = {
 # every extension table: load() binds SIGNATURES plus these (a new extension header adds its table here)
 EXTENSION_SIGNATURES = (TRAJ_SIGNATURES, PG_SIGNATURES, PG_KL_SIGNATURES, OPTIM_SIGNATURES, STRIDE_SIGNATURES, COND_SIGNATURES, FP_SIGNATURES,
                         DPO_SIGNATURES, MATCH_SIGNATURES, LIK_SIGNATURES, RESAMPLE_SIGNATURES, POOL_SIGNATURES, EMA_SIGNATURES, GUIDANCE_SIGNATURES,
-                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, SYM_SIGNATURES, SYM_CONV_SIGNATURES, SYM_REFINE_SIGNATURES, SYMC_SIGNATURES, ZSL_SIGNATURES, PHONON_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
+                        SCALAR_SIGNATURES, STEER_SIGNATURES, INPUT_GRAD_SIGNATURES, RELAX_SIGNATURES, HULL_SIGNATURES, SMATCH_SIGNATURES, SYM_SIGNATURES, SYM_CONV_SIGNATURES, SYM_REFINE_SIGNATURES, SYMC_SIGNATURES, CHEM_SIGNATURES, ZSL_SIGNATURES, PHONON_SIGNATURES, VIB_SIGNATURES, ELASTIC_SIGNATURES,
                         PRETRAIN_SIGNATURES)
 
 _lib = None

@@ -16,7 +16,7 @@ LIB = os.path.join(HERE, "lib", "libmatinvent_hip.so")
 OBJ = os.path.join(HERE, "lib", "obj")
 SOURCES = ["cspnet.hip", "node_chain.hip", "node_bwd.hip", "edge_stage.hip", "sampler.hip", "backward.hip", "graph.hip", "gemnet.hip", "traj_logprob.hip", "optim.hip", "ema.hip", "stride.hip", "condition.hip", "fingerprint.hip", "dpo.hip", "fp_match.hip", "resample.hip", "pretrain.hip", "pool.hip", "guidance.hip", "scalar_head.hip", "steer.hip", "input_grad.hip", "relax.hip", "hull.hip", "vib.hip", "elastic.hip", "struct_match.hip", "symmetry.hip", "phonon.hip", "zsl.hip"]
 # the units added since: tests/test_zsl_host.py holds SOURCES at its 31 entries, so a later unit joins this list and ALL_SOURCES is what is built
-MORE_SOURCES = ["sym_conv.hip", "sym_refine.hip", "sym_constraint.hip"]
+MORE_SOURCES = ["sym_conv.hip", "sym_refine.hip", "sym_constraint.hip", "chem_valid.hip"]
 ALL_SOURCES = SOURCES + MORE_SOURCES
 # the public headers, include/*.h: every object and the library depend on all of them (a new extension header is picked up by itself)
 PUBLIC_HEADERS = sorted(os.path.join(HERE, "..", "include", f) for f in os.listdir(os.path.join(HERE, "..", "include")) if f.endswith(".h"))

@@ -379,18 +379,34 @@ def unique_mask(records, fingerprints=None, fp_tol=FP_TOL, fp_args=None, device=
     return mask
 
 
+def validity_first(smact, flt, data_list, structures, energies=None):
+    """The metric "validity" of UNFilter / SUNFilter: `smact`'s mask over the records, `flt` over the valid ones, `valid_frac` in the metrics."""
+    records = structures if structures is not None else data_list
+    n = len(records)
+    keep = np.asarray(smact(records), dtype=bool) if n else np.zeros(0, bool)
+    pick = lambda xs: [x for x, k in zip(xs, keep) if k] if xs is not None else None
+    data, strucs, metrics = flt(pick(data_list), pick(structures), None if energies is None else np.asarray(energies)[keep])
+    return data, strucs, dict(metrics, valid_frac=float(keep.mean()) if n else 0.0)
+
+
 class UNFilter:
     """The reference's filter call shape, `flt(data_list, structures, energies=None) -> (data, structures, metrics)`, for
     sample_cfg.filter: keeps the crystals that are unique within the batch and novel against the bank.  `reference_path`: a .npz bank
     (scripts/build_fingerprint_bank.py).  remember=True adds every crystal the filter passes to the bank, so that "novel" also means not
     yet scored in this run, across loops.  metrics: a subset of {"unique", "novel"}; "validity" is accepted and ignored (invalid_filter has
-    run already).  One fingerprint call serves both masks."""
+    run already) -- unless `smact` is given (a chemistry.SmactValidity, a path or its config mapping): then the composition test
+    runs first, on the (relaxed) structures as the reference's second test does (opt_filter.py:179-180), only the valid ones go on to the
+    other metrics -- whose fractions are then taken over the valid ones -- and `valid_frac` is reported.  One fingerprint call serves both masks."""
 
     NEEDS = {"stable": "a MatterSim relaxation and a convex-hull reference set downloaded from a hub",
              "synthesizable": "a synthesizability model and its downloaded weights"}
 
     def __init__(self, metrics=("unique", "novel"), reference_path=None, remember=False, fp_tol=FP_TOL, fp_args=None, device="cuda",
-                 matcher="fingerprint", ltol=0.2, stol=0.3, angle_tol=5.0, primitive=False, symprec=0.1, **ignored):
+                 matcher="fingerprint", ltol=0.2, stol=0.3, angle_tol=5.0, primitive=False, symprec=0.1, smact=None, **ignored):
+        if smact is not None:
+            from .chemistry import make_smact
+            smact = make_smact(smact)
+        self.smact = smact
         if matcher not in ("fingerprint", "structure"):
             raise ValueError(f"UNFilter: matcher {matcher!r} is neither 'fingerprint' nor 'structure'")
         self.matcher, self.ltol, self.stol, self.angle_tol = matcher, float(ltol), float(stol), float(angle_tol)
@@ -402,6 +418,7 @@ class UNFilter:
             if m not in ("unique", "novel", "validity"):
                 raise ValueError(f"UNFilter: metric {m!r} is none of 'unique', 'novel', 'validity'")
         self.metrics = tuple(m for m in ("unique", "novel") if m in metrics)
+        self.validity = "validity" in metrics and self.smact is not None
         self.remember, self.fp_tol, self.fp_args, self.device = bool(remember), float(fp_tol), dict(fp_args or {}), device
         self.reference_path, self._bank = reference_path, None
 
@@ -426,6 +443,11 @@ class UNFilter:
         return uniq, novel, float(rms[hit].mean()) if hit.any() else float("nan")
 
     def __call__(self, data_list, structures, energies=None):
+        if not self.validity:
+            return self._filter(data_list, structures, energies)
+        return validity_first(self.smact, self._filter, data_list, structures, energies)
+
+    def _filter(self, data_list, structures, energies=None):
         records = structures if structures is not None else data_list
         n = len(records)
         bank = self.bank

@@ -36,6 +36,10 @@ class ReinL:
             raise ValueError("sample_cfg.sample_steps is the DiffCSP suite's strided reverse chain; the MatterGen suite has `sampling_steps` "
                              "of its own")
         self.sampler = model_suite.get_sampler()
+        self.smact = None   # sample_cfg.smact: a path or {table, use_pauling_test, include_alloys, max_combos}; built once, its table on first use
+        if self.sample_cfg.get("smact") is not None:
+            from .chemistry import make_smact
+            self.smact = make_smact(self.sample_cfg.get("smact"))
         self.models_dir = os.path.join(save_dir, "models")
         self.sample_dir = os.path.join(save_dir, "samples")
         os.makedirs(self.models_dir, exist_ok=True)
@@ -68,6 +72,13 @@ class ReinL:
         data = [d for d, k in zip(sample_data, ok) if k]
         strucs = [s for s, k in zip(sample_struc, ok) if k]
         return data, strucs, np.asarray(rewards)[ok].astype(float), {k: np.asarray(v)[ok] for k, v in prop_dict.items()}
+
+    def _smact_log(self):
+        """{"smact_valid_frac": the share of the latest sampled batch whose composition passed}, or {} without sample_cfg.smact."""
+        if self.smact is None:
+            return {}
+        last = self.smact.last
+        return {"smact_valid_frac": float(last.valid.mean()) if last is not None and len(last) else float("nan")}
 
 
 class MatInvent(ReinL):
@@ -109,16 +120,20 @@ class MatInvent(ReinL):
         sample_cfg.target_compositions_dict (a list of {symbol: count}) reaches the sampler with the other keys: the loop then samples
         crystals of those formulas only (replacement conditioning) and fine-tunes on them -- a fixed-formula RL loop.
         sample_cfg.resample_times / sample_cfg.jump_length reach it the same way: the conditioned chains make RePaint's jumps.
-        sample_cfg.symmetry_template / sample_cfg.symmetry_fix_types too: every crystal is sampled under the template's space group."""
+        sample_cfg.symmetry_template / sample_cfg.symmetry_fix_types too: every crystal is sampled under the template's space group.
+        sample_cfg.smact never reaches the sampler: its mask is ANDed into the pre-filter and smact_valid_frac is logged."""
         rank, world = rank_world()
-        kw = {k: v for k, v in self.sample_cfg.items() if k not in ("filter", "mlip_opt", "geometric_filter")}
+        kw = {k: v for k, v in self.sample_cfg.items() if k not in ("filter", "mlip_opt", "geometric_filter", "smact")}
         if self.sample_steps is not None:   # (the sampler builds the agent's strided view; ft_step stays on the agent and its trained grid)
             logging.info(f"sampling on {self.sample_steps} of the model's {self.agent.beta_scheduler.timesteps} steps")
         data, strucs = self.sampler.generate(model=self.agent, rank=rank, world_size=world, **kw)
         if self.sample_cfg.get("geometric_filter", True):  # the reference always filters (mat_invent.py:78-79)
             n_all = len(data)
-            data, strucs = invalid_filter(data, strucs)
+            data, strucs = invalid_filter(data, strucs, **({} if self.smact is None else {"smact": self.smact}))
             logging.info(f"geometric pre-filter kept {len(data)} of {n_all} samples")
+        elif self.smact is not None:
+            keep = self.smact(data)
+            data, strucs = [d for d, k in zip(data, keep) if k], [s for s, k in zip(strucs, keep) if k]
         xyz = None
         if rank == 0 and getattr(self, "sample_dir", None):
             xyz = write_extxyz(strucs, os.path.join(self.sample_dir, f"step_{self.step:0>4d}_valid.extxyz"))
@@ -127,7 +142,7 @@ class MatInvent(ReinL):
         metrics = {}
         if callable(flt):
             data, strucs, metrics = flt(data, strucs, energies)
-        metrics = dict(metrics, **relax_log)
+        metrics = dict(metrics, **relax_log, **self._smact_log())
         max_num = self.sample_cfg.get("max_num")
         if max_num and len(strucs) > max_num:
             data, strucs = data[:max_num], strucs[:max_num]
@@ -215,12 +230,20 @@ class Baseline(ReinL):
         self.agent = self.model_suite.load_model().to(self.device)
 
     def rl_step(self):
-        kw = {k: v for k, v in self.sample_cfg.items() if k not in ("filter", "mlip_opt", "geometric_filter")}
+        kw = {k: v for k, v in self.sample_cfg.items() if k not in ("filter", "mlip_opt", "geometric_filter", "smact")}
         data, strucs = self.sampler.generate(model=self.agent, **kw)
+        if self.smact is not None:   # (the composition test alone; the baseline has no geometric pre-filter)
+            keep = self.smact(data)
+            data, strucs = [d for d, k in zip(data, keep) if k], [s for s, k in zip(strucs, keep) if k]
+            if not data:
+                logging.warning("no sample passed the composition test; nothing is scored in this loop")
+                if self.logger is not None:
+                    self.logger.log(self._smact_log(), step=self.step)
+                return
         strucs, _, relax_log = self.relax_step(strucs)
         data, strucs, rewards, props = self.reward_step(data, strucs, None, f"step_{self.step:0>4d}")
         if self.logger is not None:
-            self.logger.log(dict({"reward mean": rewards.mean(), "reward std": rewards.std()}, **relax_log), step=self.step)
+            self.logger.log(dict({"reward mean": rewards.mean(), "reward std": rewards.std()}, **relax_log, **self._smact_log()), step=self.step)
 
     def run_rl(self):
         for step in range(self.rl_epoch):
@@ -302,7 +325,7 @@ class MatInventPG(MatInvent):
         self.sampler.seed += 1
         data, rollout = sample_rollout(int(self.sample_cfg.batch_size), self.agent, seed=self.sampler.seed,
                                        geometric_filter=bool(self.sample_cfg.get("geometric_filter", True)), sample_steps=self.sample_steps,
-                                       **self._condition_kwargs())
+                                       **self._condition_kwargs(), **({} if self.smact is None else {"smact": self.smact}))
         strucs = [data2struc(d) for d in data]
         logging.info(f"rollout kept {len(data)} samples" + (f" over {rollout.T} steps" if self.sample_steps is not None else ""))
         xyz = None
@@ -314,7 +337,7 @@ class MatInventPG(MatInvent):
         metrics = {}
         if callable(flt):
             data, strucs, metrics = flt(data, strucs, energies)
-        metrics = dict(metrics, **relax_log)
+        metrics = dict(metrics, **relax_log, **self._smact_log())
         max_num = self.sample_cfg.get("max_num")
         if max_num and len(strucs) > max_num:
             data, strucs = data[:max_num], strucs[:max_num]

@@ -351,13 +351,20 @@ class PyMatGen:
     lists the substrate's planes (the reference uses (1, 0, 0) for Si, GaAs and InP), `zsl` holds substrates.ZSL arguments; NaN on any
     status other than OK, as the reference's `except` branch does.  conventional=True puts every film into its conventional cell first
     (symmetry.conventional_records), as the reference does before its substrate analysis (:136-160; its own cell conventions
-    are [UPSTREAM-UNVERIFIED]); it excludes primitive=True."""
+    are [UPSTREAM-UNVERIFIED]); it excludes primitive=True.  `abundance` / `log_abundance` are the mass-fraction-weighted crustal abundance
+    of the elements and its log10, from the `abundance` column of the user's element table (`element_table`: a chemistry.ElementTable or
+    the path of its JSON file): NaN when an element's value is missing or the weighted value is not positive, as the reference's `abundance_crust` (:23-44).  `price` stays refused."""
 
     def __init__(self, root_dir="rewards", task="density", hhi_table=None, substrate=None, substrate_millers=None, zsl=None, primitive=False, device="cuda",
-                 conventional=False, **kwargs):
-        assert task in ("density", "hhi", "mcia"), f"task {task!r} needs pymatgen / SMACT data that this build does not carry"
+                 conventional=False, element_table=None, **kwargs):
+        assert task in ("density", "hhi", "mcia", "abundance", "log_abundance"), f"task {task!r} needs pymatgen / SMACT data that this build does not carry"
         self.root_dir, self.task = root_dir, task
         self.hhi = None
+        if task in ("abundance", "log_abundance"):
+            from .chemistry import ElementTable
+            if element_table is None:
+                raise ValueError(f"task {task!r} needs element_table= (a chemistry.ElementTable or the path of its JSON file): no table is shipped")
+            self.element_table = element_table if isinstance(element_table, ElementTable) else ElementTable.load(element_table)
         if task == "mcia":
             import os
             from . import substrates
@@ -393,6 +400,13 @@ class PyMatGen:
             try:
                 if self.task == "density":
                     out.append(density(s.species, s.lengths, s.angles))
+                elif self.task in ("abundance", "log_abundance"):
+                    m = np.array([MASSES[int(z)] for z in s.species])
+                    ab = np.array([self.element_table.abundance[int(z)] for z in s.species])
+                    v = float((m / m.sum() * ab).sum())   # (an element without a value is NaN in the table)
+                    if not v > 0.0:
+                        raise ValueError("missing or non-positive abundance")
+                    out.append(float(np.log10(v)) if self.task == "log_abundance" else v)
                 else:
                     if self.hhi is None:
                         raise KeyError("no HHI table")

@@ -238,14 +238,15 @@ def _refuse_condition(where, condition):
 
 
 def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_steps=None, condition=None, resample=None, steer=None, classifier=None,
-               symmetry=None):
+               symmetry=None, smact=None):
     """sample.py:249-309: sample with the trajectory recorded and return (sample_list, sample_traj), restricted to the crystals that
     pass invalid_filter.  sample_traj[k] is the step t = T - k (t = T .. 2) with the reference's keys (atom_types, lattices, frac_coords,
     frac_coords_mid, num_atoms, timesteps, log_prob_{t,x,l}; host tensors) plus next_frac_coords / next_lattices / next_atom_types --
     the state at t - 1 -- so that any element can go straight to DiffCSPModule.forward_logprb.  (The reference's own sample_mdp unpacks
     invalid_filter into the wrong values and never builds the next_* keys that forward_logprb reads.)
     A strided view (DiffCSPModule.respaced), or sample_steps = S which builds it: T is the view's S and `timesteps` are step indices --
-    what the VIEW's forward_logprb takes.  A `condition` is refused (ValueError), and so are `resample` and `symmetry`."""
+    what the VIEW's forward_logprb takes.  A `condition` is refused (ValueError), and so are `resample` and `symmetry`.
+    smact: a chemistry.SmactValidity, handed to invalid_filter."""
     from .filters import invalid_filter
     from .resampling import refuse
     refuse("sample_mdp", resample=resample)
@@ -262,7 +263,7 @@ def sample_mdp(sample_size, model, device=None, step_lr=-1, seed=None, sample_st
     counts, step_lr = _prelude(sample_size, model, step_lr)
     outputs, traj = model.sample(counts, step_lr=step_lr, seed=_draw_seed(seed), record=True)
     data_list = _unpack(model, counts, outputs)
-    valid = invalid_filter(data_list, return_mask=True)
+    valid = invalid_filter(data_list, return_mask=True, **({} if smact is None else {"smact": smact}))
     sample_list = [d for d, ok in zip(data_list, valid) if ok]
     valid_idx = torch.as_tensor(np.where(valid)[0], dtype=torch.long)
     atom_bool = torch.as_tensor(valid)[traj[0]["batch_idx"].cpu()]
@@ -329,7 +330,7 @@ class Rollout:
 
 
 def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=True, sample_steps=None, condition=None, likelihood=None,
-                   resample=None, steer=None, classifier=None, symmetry=None):
+                   resample=None, steer=None, classifier=None, symmetry=None, smact=None):
     """Sample like sample_mdp (same atom-count draw, seed handling and invalid_filter; geometric_filter=False keeps every crystal) and
     keep the kept crystals' whole trajectories on the device as a Rollout -- compacted once per chain straight from the sampler's stacked
     record buffers, without the per-step dict or a host copy.  Returns (sample_list, rollout).  The policy gradient (policy.pg_step)
@@ -340,7 +341,8 @@ def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=T
     condition=c (for `sample_size` crystals), likelihood="free" (DESIGN 36): the chains are conditioned on c, whose atom counts replace the
     draw; rollout.lp_old is the masked record (the predictor terms of the known elements left out) and rollout.condition the kept
     crystals' part of c, which pg_step re-evaluates under.  CSP mode stays refused.  `resample` is refused (ValueError): a resampled chain
-    visits levels more than once and a rollout holds one visit.  `symmetry` is refused too."""
+    visits levels more than once and a rollout holds one visit.  `symmetry` is refused too.
+    smact: a chemistry.SmactValidity, handed to invalid_filter; with geometric_filter=False its mask alone decides."""
     from .conditioning import check_likelihood
     from .filters import invalid_filter
     from .resampling import refuse
@@ -367,7 +369,10 @@ def sample_rollout(sample_size, model, step_lr=-1, seed=None, geometric_filter=T
     sink = []
     outputs, _ = model.sample(counts, step_lr=step_lr, seed=_draw_seed(seed), record=True, rec_sink=sink, condition=condition, likelihood=likelihood)
     data_list = _unpack(model, counts, outputs)
-    valid = invalid_filter(data_list, return_mask=True) if geometric_filter else np.ones(len(data_list), dtype=bool)
+    if smact is None:
+        valid = invalid_filter(data_list, return_mask=True) if geometric_filter else np.ones(len(data_list), dtype=bool)
+    else:
+        valid = invalid_filter(data_list, return_mask=True, smact=smact) if geometric_filter else np.asarray(smact(data_list), dtype=bool)
     sample_list = [d for d, ok in zip(data_list, valid) if ok]
     valid = torch.as_tensor(np.asarray(valid, dtype=bool))
     na = counts.num_atoms

@@ -286,12 +286,18 @@ class SUNFilter:
     """The reference's filter call shape, `flt(data_list, structures, energies) -> (data, structures, metrics)`, for sample_cfg.filter: keeps
     the crystals that are stable against the phase bank, unique within the batch and novel against the fingerprint bank.  `phase_path`: a
     .npz of scripts/build_phase_bank.py; `reference_path`, `remember`, `fp_tol`, `fp_args`: the `novelty.UNFilter` it owns.  metrics: a
-    subset of {"stable", "unique", "novel"}; "validity" is accepted and ignored.  "stable" needs the energies of sample_cfg.mlip_opt."""
+    subset of {"stable", "unique", "novel"}; "validity" is accepted and ignored -- unless `smact` is given (a chemistry.SmactValidity, a path
+    or its config mapping): then the composition test runs first on the (relaxed) structures, only the valid ones go on, and
+    `valid_frac` is reported (novelty.validity_first).  "stable" needs the energies of sample_cfg.mlip_opt."""
 
     def __init__(self, metrics=("stable", "unique", "novel"), phase_path=None, reference_path=None, threshold=STABLE_THRESHOLD, per_atom=True,
                  remember=False, fp_tol=None, fp_args=None, device="cuda", bank=None, matcher="fingerprint", ltol=0.2, stol=0.3, angle_tol=5.0, primitive=False, symprec=0.1,
-                 **ignored):
+                 smact=None, **ignored):
         from .novelty import UNFilter
+        if smact is not None:
+            from .chemistry import make_smact
+            smact = make_smact(smact)
+        self.smact = smact
         from .structure import FP_TOL
         metrics = [str(m) for m in metrics]
         for m in metrics:
@@ -300,6 +306,7 @@ class SUNFilter:
             if m not in ("stable", "unique", "novel", "validity"):
                 raise ValueError(f"SUNFilter: metric {m!r} is none of 'stable', 'unique', 'novel', 'validity'")
         self.metrics = tuple(m for m in ("stable", "unique", "novel") if m in metrics)
+        self.validity = "validity" in metrics and self.smact is not None
         if "stable" in self.metrics and phase_path is None and bank is None:
             raise ValueError("SUNFilter: metric 'stable' needs phase_path (a .npz phase bank of scripts/build_phase_bank.py) or bank")
         if not (np.isfinite(threshold)):
@@ -317,6 +324,12 @@ class SUNFilter:
         return self._bank
 
     def __call__(self, data_list, structures, energies=None):
+        if not self.validity:
+            return self._filter(data_list, structures, energies)
+        from .novelty import validity_first
+        return validity_first(self.smact, self._filter, data_list, structures, energies)
+
+    def _filter(self, data_list, structures, energies=None):
         from . import novelty
         records = structures if structures is not None else data_list
         n = len(records)

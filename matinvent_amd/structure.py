@@ -5,7 +5,7 @@ What the reference gets from pymatgen / ase on the sampler -> filter -> reward h
     the device from the sampler's final state (K18, `mi_structure_check`), and `geometric_mask`, the cell test of
     pipeline/filters/opt_filter.py:53-55 (`max(abc) < 25`) plus the distance / volume thresholds of the external
     `structure_validity` check (0.5 A, 0.1 A^3 -- [UPSTREAM-UNVERIFIED] defaults of mattergen's evaluator).  The charge-
-    neutrality test (SMACT) of `invalid_filter` needs its element database and is not reproduced.
+    neutrality test (SMACT) of `invalid_filter` is matinvent_amd.chemistry, over an element table the user supplies.
   * `lattice_matrix` (pymatgen `Lattice.from_parameters` orientation), `volume`, `density`, `composition`,
     `reduced_formula` -- the keys memory/replay_buffer.py:38 and memory/ltm.py:31 dedupe on;
   * `write_extxyz` / `write_cif` -- pipeline/utils/save.py:32-41 writes extxyz through ase; `read_extxyz`, the inverse of the former.
