@@ -160,9 +160,11 @@ int mi_debug_rt_clock(void* dev_buffer, int ext, int skip);
  * row epilogue for every launch; 2 behaves as 1 and the bits above bit 1 are ignored.  Returns the previous setting. */
 int mi_debug_set_rt_lean(int on);
 /* Phase clock of that kernel (measurement only): device buffer of [row tiles][8] 64-bit s_memtime stamps (start, first operand chunk
- * landed, main loop done, epilogue done); nullptr = off. */
+ * landed, main loop done, epilogue done; word 6: head of the main loop's third iteration from its end); nullptr = off. */
 int mi_debug_edge2_clock(void* dev_buffer);
-int mi_debug_edge1_clock(void* dev_buffer);   /* the same for the first edge GEMM: [row tiles x column quarters][8] stamps */
+/* The same for the first edge GEMM: [row tiles x column quarters][8] stamps; self-edge workgroup d of the launch writes its entry and its
+ * exit into words 4 and 5 of row d (while d is below the number of rows).  scripts/edge_fixed_costs.py reads both. */
+int mi_debug_edge1_clock(void* dev_buffer);
 /* Phase clock of that launch (measurement only): a device buffer of [workgroups][16] 64-bit words that every workgroup fills with
  * s_memtime stamps at its phase boundaries; nullptr (default) = off. */
 int mi_debug_node_chain_clock(void* dev_buffer);

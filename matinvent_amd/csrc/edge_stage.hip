@@ -24,17 +24,22 @@
 #include <cstdlib>
 #include "net.h"
 #include "gemm_split.h"
+#include "loop_waits.h"
 // The k-loops of edge_gemm1b_kernel, edge_gemm2b_kernel and gemm_rt_kernel run with EVERY memory operation under manual control: LDS fragment
 // reads and the weight ring as inline asm with counted lgkmcnt / vmcnt waits, and a bare s_barrier.  With compiler-visible LDS reads and
 // __syncthreads() the compiler drains the LDS-DMA in flight in front of every barrier (`s_waitcnt vmcnt(1)`: it cannot tell that the k-tiles
 // requested two and three iterations ahead target other stages than the one being read).  (Those forms measured 1-4 % slower: docs/rounds/round4.md
 // 18.4e, profiles/r4_asm_lds_ab.log; last present at 3e3d930.)
 #define MI_LOOP_BARRIER() __builtin_amdgcn_s_barrier()
-// Weight slice of a k-step: requested four steps ahead; the vector-memory operations this wave issues after it and before its use are the
-// other three slices in flight (12) and the LDS-DMA pieces of the two k-tile heads in between (8) -- vector loads retire in order, so at most
-// 20 outstanding means it has arrived.  (The last three k-tiles and the first drain the counter at their head: fewer operations behind a slice
-// there.)  The slice rides through the wait as read-write operands, so that no MFMA can be scheduled in front of it.
-#define MI_RING_WAIT(w) asm volatile("s_waitcnt vmcnt(20)" : "+v"((w)[0][0]), "+v"((w)[0][1]), "+v"((w)[1][0]), "+v"((w)[1][1]))
+// Phase-clock stamp inside a k-loop, at an iteration's head (no LDS read in flight there): the clock read with its own wait in ONE statement --
+// s_memtime returns out of order with LDS reads, so left pending it would blur the loop's counted lgkmcnt waits -- into scalar registers; the
+// kernel stores them behind the loop (a store inside it would only be one more operation behind everything in flight: a wait too early).
+#define MI_LOOP_STAMP(t) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory")
+// Weight slice of a k-step: requested four steps ahead; vector loads retire in order, so it has arrived once no more operations are outstanding
+// than this wave issued behind it -- in the steady state the other three slices in flight and the LDS-DMA pieces of the two k-tile heads in
+// between, fewer while the loop fills and drains (loop_waits.h has the count for every k-step).  The slice rides through the wait as
+// read-write operands, so that no MFMA can be scheduled in front of it.
+#define MI_RING_WAIT(w, n) asm volatile("s_waitcnt vmcnt(%4)" : "+v"((w)[0][0]), "+v"((w)[0][1]), "+v"((w)[1][0]), "+v"((w)[1][1]) : "n"(n))
 
 namespace mi {
 
@@ -150,6 +155,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:1024" : "=v"(w[t][1]) : "v"(voffw[t]), "s"(rsw_s), "s"(soff));
         }
     };
+    // (inside the loop the slot is a read-write operand of its own reload: the slice stays in the registers the prologue gave it, from the
+    //  first request to the last product -- no new value for the register allocator to place somewhere else)
+    auto ring_reload = [&](int ks, u32x4 (&w)[2][2]) {
+        const int soff = __builtin_amdgcn_readfirstlane(ks * 2048);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(w[t][0]) : "v"(voffw[t]), "s"(rsw_s), "s"(soff));
+            asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:1024" : "+v"(w[t][1]) : "v"(voffw[t]), "s"(rsw_s), "s"(soff));
+        }
+    };
 #pragma unroll
     for (int d = 0; d < D; ++d) ring_load(d, ring[d]);
 
@@ -201,31 +216,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
     };
     static_assert(D == 4, "two k-tiles of ring per unrolled pair of iterations");
-    // vector loads retire in order.  Per k-tile this wave issues 4 DMA pieces (k-tile kt + 3) and then 8 ring loads; k-tile kt's pieces were
-    // issued three iterations ago, i.e. at least 8 + 12 + 12 operations ago: vmcnt(24) leaves the younger ones in flight.
-#pragma unroll 1
-    for (int kt = 0; kt < KT; kt += 2) {
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-            const int k = kt + h2;
-            // (the last three k-tiles have fewer loads behind them -- no further DMA, the ring runs dry: drain)
-            if (k == 0 || k >= KT - 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-            MI_LOOP_BARRIER();   // k-tile k has landed for every wave; every wave is done with the stage k-tile k + 3 goes to (= that of k - 1)
-            if (k == 0) stamp();
-            if (k + 3 < KT) dma_tile(k + 3, (k + 3) & 3);
-            f16x8 af[4][2];
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                read_a(k & 3, s2, af);
-                MI_RING_WAIT(ring[2 * h2 + s2]);
-                mma(ring[2 * h2 + s2], af);
-                if (2 * k + s2 + D < KS) ring_load(2 * k + s2 + D, ring[2 * h2 + s2]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
+    // Every wait of the loop is counted, from the fill to the drain (loop_waits.h: per k-tile this wave issues 4 DMA pieces -- k-tile k + 3 --
+    // and then 2 x 4 ring loads; a k-tile or a slice has landed once no more operations are outstanding than were issued behind it).  The
+    // phase clock keeps its two in-loop stamps in scalar registers and stores them behind the loop (MI_LOOP_STAMP).
+    unsigned long long t_first = 0, t_tail = 0;
+    auto head = [&](int k, auto hw, auto dma, auto mark) {
+        if (decltype(mark)::value == LW_MARK_TAIL && a.clk) MI_LOOP_STAMP(t_tail);   // head of the third iteration from the end
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(hw)::value) : "memory");
+        MI_LOOP_BARRIER();   // k-tile k has landed for every wave; every wave is done with the stage k-tile k + 3 goes to (= that of k - 1)
+        if (decltype(mark)::value == LW_MARK_FIRST && a.clk) MI_LOOP_STAMP(t_first);
+        if (decltype(dma)::value) dma_tile(k + 3, (k + 3) & 3);
+    };
+    auto step = [&](int k, auto slot, auto rw, auto issue) {
+        constexpr int SL = decltype(slot)::value, s2 = SL & 1;
+        f16x8 af[4][2];
+        read_a(k & 3, s2, af);
+        MI_RING_WAIT(ring[SL], decltype(rw)::value);
+        mma(ring[SL], af);
+        if (decltype(issue)::value) ring_reload(2 * k + s2 + D, ring[SL]);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    lw_k_loop<4, 4, D, lw_form(KT)>(KT, head, step);
+    stamp_i = 2;
     stamp();
+    if (a.clk && tid == 0) {
+        a.clk[(size_t)(tile * 2 + half) * 8 + 1] = t_first;
+        a.clk[(size_t)(tile * 2 + half) * 8 + 6] = t_tail;
+    }
 
     if constexpr (SAVE_Z) {
         // training forward: Z2 = acc / (s_A s_W) + b2 is kept for the backward pass.  In the result layout that would be 128 four-byte
@@ -339,7 +356,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // N % 256 == 0; the column blocks of a row tile run on the same XCD.  Same products, same k order, same epilogue function as the
 // 128 x 128 plane kernel: bit-identical results.
 // ------------------------------------------------------------------------------------------------------------------------------------
-template <bool EXT, bool LEAN = false>
+template <bool EXT, bool LEAN, int FORM>   // FORM: the unrolled form of the k-loop (loop_waits.h lw_form: 0 = K >= 256, else K / 32)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_rt_kernel(Planes A, const u16* __restrict__ Wf, int M, int N, int K,
                                                                                                  PlanesEpilogue pe, unsigned long long* __restrict__ clk) {
     const int KS = K >> 4, KT = K >> 5;
@@ -389,6 +406,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:1024" : "=v"(w[t][1]) : "v"(voffw[t]), "s"(rsw_s), "s"(soff));
         }
     };
+    // (inside the loop the slot is a read-write operand of its own reload: the slice stays in the registers the prologue gave it, from the
+    //  first request to the last product -- no new value for the register allocator to place somewhere else)
+    auto ring_reload = [&](int ks, u32x4 (&w)[2][2]) {
+        const int soff = __builtin_amdgcn_readfirstlane(ks * 2048);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(w[t][0]) : "v"(voffw[t]), "s"(rsw_s), "s"(soff));
+            asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:1024" : "+v"(w[t][1]) : "v"(voffw[t]), "s"(rsw_s), "s"(soff));
+        }
+    };
 #pragma unroll
     for (int d = 0; d < 4; ++d) ring_load(d, ring[d]);
 
@@ -430,29 +457,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i][term == 0 ? 1 : 0], __builtin_bit_cast(f16x8, w[j][term == 1 ? 1 : 0]), acc[i][j], 0, 0, 0);
         }
     };
-    // (waits as in edge_gemm2b_kernel: k-tile k's DMA pieces were issued at least 8 + 12 + 12 vector-memory operations ago.  EXT: touching the
-    //  epilogue's row-wise operands 3 / 5 / 8 k-tiles before the loop ends measured no gain -- docs/rounds/round4.md 18.4; last present at 3e3d930)
-#pragma unroll 1
-    for (int kt = 0; kt < KT; kt += 2) {
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-            const int k = kt + h2;
-            if (k == 0 || k >= KT - 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-            MI_LOOP_BARRIER();
-            if (k == 0) stamp();
-            if (k + 3 < KT) dma_tile(k + 3, (k + 3) & 3);
-            f16x8 af[4][2];
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                read_a(k & 3, s2, af);
-                MI_RING_WAIT(ring[2 * h2 + s2]);
-                mma(ring[2 * h2 + s2], af);
-                if (2 * k + s2 + 4 < KS) ring_load(2 * k + s2 + 4, ring[2 * h2 + s2]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
+    // (waits as in edge_gemm2b_kernel, counted for any even KT: loop_waits.h.  EXT: touching the epilogue's row-wise operands 3 / 5 / 8 k-tiles
+    //  before the loop ends measured no gain -- docs/rounds/round4.md 18.4; last present at 3e3d930)
+    unsigned long long t_first = 0;
+    auto head = [&](int k, auto hw, auto dma, auto mark) {
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(hw)::value) : "memory");
+        MI_LOOP_BARRIER();
+        if (decltype(mark)::value == LW_MARK_FIRST && clk) MI_LOOP_STAMP(t_first);
+        if (decltype(dma)::value) dma_tile(k + 3, (k + 3) & 3);
+    };
+    auto step = [&](int k, auto slot, auto rw, auto issue) {
+        constexpr int SL = decltype(slot)::value, s2 = SL & 1;
+        f16x8 af[4][2];
+        read_a(k & 3, s2, af);
+        MI_RING_WAIT(ring[SL], decltype(rw)::value);
+        mma(ring[SL], af);
+        if (decltype(issue)::value) ring_reload(2 * k + s2 + 4, ring[SL]);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    lw_k_loop<4, 4, 4, FORM>(KT, head, step);
+    if (clk && tid == 0) clk[(size_t)blockIdx.x * 8 + 1] = t_first;
+    stamp_i = 2;
     __syncthreads();   // every wave is done with the stages: they become the epilogue's per-wave patches
     stamp();
     if constexpr (LEAN) planes_epilogue_lean<4, 2>(pe, acc, tile, cb * 256 + wave * 64, M, lane);
@@ -515,7 +540,7 @@ __global__ void pack_frag_wff_pair_kernel(const float* __restrict__ W1, int edge
 // A wave owns all 128 pairs of the tile and one 32-column MFMA tile: every activation fragment read from LDS feeds ONE column tile, 8 ds_read_b128
 // per 12 MFMAs.  (A 128 x 256-tile form with 512 registers per lane and a 2 x 2-wave form of 64 x 64 measured 11-13 % slower, a one-accumulator-set
 // form that multiplies the sine half twice no faster: docs/rounds/round3.md 16.3a, round4.md 18.4e; last present at 3e3d930.)
-template <int D, bool WIDE>
+template <int D, bool WIDE, int FORM>   // FORM: the unrolled form of the k-loop (loop_waits.h lw_form: 0 = K >= 256, else K / 32)
 __device__ __forceinline__ void edge_gemm1_body(const Planes& A, const u16* __restrict__ Wf, int M, int N, int K, PlanesEpilogue& pe, unsigned long long* clk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -525,7 +550,8 @@ __device__ __forceinline__ void edge_gemm1_body(const Planes& A, const u16* __re
     const int KT = K / 32, KS = K / 16, nq = N / WGC;   // k-tiles, k-steps, column blocks of a row tile
     const int wm = wave / WN, wn = wave % WN;
     const int id = blockIdx.x;
-    // this layer's M1 scale from the absmax slots and the weight bounds; workgroup 0 publishes all six scales (as the plane GEMM does)
+    // this layer's M1 scale from the absmax slots and the weight bounds; workgroup 0 publishes all six scales (as the plane GEMM does) -- with
+    // self edges in the launch that is the first self-edge workgroup, without them pair tile 0: edge_gemm2b_kernel and the node chain read them
     float cps_local = 0.f;
     auto eval_scales = [&]() {
         if (pe.sc_pq) {
@@ -538,35 +564,87 @@ __device__ __forceinline__ void edge_gemm1_body(const Planes& A, const u16* __re
             }
         }
     };
-    // (evaluated in front of the operand loads: behind them -- so that its four dependent scalar loads would run under the LDS-DMA latency --
-    //  measured 2 k cycles SLOWER per workgroup, 4.9 k -> 6.9 k to the first barrier: profiles/r5_index_loads_ab.log)
-    eval_scales();
-    if (pe.diag_C0 && id >= pe.diag_block0) {  // self edges: eight nodes per workgroup, a thread per column pair (d = 0: the Fourier term is C0)
-        const float cps = cps_local != 0.f ? cps_local : pe.Cp.s();
-        const int n0 = (id - pe.diag_block0) * 8, n1 = n0 + 8 < pe.diag_nodes ? n0 + 8 : pe.diag_nodes;
+    // ---- self edges (d = 0: the Fourier term is the constant C0): the FIRST pe.diag_blocks workgroups of the launch, eight nodes each ----
+    // They take slots when the launch starts instead of queueing behind its pair tiles (behind them they were the launch's last arrivals, each
+    // holding half a CU for a chain of dependent loads).  A thread owns one (node, 8-column chunk) item, two of them at H = 512, and requests
+    // every load of both up front -- from clamped indices, masked at the use, as the pair epilogue's index loads are -- so that one memory
+    // latency (two for G, whose row hangs on node2graph) covers the workgroup's life; a plane's eight halfs leave as ONE 16-byte store (eight
+    // consecutive columns of a 32-column piece are contiguous in the tile-blocked layout).  Same sums in the same order as before:
+    // v = C0 + ((P_i + P_j) + G), silu_fast, pl_split_pair.  They use no LDS (the launch's dynamic LDS is per launch: they hold it unused).
+    if (id < pe.diag_blocks) {
+        if (id * 8 >= pe.diag_nodes) return;   // (diag_blocks is rounded up to a multiple of 8: see the pair tiles' mapping below)
+        const bool clocked = clk && tid == 0 && id < (int)gridDim.x - pe.diag_blocks;   // phase clock: entry / exit of self-edge workgroup d in slots 4 / 5 of row d
+        if (clocked) clk[(size_t)id * 8 + 4] = __builtin_amdgcn_s_memtime();
+        const int nch = N >> 3, items = 8 * nch;   // 8-column chunks of a node, items of the workgroup
         const float* PQ = pe.ep.row_bias;
         const int ldpq = pe.ep.ld_row_bias;
-        for (int f = 2 * tid; f < N; f += 512) {
-            const float c0 = pe.diag_C0[f], c1 = pe.diag_C0[f + 1];
-            for (int i = n0; i < n1; ++i) {
-                const int e = pe.diag_e[i], g = pe.diag_node2graph[i];
-                const float* G = pe.ep.row_bias3 + (size_t)g * pe.ep.ld_row_bias3;
-                const float v0 = c0 + ((PQ[(size_t)i * ldpq + f] + PQ[(size_t)i * ldpq + N + f]) + G[f]);
-                const float v1 = c1 + ((PQ[(size_t)i * ldpq + f + 1] + PQ[(size_t)i * ldpq + N + f + 1]) + G[f + 1]);
-                if (pe.ep.pre_act) {   // (training forward: the self edges' pre-activation is on the tape too)
-                    pe.ep.pre_act[(size_t)e * pe.ep.ld_pre + f] = v0;
-                    pe.ep.pre_act[(size_t)e * pe.ep.ld_pre + f + 1] = v1;
-                }
-                unsigned p[3];
-                pl_split_pair(silu_fast(v0), silu_fast(v1), cps, p);
+        for (int base = 0; base < items; base += 512) {
+            bool ok[2];
+            int col[2], e[2], g[2];
+            f32x4 pi[2][2], pj[2][2], c0[2][2], gv[2][2];
 #pragma unroll
-                for (int k = 0; k < NPL; ++k) *reinterpret_cast<unsigned*>(pe.Cp.base + pe.Cp.elem(e, f, k)) = p[k];
+            for (int u = 0; u < 2; ++u) {   // index loads first: G's address waits for them alone
+                const int item = base + tid + 256 * u, itc = item < items ? item : items - 1;
+                const int node = id * 8 + itc / nch, nc = node < pe.diag_nodes ? node : pe.diag_nodes - 1;
+                ok[u] = item < items && node < pe.diag_nodes;
+                col[u] = (itc % nch) * 8;
+                e[u] = pe.diag_e[nc];
+                g[u] = pe.diag_node2graph[nc];
+                const float* pr = PQ + (size_t)nc * ldpq + col[u];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    pi[u][h] = *reinterpret_cast<const f32x4*>(pr + 4 * h);
+                    pj[u][h] = *reinterpret_cast<const f32x4*>(pr + N + 4 * h);
+                    c0[u][h] = *reinterpret_cast<const f32x4*>(pe.diag_C0 + col[u] + 4 * h);
+                }
             }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const float* gr = pe.ep.row_bias3 + (size_t)g[u] * pe.ep.ld_row_bias3 + col[u];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) gv[u][h] = *reinterpret_cast<const f32x4*>(gr + 4 * h);
+            }
+            if (base == 0) eval_scales();   // (its scalar loads and arithmetic run under the requests)
+            const float cps = cps_local != 0.f ? cps_local : pe.Cp.s();
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                if (!ok[u]) continue;
+                f32x4 v[2];
+                u32x4 o[NPL];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) v[h][t] = c0[u][h][t] + ((pi[u][h][t] + pj[u][h][t]) + gv[u][h][t]);
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        unsigned p[3];
+                        pl_split_pair(silu_fast(v[h][2 * t]), silu_fast(v[h][2 * t + 1]), cps, p);
+#pragma unroll
+                        for (int k = 0; k < NPL; ++k) o[k][2 * h + t] = p[k];
+                    }
+                }
+                if (pe.ep.pre_act) {   // (training forward: the self edges' pre-activation is on the tape too)
+                    float* z = pe.ep.pre_act + (size_t)e[u] * pe.ep.ld_pre + col[u];
+                    *reinterpret_cast<f32x4*>(z) = v[0];
+                    *reinterpret_cast<f32x4*>(z + 4) = v[1];
+                }
+#pragma unroll
+                for (int k = 0; k < NPL; ++k) *reinterpret_cast<u32x4*>(pe.Cp.base + pe.Cp.elem(e[u], col[u], k)) = o[k];
+            }
+        }
+        if (clocked) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the stores of thread 0's wave have left: the exit stamp closes the workgroup's memory work)
+            clk[(size_t)id * 8 + 5] = __builtin_amdgcn_s_memtime();
         }
         return;
     }
-    // XCD-aware mapping: the column quarters of a row tile run on the same XCD
-    const int slot = id >> 3, qt = slot % nq, tile = (slot / nq) * 8 + (id & 7);
+    // (evaluated in front of the operand loads: behind them -- so that its four dependent scalar loads would run under the LDS-DMA latency --
+    //  measured 2 k cycles SLOWER per workgroup, 4.9 k -> 6.9 k to the first barrier: profiles/r5_index_loads_ab.log)
+    eval_scales();
+    // XCD-aware mapping: the column quarters of a row tile run on the same XCD.  Workgroups go round-robin to the 8 XCDs by their launch id;
+    // the self-edge workgroups in front are a multiple of 8, so the pair tiles' ids are shifted by whole rounds and id & 7 is still the XCD.
+    const int pid = id - pe.diag_blocks;
+    const int slot = pid >> 3, qt = slot % nq, tile = (slot / nq) * 8 + (pid & 7);
     const int row0 = tile * 128;
     if (row0 >= M) return;
     int stamp_i = 0;
@@ -602,6 +680,11 @@ __device__ __forceinline__ void edge_gemm1_body(const Planes& A, const u16* __re
         asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(w[0][0]) : "v"(voffw[0]), "s"(rsw_s), "s"(soff));
         asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:1024" : "=v"(w[0][1]) : "v"(voffw[0]), "s"(rsw_s), "s"(soff));
     };
+    auto ring_reload = [&](int ks, u32x4 (&w)[NJ][2]) {   // (read-write, as in edge_gemm2b_kernel: the slot keeps its registers)
+        const int soff = __builtin_amdgcn_readfirstlane(ks * 2048);
+        asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(w[0][0]) : "v"(voffw[0]), "s"(rsw_s), "s"(soff));
+        asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:1024" : "+v"(w[0][1]) : "v"(voffw[0]), "s"(rsw_s), "s"(soff));
+    };
 #pragma unroll
     for (int d = 0; d < D; ++d) ring_load(d, ring[d]);
 
@@ -625,8 +708,8 @@ __device__ __forceinline__ void edge_gemm1_body(const Planes& A, const u16* __re
         MI_RD128(af[3][0], 3 * 2048);        MI_RD128(af[3][1], 3 * 2048 + 8192);
 #undef MI_RD128
     };
-    auto mma = [&](u32x4 (&w)[NJ][2], f16x8 (&af)[MI][2]) {   // terms (a1, b0), (a0, b1), (a0, b0)
-        asm volatile("s_waitcnt vmcnt(14)" : "+v"(w[0][0]), "+v"(w[0][1]));
+    auto mma = [&](u32x4 (&w)[NJ][2], f16x8 (&af)[MI][2], auto rw) {   // terms (a1, b0), (a0, b1), (a0, b0); the slice has landed at vmcnt(rw)
+        asm volatile("s_waitcnt vmcnt(%2)" : "+v"(w[0][0]), "+v"(w[0][1]) : "n"(decltype(rw)::value));
 #pragma unroll
         for (int ip = 0; ip < 2; ++ip) {   // two row blocks at a time, each pair behind the wait for its own fragments
             if (ip == 0) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(af[0][0]), "+v"(af[0][1]), "+v"(af[1][0]), "+v"(af[1][1]));
@@ -640,48 +723,51 @@ __device__ __forceinline__ void edge_gemm1_body(const Planes& A, const u16* __re
     };
     static_assert(D == 4, "two k-tiles of ring per unrolled pair of iterations");
     const int khalf = KT / 2;
-    // (vmcnt: per k-tile this wave issues 4 DMA pieces and then 4 ring loads; k-tile kt's pieces were issued three iterations ago, i.e. at
-    //  least 4 + 8 + 8 operations ago: vmcnt(16) leaves the younger ones in flight; the last three k-tiles drain)
-#pragma unroll 1
-    for (int kt = 0; kt < KT; kt += 2) {
+    // Every wait of the loop is counted, from the fill to the drain (loop_waits.h: per k-tile this wave issues 4 DMA pieces and then 2 x 2 ring loads;
+    // vector memory operations retire in order, so a k-tile or a slice has landed once no more operations are outstanding than were issued behind
+    // it).  The phase clock keeps its two in-loop stamps in scalar registers and stores them behind the loop (MI_LOOP_STAMP).
+    unsigned long long t_first = 0, t_tail = 0;
+    auto head = [&](int k, auto hw, auto dma, auto mark) {
+        if (k == khalf) {   // the cosine half of K goes into the second accumulator set
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-            const int k = kt + h2;
-            if (k == khalf) {   // the cosine half of K goes into the second accumulator set
+            for (int i = 0; i < MI; ++i)
 #pragma unroll
-                for (int i = 0; i < MI; ++i)
+                for (int j = 0; j < NJ; ++j) {
+                    accS[i][j] = acc[i][j];
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        accS[i][j] = acc[i][j];
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-                    }
-            }
-            if (k == 0 || k >= KT - 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-            MI_LOOP_BARRIER();
-            if (k == 0) stamp();
-            if (k + 3 < KT) dma_tile(k + 3, (k + 3) & 3);
-            f16x8 af[MI][2];
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                read_a(k & 3, s2, af);
-                mma(ring[2 * h2 + s2], af);
-                if (2 * k + s2 + D < KS) ring_load(2 * k + s2 + D, ring[2 * h2 + s2]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+                }
         }
-    }
+        if (decltype(mark)::value == LW_MARK_TAIL && clk) MI_LOOP_STAMP(t_tail);   // head of the third iteration from the end
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(hw)::value) : "memory");
+        MI_LOOP_BARRIER();
+        if (decltype(mark)::value == LW_MARK_FIRST && clk) MI_LOOP_STAMP(t_first);
+        if (decltype(dma)::value) dma_tile(k + 3, (k + 3) & 3);
+    };
+    auto step = [&](int k, auto slot, auto rw, auto issue) {
+        constexpr int SL = decltype(slot)::value, s2 = SL & 1;
+        f16x8 af[MI][2];
+        read_a(k & 3, s2, af);
+        mma(ring[SL], af, rw);
+        if (decltype(issue)::value) ring_reload(2 * k + s2 + D, ring[SL]);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    lw_k_loop<4, 2 * NJ, D, FORM>(KT, head, step);
+    stamp_i = 2;
     stamp();
+    if (clk && tid == 0) {
+        clk[(size_t)(tile * nq + qt) * 8 + 1] = t_first;
+        clk[(size_t)(tile * nq + qt) * 8 + 6] = t_tail;
+    }
     __syncthreads();   // the epilogue's per-wave patches overlay the operand stages
     planes_epilogue_pairs<MI, NJ, WIDE>(pe, accS, acc, row0 + wm * MI * 32, qt * WGC + wn * 32 * NJ, M, N, lane, reinterpret_cast<float*>(smem) + wave * 2304, cps_local);
     stamp();
 }
 
-template <int D, bool WIDE = true>
+template <int D, bool WIDE, int FORM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void edge_gemm1b_kernel(Planes A, const u16* __restrict__ Wf, int M, int N, int K,
                                                                                                      PlanesEpilogue pe, unsigned long long* clk) {
-    edge_gemm1_body<D, WIDE>(A, Wf, M, N, K, pe, clk);
+    edge_gemm1_body<D, WIDE, FORM>(A, Wf, M, N, K, pe, clk);
 }
 
 unsigned long long* g_edge1_clk = nullptr;
@@ -696,21 +782,32 @@ int edge_gemm1(mi_net* net, const Planes& A, int layer, int M, PlanesEpilogue pe
     static std::once_flag once;
     static hipError_t attr_err = hipSuccess;
     std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)edge_gemm1b_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, EG2B_LDS);
-        if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute((const void*)edge_gemm1b_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, EG2B_LDS);
+        auto set = [](auto form) {
+            constexpr int F = decltype(form)::value;
+            if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute((const void*)edge_gemm1b_kernel<4, true, F>, hipFuncAttributeMaxDynamicSharedMemorySize, EG2B_LDS);
+            if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute((const void*)edge_gemm1b_kernel<4, false, F>, hipFuncAttributeMaxDynamicSharedMemorySize, EG2B_LDS);
+        };
+        set(LwInt<0>{});
+        set(LwInt<2>{});
+        set(LwInt<4>{});
+        set(LwInt<6>{});
     });
     MI_HIP(attr_err);
     const int H = net->H, K = 2 * net->Kh;
     count_mfma(M, H, K, MI_PLANES_TERMS);   // (pair rows x [sine block | cosine block] of the Fourier columns)
     pe.out_scale = 1.f / (A.scale * PL_SW);
     int nblk = (H / 128) * ((cdiv(M, 128) + 7) / 8 * 8);
-    if (pe.diag_C0) {
-        pe.diag_block0 = nblk;
-        nblk += cdiv(pe.diag_nodes, 8);
+    if (pe.diag_C0) {   // the self-edge workgroups come first (a multiple of 8: the pair tiles keep their XCDs)
+        pe.diag_blocks = (cdiv(pe.diag_nodes, 8) + 7) / 8 * 8;
+        nblk += pe.diag_blocks;
     }
     const u16* Wf = net->Wffc + (size_t)layer * ((size_t)H * K * 2);
-    if (pe.pair_wide) hipLaunchKernelGGL((edge_gemm1b_kernel<4>), dim3(nblk), dim3(256), EG2B_LDS, s, A, Wf, M, H, K, pe, g_edge1_clk);
-    else hipLaunchKernelGGL((edge_gemm1b_kernel<4, false>), dim3(nblk), dim3(256), EG2B_LDS, s, A, Wf, M, H, K, pe, g_edge1_clk);
+    lw_dispatch_form(K / 32, [&](auto form) {   // (one kernel instance per unrolled form of the k-loop: loop_waits.h)
+        constexpr int F = decltype(form)::value;
+        if (pe.pair_wide) hipLaunchKernelGGL((edge_gemm1b_kernel<4, true, F>), dim3(nblk), dim3(256), EG2B_LDS, s, A, Wf, M, H, K, pe, g_edge1_clk);
+        else hipLaunchKernelGGL((edge_gemm1b_kernel<4, false, F>), dim3(nblk), dim3(256), EG2B_LDS, s, A, Wf, M, H, K, pe, g_edge1_clk);
+        return 0;
+    });
     MI_KERNEL_CHECK();
     return MI_OK;
 }
@@ -789,13 +886,20 @@ int gemm_rt(const Planes& A, const u16* Wfrag, int M, int N, int K, const Planes
     static std::once_flag once;
     static hipError_t attr_err = hipSuccess;
     std::call_once(once, [] {
-        attr_err = hipFuncSetAttribute((const void*)gemm_rt_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, EG2B_NST * EG2B_STAGE);
-        if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute((const void*)gemm_rt_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, EG2B_NST * EG2B_STAGE);
-        if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute((const void*)gemm_rt_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, EG2B_NST * EG2B_STAGE);
+        auto set = [](auto form) {
+            constexpr int F = decltype(form)::value;
+            if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute((const void*)gemm_rt_kernel<false, false, F>, hipFuncAttributeMaxDynamicSharedMemorySize, EG2B_NST * EG2B_STAGE);
+            if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute((const void*)gemm_rt_kernel<true, false, F>, hipFuncAttributeMaxDynamicSharedMemorySize, EG2B_NST * EG2B_STAGE);
+            if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute((const void*)gemm_rt_kernel<false, true, F>, hipFuncAttributeMaxDynamicSharedMemorySize, EG2B_NST * EG2B_STAGE);
+        };
+        set(LwInt<0>{});
+        set(LwInt<2>{});
+        set(LwInt<4>{});
+        set(LwInt<6>{});
         if (const char* e = getenv("MI_RT_LEAN")) g_rt_lean = atoi(e) & 3;   // (A/B runs of whole test files: scripts/gpu_rt_lean_ab.sh; 2 behaves as 1)
     });
     MI_HIP(attr_err);
-    MI_CHECK(Wfrag && (N & 255) == 0 && (K & 63) == 0 && K >= 128 && A.KT >= K / 32, MI_EINVAL, "gemm_rt: N % 256, K % 64, K >= 128 and a fragment-order W operand");
+    MI_CHECK(Wfrag && (N & 255) == 0 && (K & 63) == 0 && K >= 64 && A.KT >= K / 32, MI_EINVAL, "gemm_rt: N % 256, K % 64, K >= 64 and a fragment-order W operand");
     if (M <= 0) return MI_OK;
     count_mfma(M, N, K, MI_PLANES_TERMS);
     const dim3 grid((N >> 8) * ((cdiv(M, 128) + 7) / 8 * 8));
@@ -813,9 +917,13 @@ int gemm_rt(const Planes& A, const u16* Wfrag, int M, int N, int K, const Planes
             if (g_rt_clk_ext >= 0) g_rt_clk = nullptr;   // one launch
         }
     }
-    if (g_rt_lean && planes_epilogue_is_lean(pe)) hipLaunchKernelGGL((gemm_rt_kernel<false, true>), grid, dim3(256), EG2B_NST * EG2B_STAGE, s, A, Wfrag, M, N, K, pe, clk);
-    else if (ext) hipLaunchKernelGGL(gemm_rt_kernel<true>, grid, dim3(256), EG2B_NST * EG2B_STAGE, s, A, Wfrag, M, N, K, pe, clk);
-    else hipLaunchKernelGGL(gemm_rt_kernel<false>, grid, dim3(256), EG2B_NST * EG2B_STAGE, s, A, Wfrag, M, N, K, pe, clk);
+    lw_dispatch_form(K / 32, [&](auto form) {   // (one kernel instance per unrolled form of the k-loop: loop_waits.h)
+        constexpr int F = decltype(form)::value;
+        if (g_rt_lean && planes_epilogue_is_lean(pe)) hipLaunchKernelGGL((gemm_rt_kernel<false, true, F>), grid, dim3(256), EG2B_NST * EG2B_STAGE, s, A, Wfrag, M, N, K, pe, clk);
+        else if (ext) hipLaunchKernelGGL((gemm_rt_kernel<true, false, F>), grid, dim3(256), EG2B_NST * EG2B_STAGE, s, A, Wfrag, M, N, K, pe, clk);
+        else hipLaunchKernelGGL((gemm_rt_kernel<false, false, F>), grid, dim3(256), EG2B_NST * EG2B_STAGE, s, A, Wfrag, M, N, K, pe, clk);
+        return 0;
+    });
     MI_KERNEL_CHECK();
     return MI_OK;
 }

@@ -589,6 +589,7 @@ struct PlanesEpilogue {
     const int* diag_e = nullptr;
     int diag_nodes = 0;
     int diag_block0 = 0;
+    int diag_blocks = 0;   // edge_gemm1b_kernel: its self-edge workgroups are the launch's first diag_blocks (a multiple of 8), not those from diag_block0 on
     // optional DEVICE-side row count: the launch is sized by an upper bound M (a capacity), the kernel works on min(M, *m_dev) rows.
     // Lets a chain of launches whose row count is produced on the device (the periodic graph's edge count) run without a host
     // round trip per evaluation (gemnet.hip, the sampler's forwards).
@@ -2203,7 +2204,7 @@ int gemm_planes(const Planes& A, const Planes& W, int M, int N, int K, const Pla
             else if (lat) hipLaunchKernelGGL((gemm_planes_lat_kernel<1>), dim3(nblk), dim3(256), planes_lds_bytes(1, 2), s, A, W, M, N, K, pe, 0);
             else hipLaunchKernelGGL((gemm_planes_kernel<1, 2>), dim3(nblk), dim3(256), planes_lds_bytes(1, 2), s, A, W, M, N, K, pe, 0);
         }
-    } else if (MI_PLANES_FP16 && W.frag && g_planes_rt && (g_planes_rt > 1 || ext) && (N & 255) == 0 && (K & 63) == 0 && K >= 128 && Ms >= g_planes_rt_min_rows &&
+    } else if (MI_PLANES_FP16 && W.frag && g_planes_rt && (g_planes_rt > 1 || ext) && (N & 255) == 0 && (K & 63) == 0 && K >= 64 && Ms >= g_planes_rt_min_rows &&
                planes_epilogue_is_rows(pe, N)) {
         return gemm_rt(A, W.frag, M, N, K, pe, ext, s);
     } else if (MI_PLANES_FP16 && (N & 255) == 0 && g_planes_big && (g_planes_big > 1 || !ext) && Ms >= g_planes_big_min_rows && planes_epilogue_is_rows(pe, N)) {
